@@ -15,9 +15,13 @@ as the API has no paired mode; each of the three workers takes its 16.7 M reads 
 With N ranks every rank aligns its own shard of that size (weak scaling, reads sharded by contiguous
 ordinal range, index replicated).  Rank 0 prints ONE JSON line.
 
-Beside `value` (reads resident in HBM -> hits resident in HBM) the line carries the metric as SURVEY 8d words
-it: `value_host_to_host` (pinned host reads -> host SoA hits through slx_align_batch) and `value_bamrecords`
-(the C++ class: UnalignedSequenceVector -> BamRecordPtrVector, on a bounded sample, tools/bamrec_bench.cpp).
+A plain run sets up, warms up, times the K steps and prints the line (`value`: reads resident in HBM -> hits
+resident in HBM; `ms_per_step`: one timed step).  `--full` adds what takes time of its own after the timed
+steps: the CPU baseline, the bit-for-bit oracle check of a sample (`--verify`), the rooflines' inputs, the
+N > 1 gather check, and the metric as SURVEY 8d words it: `value_host_to_host` (pinned host reads -> host SoA
+hits through slx_align_batch), `value_bamrecords` (the C++ class: UnalignedSequenceVector -> BamRecordPtrVector,
+tools/bamrec_bench.cpp), `value_per_call` and the bounded C5 leg.  `--dump-outputs DIR` writes the last timed
+step's results as .npy files (dump_hits / dump_contigs), so that two builds can be compared output for output.
 """
 import os
 # Four objects with streams of their own drive the GPU side by side in the C5 pipeline (two fml contexts, two aligners of three workers each): the HIP runtime maps
@@ -182,6 +186,71 @@ def compare(got, exp, m):
                                        exp["cigar"][exp["cig_off"][b0]:exp["cig_off"][b1]] if b1 > b0 else exp["cigar"][:0])
         same += bool(ok)
     return same / max(m, 1)
+
+
+DUMP_LIMIT = 48 << 20          # bytes of array data --dump-outputs writes at most (well under 64 MB with the .npy headers)
+DUMP_SEED = 20261016           # the samples --dump-outputs takes: the same rows in every run and every build
+
+
+def _hit_fields(res, rows, prefix=""):
+    """float64 copies (exact for these integers) of the SoA hits (include/seqlib_amd.h) of result rows `rows`, ascending: hits per row, every hit's fields,
+    the hits' CIGAR words"""
+    ho = np.asarray(res["hit_off"], dtype=np.int64)
+    lo, cnt = ho[rows], ho[rows + 1] - ho[rows]
+    hits = np.repeat(lo - np.cumsum(cnt) + cnt, cnt) + np.arange(cnt.sum())
+    co = np.asarray(res["cig_off"], dtype=np.int64)
+    c_lo, c_cnt = co[hits], co[hits + 1] - co[hits]
+    words = np.repeat(c_lo - np.cumsum(c_cnt) + c_cnt, c_cnt) + np.arange(c_cnt.sum())
+    out = {"n_hits": cnt}
+    for k in ("rid", "pos", "flag", "mapq", "score", "nm", "na", "n_cigar"):
+        out[k] = np.asarray(res[k])[hits]
+    out["cigar"] = np.asarray(res["cigar"])[words]
+    return {prefix + k: v.astype(np.float64) for k, v in out.items()}
+
+
+def _save(d, arrays):
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
+def dump_hits(d, res):
+    """--dump-outputs of the aligner's path: the hits of a fixed, seeded sample of the batch's reads (reads = their ordinals in the batch, then _hit_fields)
+    and the batch's totals (reads, hits, CIGAR words)"""
+    n = len(res["hit_off"]) - 1
+    k = min(n, 1 << 17)
+    while True:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+        out = dict(reads=rows.astype(np.float64), **_hit_fields(res, rows))
+        if sum(a.nbytes for a in out.values()) <= DUMP_LIMIT or k <= 1:
+            break
+        k //= 2
+    out["totals"] = np.array([n, len(res["rid"]), len(res["cigar"])], dtype=np.float64)
+    _save(d, out)
+
+
+def dump_contigs(d, wins, hits):
+    """--dump-outputs of the C5 pipeline: every window's contig count; every contig's length and supporting reads (window order, the library's order within a
+    window); the realigned contigs' hits (_hit_fields of every contig, prefixed realign_); and the bases and per-base coverage codes of a fixed, seeded sample of
+    the contigs as float32 character codes, as many as the size limit leaves room for.  A realignment's ties are broken by the aligner's read ordinal, which
+    every call advances (alignSequences), so the realign_ arrays are comparable between runs of the same --steps / --warmup"""
+    us = [u for w in wins for u in w]
+    out = {"contigs_per_window": np.array([len(w) for w in wins], dtype=np.float64),
+           "contig_len": np.array([u["len"] for u in us], dtype=np.float64),
+           "contig_nsr": np.array([u["nsr"] for u in us], dtype=np.float64)}
+    if hits is not None:
+        out.update(_hit_fields(hits, np.arange(len(hits["hit_off"]) - 1), "realign_"))
+    budget = (DUMP_LIMIT - sum(a.nbytes for a in out.values())) // 8          # 4 bytes for a base and 4 for its coverage code
+    pick, used = [], 0
+    for i in np.random.default_rng(DUMP_SEED).permutation(len(us)):
+        if used + len(us[i]["seq"]) <= budget:
+            pick.append(i)
+            used += len(us[i]["seq"])
+    pick = sorted(pick)
+    out["contig_sample"] = np.array(pick, dtype=np.float64)
+    out["contig_sample_bases"] = np.frombuffer(b"".join(us[i]["seq"] for i in pick), dtype=np.uint8).astype(np.float32)
+    out["contig_sample_cov"] = np.frombuffer(b"".join(us[i]["cov"] or bytes(len(us[i]["seq"])) for i in pick), dtype=np.uint8).astype(np.float32)
+    _save(d, out)
 
 
 def spawn_ranks(n):
@@ -418,6 +487,8 @@ def main_c5(args):
         dt = float(t.item())
     n_reads = n_win * per_win
     value = n_reads * world / (dt / args.steps)
+    if args.dump_outputs and rank == 0:          # the last timed step's windows and realigned contigs (N > 1: rank 0's windows; there is no data-path collective)
+        dump_contigs(args.dump_outputs, done[-1][0], done[-1][3])
     if rank == 0:
         lens = sorted((len(c) for c in contigs), reverse=True)
         half, run, n50 = sum(lens) / 2, 0, 0
@@ -621,9 +692,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--reads", type=int, default=0, help="reads per GPU per step (default: the config's size: C3 = 50 M, C2 = 10 M)")
     ap.add_argument("--config", default="C3")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip value_host_to_host / value_bamrecords")
-    ap.add_argument("--verify", type=int, default=20000, help="reads of the timed batch checked bit-for-bit against the oracle (C5: reads of window 0, default the whole window; -D = a window of 1/D of the size at the same coverage)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run the CPU baseline, the oracle check, the rooflines' inputs and the extras "
+                                                         "(value_host_to_host, value_bamrecords, value_per_call, the C5 leg); without it a run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step as DIR/<name>.npy (float64 / float32, "
+                                                                         "a fixed seeded sample, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip value_host_to_host / value_bamrecords / value_per_call / the C5 leg")
+    ap.add_argument("--verify", type=int, default=None, help="with --full: reads of the timed batch checked bit-for-bit against the oracle (default 20000; C5: reads of "
+                                                             "window 0, default the whole window; -D = a window of 1/D of the size at the same coverage)")
     ap.add_argument("--windows", type=int, default=64, help="C5: windows per GPU and step (the stages of the longest contig are single-wave long poles: more windows per "
                                                             "step fill the chip under them -- 8: 0.51 M reads/s, 32: 1.34 M, 64: 2.05 M on one MI355X)")
     ap.add_argument("--no-pipeline", action="store_true", help="C5: assemble and realign one after the other inside a step (default: step k + 1's assembly overlaps step k's realignment)")
@@ -640,9 +716,12 @@ def main():
     if world != args.gpus:
         sys.stderr.write("bench.py: --gpus %d but the launcher started %d rank(s)\n" % (args.gpus, world))
         sys.exit(2)
+    if not args.full:          # a plain run: set-up, warm-up, the timed steps, --dump-outputs and the line; every other figure and check is --full's
+        args.no_cpu_baseline = args.no_extras = True
+        args.verify = 0
+    elif args.verify is None:
+        args.verify = (args.reads or 100_000) if args.config == "C5" else 20000          # C5: one whole window through both checkers (~25 s of CPU)
     if args.config == "C5":
-        if args.verify == 20000:
-            args.verify = args.reads or 100_000          # one whole window through both checkers (~25 s of CPU on the GPU box)
         return main_c5(args)
 
     # ---- workload, generated before this process touches the GPU (forked generator workers)
@@ -751,9 +830,21 @@ def main():
     total_reads = n * world
     value = total_reads / (dt / args.steps)
 
-    # ---- N > 1: the merged gather of a sample equals what one process computes for the same reads
+    # ---- --dump-outputs: the last timed step's hits as its caller receives them (N > 1: rank 0's merged gather of every rank's hits)
+    if args.dump_outputs and rank == 0:
+        if world > 1:
+            res = gather.merge([gather.unpack(p.cpu().numpy()) for p in parts])
+        else:
+            buf = torch.empty(al.packed_size(h), dtype=torch.uint8, device=dev)
+            al.pack_into(h, buf.data_ptr(), buf.numel())
+            res = gather.unpack(buf.cpu().numpy())
+            del buf
+        dump_hits(args.dump_outputs, res)
+        del res
+
+    # ---- N > 1 (--full): the merged gather of a sample equals what one process computes for the same reads
     gather_ok = None
-    if world > 1:
+    if world > 1 and args.full:
         m = min(4096, n)
         _, parts = step(m)
         if rank == 0:
@@ -771,9 +862,11 @@ def main():
                 gather_ok = gather_ok and all(np.array_equal(got_r[k], one[k]) for k in ("hit_off", "pos", "cig_off", "rid", "score", "nm", "na", "n_cigar", "cigar", "flag", "mapq"))
 
     if rank == 0:
-        tmp = tempfile.mkdtemp(prefix="slx_bench_")
-        prefix = os.path.join(tmp, cfg["name"])
-        idx.WriteIndex(prefix)
+        tmp = prefix = None
+        if args.full:          # the index files the CPU baseline, the oracle check and the extras' tools load
+            tmp = tempfile.mkdtemp(prefix="slx_bench_")
+            prefix = os.path.join(tmp, cfg["name"])
+            idx.WriteIndex(prefix)
         per_read, cpu, match = None, None, None
         if not args.no_cpu_baseline:
             cpu, per_read = cpu_baseline(prefix, reads, args.config, timed=(world == 1))
@@ -972,7 +1065,7 @@ def main():
         other = None
         if not args.no_extras and args.config == "C3" and world == 1 and os.environ.get("SLX_BENCH_NO_C5_LEG") != "1":
             try:
-                o = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", "C5", "--steps", "12", "--warmup", "1", "--verify", "-10"],
+                o = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", "C5", "--steps", "12", "--warmup", "1", "--full", "--verify", "-10"],
                                    stdout=subprocess.PIPE, timeout=900, env=dict(os.environ, HIP_VISIBLE_DEVICES=os.environ.get("HIP_VISIBLE_DEVICES", str(local_rank))))
                 ln = [x for x in o.stdout.decode().splitlines() if x.startswith("{")]
                 if o.returncode == 0 and ln:

@@ -3,12 +3,12 @@
 exec < /dev/null
 ulimit -c 0
 CFG=$1; STEPS=$2; shift; shift
-R=$GRAFT_REPO_ROOT; mkdir -p $R/gpurun_out
+R=$(cd "$(dirname "$0")/.." && pwd); OUT=${OUT:-$R/bench_runs}; mkdir -p $OUT
 export SLX_BENCH_READS_CACHE=/tmp/slx_reads_cache
 for v in "$@"; do
   lib=""; [ "$v" != base ] && lib=$R/seqlib_amd/variants/libseqlib_amd_$v.so
-  SLX_LIB=$lib timeout -s KILL 600 python $R/bench.py --config $CFG --no-cpu-baseline --no-extras --steps $STEPS --warmup 1 --verify 2000 > $R/gpurun_out/lab_$v.json 2> $R/gpurun_out/lab_$v.err
-  python - "$v" $R/gpurun_out/lab_$v.json <<'PY'
+  SLX_LIB=$lib timeout -s KILL 600 python $R/bench.py --config $CFG --full --no-cpu-baseline --no-extras --steps $STEPS --warmup 1 --verify 2000 > $OUT/lab_$v.json 2> $OUT/lab_$v.err
+  python - "$v" $OUT/lab_$v.json <<'PY'
 import json,sys
 for l in open(sys.argv[2]):
     if l.startswith('{"metric"'):

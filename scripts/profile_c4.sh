@@ -23,7 +23,7 @@ done
 python3 $R/scripts/pmc_summary.py $OUT $CFG > $OUT/pmc_summary.json
 rm -rf $OUT/stats $OUT/pmc[0-9] $OUT/pmc[0-9].log
 # the clean line: same workload, three timed steps, CPU baseline (the checker loads the index the GPU wrote) for the algorithmic bytes, traffic from the summary above
-SLX_PMC_SUMMARY=$OUT/pmc_summary.json timeout -s KILL 2400 python3 $R/bench.py --config $CFG --reads $READS --no-extras --steps 3 --warmup 1 > $OUT/bench_clean.json 2> $OUT/bench_clean.err
+SLX_PMC_SUMMARY=$OUT/pmc_summary.json timeout -s KILL 2400 python3 $R/bench.py --config $CFG --reads $READS --full --no-extras --steps 3 --warmup 1 > $OUT/bench_clean.json 2> $OUT/bench_clean.err
 tail -c 300 $OUT/bench_clean.json
 rm -f ${SLX_BENCH_READS_CACHE}.$CFG.*
 ls -la $OUT

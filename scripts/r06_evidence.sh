@@ -10,10 +10,10 @@ cd $R
 case " $SKIP " in *" tests "*) ;; *)
 timeout 1500 python -m pytest tests -m gpu -q > $OUT/pytest_gpu.txt 2>&1; tail -3 $OUT/pytest_gpu.txt ;; esac
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.txt 2>&1; tail -1 $OUT/smoke.txt
-timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 300 $OUT/bench_default.json
-timeout 400 python bench.py --config C2 > $OUT/bench_c2.json 2> $OUT/bench_c2.err; tail -c 200 $OUT/bench_c2.json
-timeout 600 python bench.py --config C5 --steps 12 --warmup 1 > $OUT/bench_c5.json 2> $OUT/bench_c5.err; tail -c 200 $OUT/bench_c5.json
-SEQLIB_AMD_LOCAL_RANKS=8 timeout 900 python bench.py > $OUT/bench_host_budget_2cpu.json 2> $OUT/bench_host_budget_2cpu.err; tail -c 200 $OUT/bench_host_budget_2cpu.json
+timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 300 $OUT/bench_default.json
+timeout 400 python bench.py --config C2 --full > $OUT/bench_c2.json 2> $OUT/bench_c2.err; tail -c 200 $OUT/bench_c2.json
+timeout 600 python bench.py --config C5 --steps 12 --warmup 1 --full > $OUT/bench_c5.json 2> $OUT/bench_c5.err; tail -c 200 $OUT/bench_c5.json
+SEQLIB_AMD_LOCAL_RANKS=8 timeout 900 python bench.py --full > $OUT/bench_host_budget_2cpu.json 2> $OUT/bench_host_budget_2cpu.err; tail -c 200 $OUT/bench_host_budget_2cpu.json
 case " $SKIP " in *" prof "*) ;; *)
 bash scripts/profile_round.sh $OUT/c3 C3 > $OUT/profile_c3.log 2>&1
 bash scripts/profile_alone.sh $OUT/alone_C3 C3 16666666 > $OUT/alone_C3.txt 2>&1

@@ -1,13 +1,13 @@
 #!/bin/bash
 # seeding A/B: alone-run (one worker, one chunk) and whole-pipeline numbers per library variant (scripts/build_variant.sh) and knob set (KN=...)
-mkdir -p gpurun_out
+OUT=${OUT:-bench_runs}; mkdir -p $OUT
 for spec in "$@"; do
     name=${spec%%|*}; envs=${spec#*|}
     [ "$envs" = "$spec" ] && envs=""
     for cfg in C2:3333333 C3:8333332; do
         c=${cfg%%:*}; n=${cfg#*:}
-        env $envs SLX_KNOBS="workers=1,${KN}" timeout -s KILL 300 python bench.py --config $c --reads $n --no-cpu-baseline --no-extras --steps 2 --warmup 1 --verify 0 > gpurun_out/ab_${name}_$c.json 2> gpurun_out/ab_${name}_$c.err
-        python - "$name" "$c alone" gpurun_out/ab_${name}_$c.json <<'PY'
+        env $envs SLX_KNOBS="workers=1,${KN}" timeout -s KILL 300 python bench.py --config $c --reads $n --no-cpu-baseline --no-extras --steps 2 --warmup 1 --verify 0 > $OUT/ab_${name}_$c.json 2> $OUT/ab_${name}_$c.err
+        python - "$name" "$c alone" $OUT/ab_${name}_$c.json <<'PY'
 import json,sys
 for l in open(sys.argv[3]):
     if l.startswith('{"metric"'):
@@ -16,8 +16,8 @@ for l in open(sys.argv[3]):
 PY
     done
     for c in C2 C3; do
-        env $envs SLX_KNOBS="${KN}" timeout -s KILL 300 python bench.py --config $c --no-cpu-baseline --no-extras --steps 2 --warmup 1 --verify 2000 > gpurun_out/ab_${name}_${c}_full.json 2> gpurun_out/ab_${name}_${c}_full.err
-        python - "$name" "$c full" gpurun_out/ab_${name}_${c}_full.json <<'PY'
+        env $envs SLX_KNOBS="${KN}" timeout -s KILL 300 python bench.py --config $c --full --no-cpu-baseline --no-extras --steps 2 --warmup 1 --verify 2000 > $OUT/ab_${name}_${c}_full.json 2> $OUT/ab_${name}_${c}_full.err
+        python - "$name" "$c full" $OUT/ab_${name}_${c}_full.json <<'PY'
 import json,sys
 for l in open(sys.argv[3]):
     if l.startswith('{"metric"'):

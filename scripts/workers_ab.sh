@@ -1,11 +1,11 @@
 #!/bin/bash
 # whole-pipeline throughput vs number of workers / hardware queues:  scripts/workers_ab.sh "name|ENV=.. KN=.." ...
-mkdir -p gpurun_out
+OUT=${OUT:-bench_runs}; mkdir -p $OUT
 for spec in "$@"; do
     name=${spec%%|*}; rest=${spec#*|}
     for c in ${CFGS:-C2 C3}; do
-        env $rest timeout -s KILL 400 python bench.py --config $c --no-cpu-baseline --no-extras --steps 2 --warmup 1 --verify 2000 > gpurun_out/wk_${name}_$c.json 2> gpurun_out/wk_${name}_$c.err
-        python - "$name" "$c" gpurun_out/wk_${name}_$c.json <<'PY'
+        env $rest timeout -s KILL 400 python bench.py --config $c --full --no-cpu-baseline --no-extras --steps 2 --warmup 1 --verify 2000 > $OUT/wk_${name}_$c.json 2> $OUT/wk_${name}_$c.err
+        python - "$name" "$c" $OUT/wk_${name}_$c.json <<'PY'
 import json,sys
 ok=False
 for l in open(sys.argv[3]):

@@ -31,7 +31,7 @@ def test_bench_two_ranks_under_rccl():
         pytest.skip("needs two visible GPUs (the 1-GPU box cannot host two RCCL ranks)")
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "C1", "--steps", "2", "--warmup", "1"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "C1", "--steps", "2", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -51,7 +51,7 @@ def test_bench_c5_two_ranks():
         pytest.skip("needs two visible GPUs")
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "C5", "--windows", "4", "--reads", "20000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "C5", "--windows", "4", "--reads", "20000", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -67,7 +67,7 @@ def test_bench_c5_two_ranks_sharing_the_gpu():
     assembles and realigns windows [r W, (r + 1) W) of the job; the line reports both ranks' reads over the slowest rank's time"""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", SLX_BENCH_SHARE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "C5", "--windows", "4", "--reads", "20000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "C5", "--windows", "4", "--reads", "20000", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
