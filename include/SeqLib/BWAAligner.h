@@ -45,6 +45,7 @@
 #include "seqlib_amd.h"
 #include "SeqLib/BWAIndex.h"
 #include "SeqLib/BamRecord.h"
+#include "SeqLib/BamReader.h"
 #include "SeqLib/UnalignedSequence.h"
 
 namespace SeqLib {
@@ -301,6 +302,64 @@ public:
         if (index_->IsEmpty() || reads.empty()) return;
         Flush();
         run_batch(reads, out, hardclip, keepSecFrac, maxSecondary);
+    }
+    // ---- batch entry from a BAM file (new): realignment without the reads ever leaving HBM ------------------
+    // Every batch of the reader (BamReader.h) is unpacked on the GPU (slx_bam_reads_device: the sequences of the records that carry none of
+    // skip_flags, as stored or -- original_strand -- as sequenced) and aligned where it lies (slx_align_batch_device); the host sees the inflated
+    // stream only, from which the records take their names and sequences.  out gets one vector per kept read, in file order; read i of a batch
+    // takes lrand48 draw first_ordinal + i, as in the entry above.  A single-device aligner only; a batch that Next() has begun to serve is
+    // refused (std::logic_error): Reset() the reader or finish the batch first.
+    void alignSequences(BamReader &reader, std::vector<BamRecordPtrVector> &out, bool hardclip, double keepSecFrac, int maxSecondary,
+                        int skip_flags = 0x900, bool original_strand = false) const
+    {
+        out.clear();
+        if (index_->IsEmpty() || !reader.IsOpen()) return;
+        if (reader.cur_ < (size_t)reader.batch_.n_records) throw std::logic_error("BWAAligner::alignSequences(BamReader&): the reader is inside a batch that Next() began to serve");
+        Flush();
+        slx_aligner *al = handle();
+        std::string seq;
+        for (;;) {
+            slx_bam_batch b;
+            if (!reader.fetch(b)) throw std::runtime_error(std::string("BWAAligner::alignSequences(BamReader&): ") + slx_last_error());
+            if (b.n_records == 0) break;
+            void *d_bases = nullptr, *d_offs = nullptr;
+            int64_t n = 0;
+            const int64_t *rec_of_read = nullptr;
+            throw_rc(slx_bam_reads_device(reader.rd_, &b, skip_flags, original_strand ? 1 : 0, &d_bases, &d_offs, &n, &rec_of_read));
+            if (n == 0) continue;
+            uint64_t state;
+            {
+                std::lock_guard<std::mutex> g(rng_mutex());
+                state = slx_lrand48_peek_libc();
+                slx_lrand48_skip_libc((uint64_t)n);
+            }
+            slx_hits dh, h;
+            throw_rc(slx_align_batch_device(al, &memopt_, d_bases, d_offs, n, state, 0, hardclip ? 1 : 0, keepSecFrac, maxSecondary, &dh));
+            throw_rc(slx_bam_hits_to_host(reader.rd_, al, &dh, &h));
+            const size_t base = out.size();
+            out.resize(base + (size_t)n);
+            try {
+                detail::SlabWriter writer;
+                detail::SlabWriter *sw = n >= 4096 ? &writer : nullptr;
+                for (int64_t i = 0; i < n; ++i) {
+                    const uint8_t *p = b.stream + b.rec_off[rec_of_read[i]];
+                    const size_t l_name = p[12] ? (size_t)p[12] - 1 : 0;
+                    uint16_t n_cig, flag; int32_t l_seq;
+                    std::memcpy(&n_cig, p + 16, 2); std::memcpy(&flag, p + 18, 2); std::memcpy(&l_seq, p + 20, 4);
+                    const uint8_t *s4 = p + 36 + p[12] + 4 * (size_t)n_cig;
+                    const bool rev = original_strand && (flag & BAM_FREVERSE);
+                    seq.resize((size_t)l_seq);
+                    for (int32_t x = 0; x < l_seq; ++x) {
+                        const int32_t j = rev ? l_seq - 1 - x : x;
+                        unsigned c = (s4[j >> 1] >> ((~j & 1) << 2)) & 15u;
+                        if (rev) c = ((c & 1) << 3) | ((c & 2) << 1) | ((c & 4) >> 1) | ((c & 8) >> 3);          // the IUPAC complement reverses the four bits
+                        seq[(size_t)x] = "=ACMGRSVTWYHKDBN"[c];
+                    }
+                    build_read(h, i, seq, reinterpret_cast<const char *>(p + 36), l_name, hardclip, nullptr, out[base + (size_t)i], sw);
+                }
+            } catch (...) { slx_hits_free(&h); throw; }
+            slx_hits_free(&h);
+        }
     }
     // ---- deferred per-read calls (new): the reference's calling convention at batch speed ----------------
     // Every reference caller loops `alignSequence` over its reads (README.md:174-180, src/seqtools/seqtools.cpp:198-210).  Here one such
