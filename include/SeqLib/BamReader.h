@@ -5,9 +5,13 @@
 // CRC-checked and cut into records on the GPU behind include/seqlib_amd_bam.h, a batch of members at a time, and Next() serves records out of the
 // current batch.  A record's bam1_t is the 32 fixed bytes plus the variable part exactly as they stand in the file, so BamWriter::WriteRecord writes
 // back the bytes that were read.
+// Open loads the BAI index beside the file when there is one (<path>.bai, or .bai in place of .bam; src/BamReader.cpp:33), and SetRegion(GenomicRegion) /
+// SetRegions(GRC) then make Next, NextBatch and BWAAligner::alignSequences(BamReader&) serve the regions in the order given, a record once per region it
+// overlaps (src/BamReader.cpp:64-137: one iterator per region): only the BGZF members the index names are inflated, and the records are tested against the
+// region and compacted on the GPU.  The interval handed down is [pos1, pos2), exactly what the reference hands to sam_itr_queryi.
 // New next to the reference: GetNextRecord (the README's spelling, README.md:150-181), NextBatch (many records at once through the slab path of
-// BamRecord.h), SetBatchBytes.
-// Refused loudly: SetRegion / SetRegions (BAI and GenomicRegion are not carried), CRAM and SAM-text input, "-" (stdin), a second Open.
+// BamRecord.h), SetBatchBytes, HasIndex.
+// Refused loudly: SetRegion / SetRegions with anything but a GenomicRegion / a GRC, CRAM and SAM-text input, "-" (stdin), a second Open.
 #pragma once
 #include <cstdint>
 #include <cstring>
@@ -15,8 +19,10 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <vector>
 #include "SeqLib/BamHeader.h"
 #include "SeqLib/BamRecord.h"
+#include "SeqLib/GenomicRegionCollection.h"
 #include "seqlib_amd_bam.h"
 
 namespace SeqLib {
@@ -67,14 +73,29 @@ public:
         slx_bam_rewind(rd_);
         clear_batch();
     }
+    // false when the reader is not open, has no index or the region names a reference outside the header
+    bool SetRegion(const GenomicRegion &gr)
+    {
+        if (!rd_ || !HasIndex()) return false;
+        const slx_bam_region r = {gr.chr, gr.pos1, gr.pos2};
+        return arm(&r, 1);
+    }
+    bool SetRegions(const GRC &grc)
+    {
+        if (!rd_ || !HasIndex() || !grc.size()) return false;
+        std::vector<slx_bam_region> r;
+        for (const GenomicRegion &g : grc) r.push_back(slx_bam_region{g.chr, g.pos1, g.pos2});
+        return arm(r.data(), (int64_t)r.size());
+    }
+    bool HasIndex() const { return rd_ && slx_bam_has_index(rd_) != 0; }
     template <class Region> bool SetRegion(const Region &)
     {
-        std::cerr << "BamReader::SetRegion - region iteration needs a BAI index and GenomicRegion; not available in the MI355X drop-in" << std::endl;
+        std::cerr << "BamReader::SetRegion - region iteration needs a BAI index and GenomicRegion; not available in the MI355X drop-in for this argument type (pass a SeqLib::GenomicRegion)" << std::endl;
         return false;
     }
     template <class Regions> bool SetRegions(const Regions &)
     {
-        std::cerr << "BamReader::SetRegions - region iteration needs a BAI index and GenomicRegion; not available in the MI355X drop-in" << std::endl;
+        std::cerr << "BamReader::SetRegions - region iteration needs a BAI index and GenomicRegion; not available in the MI355X drop-in for this argument type (pass a SeqLib::GRC)" << std::endl;
         return false;
     }
     bool SetCramReference(const std::string &) { std::cerr << "BamReader::SetCramReference - CRAM input is not available in the MI355X drop-in" << std::endl; return false; }
@@ -167,6 +188,12 @@ private:
         return std::allocate_shared<BamRecord>(detail::SlabAlloc<BamRecord>(slab), std::shared_ptr<bam1_t>(box, r));
     }
     void clear_batch() { std::memset(&batch_, 0, sizeof batch_); cur_ = 0; eof_ = false; }
+    bool arm(const slx_bam_region *r, int64_t n)
+    {
+        if (slx_bam_set_regions(rd_, r, n) != SLX_OK) { std::cerr << "BamReader::SetRegion - " << slx_last_error() << std::endl; return false; }
+        clear_batch();
+        return true;
+    }
     // makes batch_[cur_] a record: fetches the next batch when the current one is used up; false at the end of the file or on an error (message on stderr)
     bool advance()
     {

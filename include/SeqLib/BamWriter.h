@@ -11,7 +11,9 @@
 //          bam1_t::data image as is; 64 KiB BGZF blocks and the 28-byte EOF block.  The bin field is computed from
 //          the alignment span (reg2bin); compressed bytes depend on the deflate implementation, the inflated stream
 //          does not.
-// CRAM needs htslib's codec stack and reference access: Open() fails loudly for it; BuildIndex() (BAI) likewise.
+// CRAM needs htslib's codec stack and reference access: Open() fails loudly for it.  BuildIndex() writes <file>.bai for a closed, coordinate-sorted
+// BAM: the index is built on the GPU (slx_bam_index_build, include/seqlib_amd_bam.h); false with "Failed to create index" for SAM output, an unsorted file
+// or without a GPU.
 #pragma once
 #include <cstdio>
 #include <algorithm>
@@ -23,6 +25,7 @@
 #include <zlib.h>
 #include "SeqLib/BamHeader.h"
 #include "SeqLib/BamRecord.h"
+#include "seqlib_amd_bam.h"
 
 namespace SeqLib {
 
@@ -134,8 +137,11 @@ public:
     {
         if (fop) { std::cerr << "Trying to index open BAM. Close first with Close()" << std::endl; return false; }
         if (m_out.empty()) { std::cerr << "Trying to make index, but no BAM specified" << std::endl; return false; }
-        std::cerr << "Failed to create index" << std::endl;     // BAI construction is htslib's; not in this drop-in
-        return false;
+        if (output_format != "wb" || m_out == "-" || slx_bam_index_build(m_out.c_str(), -1, nullptr) != SLX_OK) {
+            std::cerr << "Failed to create index" << (output_format == "wb" && m_out != "-" ? std::string(": ") + slx_last_error() : std::string()) << std::endl;
+            return false;
+        }
+        return true;
     }
     bool SetCramReference(const std::string &) { return false; }
 

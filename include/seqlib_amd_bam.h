@@ -14,8 +14,23 @@
  *   slx_bam_close         BamReader::Close                   src/BamReader.cpp:44-54
  *   slx_bam_set, slx_bam_counter   (new) knobs and diagnostics
  *   slx_bam_scan_members, slx_bam_members_free, slx_bam_inflate_file   (new) helpers for tests and tools
+ *   slx_bam_index_load, slx_bam_has_index   the sam_index_load of BamReader::Open          src/BamReader.cpp:33
+ *   slx_bam_set_regions   BamReader::SetRegion / SetRegions (sam_itr_queryi per region)    src/BamReader.cpp:64-102, 104-137
+ *   slx_bam_index_build   BamWriter::BuildIndex (sam_index_build)                          src/BamWriter.cpp
+ *   slx_bai_query, slx_bai_stats, slx_bai_free   (new) the index on the host, for tests and tools
  *
- * No CPU fallback: without a GPU slx_bam_open and slx_bam_inflate_file return SLX_ENODEVICE.  Not carried: region iteration (BAI), CRAM, SAM text.
+ * The BAI index is restated from SAMv1 section 5.2; where it leaves a choice the rule is htslib's:
+ *   end of a record   pos + reference length of the CIGAR (M D N = X); pos + 1 when that is 0 or the record carries 0x4
+ *   bin               reg2bin(pos, end), computed: the record's stored bin is not trusted
+ *   virtual offset    of whole-file inflated offset x: the first member m with start[m] + isize[m] > x (never an empty one) gives
+ *                     file_off[m] << 16 | (x - start[m]); the end of the data gives the file offset behind the last non-empty member << 16
+ *   chunk             a maximal run of file-consecutive records with one (tid, bin), tid >= 0: (begin of the first, end of the last)
+ *   linear index      per 16 KiB window the lowest begin of the records touching it; an untouched window takes the next touched one above it
+ *   pseudo-bin 37450  per reference with records: (begin of its first record, end of its last), (n_mapped, n_unmapped: 0x4); n_no_coor: tid < 0
+ * Not done: htslib's post-pass that merges chunks lying in one BGZF block and lifts sparse bins into their parents (the index is valid without it,
+ * byte parity with `samtools index` is not claimed), and CSI.
+ *
+ * No CPU fallback: without a GPU slx_bam_open, slx_bam_inflate_file and slx_bam_index_build return SLX_ENODEVICE.  Not carried: CRAM, SAM text, CSI.
  */
 #ifndef SEQLIB_AMD_BAM_H
 #define SEQLIB_AMD_BAM_H
@@ -71,8 +86,39 @@ int  slx_bam_rewind(slx_bam *rd);
 /* "chunk_bytes" (65536; >= 64): chunk of the record index;  "idx_fail" 0|1: test knob, every guess of the index is made wrong */
 int  slx_bam_set(slx_bam *rd, const char *key, int64_t value);
 /* "members", "members_done", "repaired_chunks", "index_rounds", "missing_eof", "records", and kernel times of the last batch from HIP events in
- * microseconds: "us_inflate", "us_crc", "us_index", "us_unpack"; -1 = unknown name */
+ * microseconds: "us_inflate", "us_crc", "us_index", "us_unpack"; of the region iteration "regions_done", "region_candidates" (records walked),
+ * "region_kept" and "us_region"; -1 = unknown name */
 int64_t slx_bam_counter(const slx_bam *rd, const char *name);
+
+/* The index of the reader's file: bai_path, or when NULL <path>.bai, then <path> with ".bam" replaced by ".bai".  slx_bam_open tries the same two names
+ * silently (a missing index is no error).  SLX_EIO: missing, short or damaged; SLX_EINVAL: its reference count is not the header's. */
+int  slx_bam_index_load(slx_bam *rd, const char *bai_path);
+int  slx_bam_has_index(const slx_bam *rd);
+
+typedef struct { int32_t tid; int64_t beg, end; } slx_bam_region;      /* 0-based, half open */
+/* After the call slx_bam_next serves the regions in the order given, inside a region in file order: every record with tid == region.tid,
+ * pos < region.end and end > region.beg (end as above), once per region it overlaps.  Per region the index's merged chunk list is planned on the host; only
+ * the members it names are inflated and indexed, k_bam_region_keep tests their records and k_bam_gather compacts the kept ones, bytes unchanged, so a batch
+ * is what it is for the whole file: stream[0, n_bytes) holds exactly the n_records whole records, and slx_bam_reads_device works on it as it stands.  One call
+ * takes as many of the next regions as fit max_bytes, a larger region is cut at member boundaries; n_records == 0 is the end of the last region.
+ * n = 0: back to the whole file, from its start (slx_bam_rewind drops the regions too).  SLX_EINVAL: no index loaded, or a tid outside the header. */
+int  slx_bam_set_regions(slx_bam *rd, const slx_bam_region *regs, int64_t n);
+
+/* The BAI of a coordinate-sorted BAM (tid ascending as unsigned, pos non-decreasing inside a tid), built on the GPU: the file goes through the reader's
+ * inflate, CRC and record-index kernels batch by batch, and per batch k_bai_rec / k_bai_heads / k_bai_chunks compute ends, bins, virtual offsets, chunks, the
+ * linear index and the pseudo-bin's figures; hipCUB sorts the chunks; the host lays the bytes out.  bai_path NULL: bam_path + ".bai".  SLX_EINVAL: the
+ * first record out of order (slx_last_error names its 0-based ordinal) or a record past its reference's end; no file is written then.
+ * _ex: batch_bytes / chunk_bytes of the pass (0: 64 MiB / 65536), for tests and tools. */
+int  slx_bam_index_build(const char *bam_path, int device, const char *bai_path);
+int  slx_bam_index_build_ex(const char *bam_path, int device, const char *bai_path, int64_t batch_bytes, int64_t chunk_bytes);
+
+/* host only, no GPU: the merged chunk list that holds every record of tid overlapping [beg, end): the bins of reg2bins(beg, end), chunks that end at or
+ * below the linear index's offset of beg's window dropped, the rest sorted by begin and merged where they touch or overlap.  *chunks: 2 * *n virtual
+ * offsets, freed with slx_bai_free.  SLX_EIO: a missing, short, truncated or damaged file (every count is checked against the bytes left). */
+int  slx_bai_query(const char *bai_path, int tid, int64_t beg, int64_t end, uint64_t **chunks, int64_t *n);
+/* host only: n_ref and the trailing n_no_coor (0 when absent); for tid >= 0 also the pseudo-bin's two counts, n_bin (the pseudo-bin counted) and n_intv */
+int  slx_bai_stats(const char *bai_path, int *n_ref, uint64_t *n_no_coor, int tid, uint64_t *n_mapped, uint64_t *n_unmapped, int *n_bin, int *n_intv);
+void slx_bai_free(void *p);
 
 /* host only: the member table of a BGZF file (*members is owned by the caller until slx_bam_members_free); *has_eof = the last member is the empty EOF block */
 int  slx_bam_scan_members(const char *path, slx_bam_member **members, int64_t *n_members, int *has_eof);

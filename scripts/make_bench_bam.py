@@ -2,8 +2,10 @@
 """Writes the input of tools/bamread_bench.cpp: a BAM of synthetic 150 bp records with qualities, BGZF members of 0xff00 bytes deflated at level 6
 (zlib, one process per slice of members).  The reads are windows of a reference FASTA (default tests/golden/tiny.fa) with 1 % substitutions, half of
 them reverse-complemented, stored as unmapped records -- so the same file feeds BWAAligner::alignSequences(BamReader&) with that reference's index.
+--sorted writes the coordinate-sorted variant tools/bamregion_bench.cpp takes: the same windows as mapped records (150M, 0x10 on half of them) at the
+place they were cut from, in (reference, position) order; without the option the output is what it always was.
 
-    python scripts/make_bench_bam.py out.bam [--records 2000000] [--ref tests/golden/tiny.fa] [--procs 8] [--seed 1]
+    python scripts/make_bench_bam.py out.bam [--records 2000000] [--ref tests/golden/tiny.fa] [--procs 8] [--seed 1] [--sorted]
 """
 import argparse
 import os
@@ -54,7 +56,44 @@ def records(n, first, ref, rng):
     return a
 
 
+def reg2bin(beg, end):
+    """SAMv1 5.3 over arrays"""
+    end = end - 1
+    out = np.zeros(len(beg), dtype=np.int64)
+    for sh, base in ((26, 1), (23, 9), (20, 73), (17, 585), (14, 4681)):          # coarse to fine: the finest level that holds the span wins
+        out = np.where(beg >> sh == end >> sh, base + (beg >> sh), out)
+    return out
+
+
+def placed_records(first, ref, rng, tid, pos):
+    """the records of the sorted variant: one per (tid, pos), mapped with CIGAR 150M, half of them flagged 0x10 (the stored bases are the forward strand's)"""
+    n, name_w = len(pos), 10
+    size = 4 + 32 + name_w + 4 + (L + 1) // 2 + L
+    a = np.zeros((n, size), dtype=np.uint8)
+    a[:, :36] = np.frombuffer(struct.pack("<IiiBBHHHiiii", size - 4, 0, 0, name_w, 60, 0, 1, 0, L, -1, -1, 0), dtype=np.uint8)
+    a[:, 4:8] = tid.astype("<i4").view(np.uint8).reshape(n, 4)
+    a[:, 8:12] = pos.astype("<i4").view(np.uint8).reshape(n, 4)
+    a[:, 14:16] = reg2bin(pos.astype(np.int64), pos.astype(np.int64) + L).astype("<u2").view(np.uint8).reshape(n, 2)
+    a[:, 18] = np.where(rng.random(n) < 0.5, 16, 0)
+    ids = np.arange(first, first + n)
+    a[:, 36] = ord("r")
+    for d in range(8):
+        a[:, 37 + d] = 48 + (ids // 10 ** (7 - d)) % 10
+    a[:, 36 + name_w:40 + name_w] = np.frombuffer(struct.pack("<I", L << 4), dtype=np.uint8)
+    return a, 40 + name_w
+
+
 def slice_job(args):
+    if len(args) == 6:
+        n, first, ref, seed, tid, start = args
+        rng = np.random.default_rng(seed)
+        a, so = placed_records(first, ref, rng, tid, start[1])
+        codes = ref[start[0][:, None] + np.arange(L)[None, :]]
+        codes = np.where(rng.random((n, L)) < 0.01, (codes + rng.integers(1, 4, size=(n, L))) & 3, codes)
+        nib = (1 << codes).astype(np.uint8)
+        a[:, so:so + L // 2] = (nib[:, 0::2] << 4) | nib[:, 1::2]
+        a[:, so + L // 2:] = np.clip(rng.normal(34, 5, size=(n, L)), 2, 40).astype(np.uint8)
+        return members(a.tobytes())
     n, first, ref, seed = args
     return members(records(n, first, ref, np.random.default_rng(seed)).tobytes())
 
@@ -66,6 +105,7 @@ def main():
     ap.add_argument("--ref", default=os.path.join(ROOT, "tests", "golden", "tiny.fa"))
     ap.add_argument("--procs", type=int, default=8)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--sorted", action="store_true", help="mapped records in coordinate order (the input of tools/bamregion_bench.cpp)")
     o = ap.parse_args()
     names, seqs = [], []
     for ln in open(o.ref):
@@ -78,12 +118,22 @@ def main():
     for i, c in enumerate("ACGT"):
         lut[ord(c)] = i
     ref = lut[np.frombuffer("".join(seqs).encode(), dtype=np.uint8)]
-    text = "@HD\tVN:1.6\tSO:unsorted\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % (n, len(s)) for n, s in zip(names, seqs))
+    text = "@HD\tVN:1.6\tSO:%s\n" % ("coordinate" if o.sorted else "unsorted") + "".join("@SQ\tSN:%s\tLN:%d\n" % (n, len(s)) for n, s in zip(names, seqs))
     hdr = b"BAM\1" + struct.pack("<I", len(text)) + text.encode() + struct.pack("<I", len(names))
     for n, s in zip(names, seqs):
         hdr += struct.pack("<I", len(n) + 1) + n.encode() + b"\0" + struct.pack("<I", len(s))
     per = 200000                                         # records per job
     jobs = [(min(per, o.records - f), f, ref, o.seed * 100003 + f) for f in range(0, o.records, per)]
+    if o.sorted:
+        # places in the concatenated reference, in order; a window that would cross into the next sequence is pulled back to end with its own
+        ends = np.cumsum([len(s) for s in seqs])
+        g = np.sort(np.random.default_rng(o.seed).integers(0, len(ref) - L, size=o.records))
+        tid = np.searchsorted(ends, g, side="right")
+        g = np.minimum(g, ends[tid] - L)
+        order = np.lexsort((g, tid))
+        g, tid = g[order], tid[order]
+        pos = g - (ends[tid] - np.array([len(s) for s in seqs])[tid])
+        jobs = [j + (tid[j[1]:j[1] + j[0]], (g[j[1]:j[1] + j[0]], pos[j[1]:j[1] + j[0]])) for j in jobs]
     with open(o.out, "wb") as f, ProcessPoolExecutor(o.procs) as ex:
         f.write(members(hdr))
         for part in ex.map(slice_job, jobs):

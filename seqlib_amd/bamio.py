@@ -13,11 +13,18 @@ from . import _ffi
 EXPORTS = [
     "slx_bam_open", "slx_bam_close", "slx_bam_header", "slx_bam_ref_name", "slx_bam_ref_len", "slx_bam_next", "slx_bam_reads_device", "slx_bam_hits_to_host", "slx_bam_rewind",
     "slx_bam_set", "slx_bam_counter", "slx_bam_scan_members", "slx_bam_members_free", "slx_bam_inflate_file",
+    "slx_bam_index_load", "slx_bam_has_index", "slx_bam_set_regions", "slx_bam_index_build", "slx_bam_index_build_ex",
 ]
+# the host-only BAI helpers of the same header
+BAI_EXPORTS = ["slx_bai_query", "slx_bai_stats", "slx_bai_free"]
 
 
 class Member(C.Structure):
     _fields_ = [("file_off", C.c_uint64), ("data_off", C.c_uint32), ("data_len", C.c_uint32), ("isize", C.c_uint32), ("crc32", C.c_uint32)]
+
+
+class Region(C.Structure):
+    _fields_ = [("tid", C.c_int32), ("beg", C.c_int64), ("end", C.c_int64)]
 
 
 class Batch(C.Structure):
@@ -52,8 +59,41 @@ def lib():
         L.slx_bam_members_free.argtypes = [C.POINTER(Member)]
         L.slx_bam_members_free.restype = None
         L.slx_bam_inflate_file.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.slx_bam_index_load.argtypes = [C.c_void_p, C.c_char_p]
+        L.slx_bam_has_index.argtypes = [C.c_void_p]
+        L.slx_bam_set_regions.argtypes = [C.c_void_p, C.POINTER(Region), C.c_int64]
+        L.slx_bam_index_build.argtypes = [C.c_char_p, C.c_int, C.c_char_p]
+        L.slx_bam_index_build_ex.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int64, C.c_int64]
+        L.slx_bai_query.argtypes = [C.c_char_p, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_int64)]
+        L.slx_bai_stats.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.slx_bai_free.argtypes = [C.c_void_p]
+        L.slx_bai_free.restype = None
         _READY = True
     return L
+
+
+def index_build(path, bai_path=None, device=-1, batch_bytes=0, chunk_bytes=0):
+    """the BAI of a coordinate-sorted BAM, built on the GPU (bai_path None: path + ".bai")"""
+    _ffi.check(lib().slx_bam_index_build_ex(str(path).encode(), device, None if bai_path is None else str(bai_path).encode(), batch_bytes, chunk_bytes))
+
+
+def bai_query(bai_path, tid, beg, end):
+    """host only -> [(u, v)]: the merged chunk list of a region"""
+    p, n = C.POINTER(C.c_uint64)(), C.c_int64(0)
+    _ffi.check(lib().slx_bai_query(str(bai_path).encode(), tid, beg, end, C.byref(p), C.byref(n)))
+    out = [(p[2 * i], p[2 * i + 1]) for i in range(n.value)]
+    lib().slx_bai_free(p)
+    return out
+
+
+def bai_stats(bai_path, tid=-1):
+    """host only -> dict(n_ref, n_no_coor[, n_mapped, n_unmapped, n_bin, n_intv])"""
+    nr, nc, nm, nu, nb, ni = C.c_int(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_int(0), C.c_int(0)
+    _ffi.check(lib().slx_bai_stats(str(bai_path).encode(), C.byref(nr), C.byref(nc), tid, C.byref(nm), C.byref(nu), C.byref(nb), C.byref(ni)))
+    d = dict(n_ref=nr.value, n_no_coor=nc.value)
+    if tid >= 0:
+        d.update(n_mapped=nm.value, n_unmapped=nu.value, n_bin=nb.value, n_intv=ni.value)
+    return d
 
 
 def scan_members(path):
@@ -102,6 +142,17 @@ class Reader:
 
     def rewind(self):
         _ffi.check(lib().slx_bam_rewind(self.h))
+
+    def index_load(self, bai_path=None):
+        _ffi.check(lib().slx_bam_index_load(self.h, None if bai_path is None else str(bai_path).encode()))
+
+    def has_index(self):
+        return bool(lib().slx_bam_has_index(self.h))
+
+    def set_regions(self, regions):
+        """regions: [(tid, beg, end)], 0-based half open; [] = the whole file again"""
+        arr = (Region * max(len(regions), 1))(*[Region(*r) for r in regions])
+        _ffi.check(lib().slx_bam_set_regions(self.h, arr, len(regions)))
 
     def next(self, max_bytes=64 << 20):
         """-> (list of whole records as bytes, block_size word included; Batch) -- an empty list at the end of the file"""

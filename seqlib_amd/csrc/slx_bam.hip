@@ -5,6 +5,8 @@
 //   k_bgzf_crc       one wave per member, a slice per lane, slices combined by x^(8n) mod P                                     dev_inflate.h
 //   k_bam_guess / k_bam_round / k_bam_scan / k_bam_fill   record starts by speculate / verify / repair, one lane per chunk      dev_bamidx.h
 //   k_bam_keep / k_bam_unpack   flag filter, 4-bit sequence -> ASCII (reverse complement on request), one wave per record
+//   k_bai_rec / k_bai_heads / k_bai_chunks / k_bai_fill   the BAI index of a sorted file: ends, bins, virtual offsets, chunks, linear index   dev_bai.h
+//   k_bam_region_keep / k_bam_gather   region iteration: records tested against the region, the kept ones compacted, one wave per record   dev_bai.h
 // Waves take members / records by a static map (wave w of the grid owns item w): there is no work queue here, so the queue hazards of DESIGN.md
 // section 4 do not arise.
 #include <hip/hip_runtime.h>
@@ -23,6 +25,8 @@
 #include "seqlib_amd_bam.h"
 #include "dev_inflate.h"
 #include "dev_bamidx.h"
+#include "dev_bai.h"
+#include "bai_host.h"
 
 #define BAM_HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { slx_set_error("HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, __LINE__); return SLX_ENODEVICE; } } while (0)
 #define BAM_CHK(x) do { const int rc_ = (x); if (rc_ != SLX_OK) return rc_; } while (0)
@@ -165,6 +169,170 @@ __global__ __launch_bounds__(256) void k_bam_unpack(const uint8_t *s, const uint
     }
 }
 
+// ---- the BAI build (dev_bai.h).  Per batch: k_bai_rec (fields, end, bin, virtual offsets, linear index, per-reference figures), k_bai_heads (run heads and the
+// order check against the predecessor, the previous batch's last record included), a hipCUB sum of the heads, k_bai_chunks (one chunk per run; a run that is open
+// at the end of a batch is closed provisionally and closed again by the next batch).  Once: hipCUB radix sort of the chunks by (tid, bin), k_bai_fill.
+struct bai_dev {
+    const uint64_t *ne_start, *ne_file; uint64_t nn, total, behind;      // the non-empty members
+    const uint64_t *lin_off;                                             // n_ref + 1: first window of every reference in lin
+    unsigned long long *lin, *ref_first, *ref_last, *n_map, *n_unmap;
+    uint32_t *n_intv;
+    int32_t n_ref;
+};
+
+// bst: [0] error bits, [1] ordinal of the first record out of order, [2] records with tid < 0
+__global__ __launch_bounds__(256) void k_bai_rec(const uint8_t *s, const uint64_t *rec, uint64_t n_rec, uint64_t base_off, bai_dev d, unsigned long long *key, unsigned long long *tp,
+                                                 unsigned long long *vbeg, unsigned long long *vend, unsigned long long *bst)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool active = r < n_rec;
+    bai_fields f = {};
+    uint64_t o0 = 0, o1 = 0;
+    if (active) { o0 = rec[r]; o1 = rec[r + 1]; f = bai_read(s + o0); }
+    const uint64_t reflen = bai_reflen_wave(f.cig, f.n_cig, active, lane);
+    unsigned long long err = 0;
+    if (active && !f.ok) err |= BAI_E_CIGAR;
+    if (active && f.tid >= d.n_ref) { err |= BAI_E_TID; f.tid = -1; }
+    const bool placed = active && f.tid >= 0;
+    const int64_t pos = f.pos < 0 ? 0 : f.pos;
+    int64_t end = bai_end(f.pos, f.flag, reflen);
+    if (end <= pos) end = pos + 1;
+    uint64_t vb = 0, ve = 0;
+    uint64_t w0 = 0, w1 = 0, lo = 0;
+    if (active) {
+        tp[r] = (unsigned long long)(uint32_t)f.tid << 32 | ((uint32_t)f.pos ^ 0x80000000u);
+        key[r] = placed ? (unsigned long long)(uint32_t)f.tid << 32 | bai_reg2bin(pos, end) : BAI_NOKEY;
+    }
+    if (placed) {
+        vb = bai_voff(d.ne_start, d.ne_file, d.nn, d.total, d.behind, base_off + o0);
+        ve = bai_voff(d.ne_start, d.ne_file, d.nn, d.total, d.behind, base_off + o1);
+        vbeg[r] = vb; vend[r] = ve;
+        lo = d.lin_off[f.tid];
+        const uint64_t cap = d.lin_off[f.tid + 1] - lo;
+        w0 = (uint64_t)pos >> 14; w1 = (uint64_t)(end - 1) >> 14;
+        if (w1 >= cap) { err |= BAI_E_SPAN; w1 = cap - 1; if (w0 > w1) w0 = w1; }
+        atomicMax(&d.n_intv[f.tid], (uint32_t)(w1 + 1));
+    }
+    if (err) atomicOr(&bst[0], err);
+    // the linear index: a record's few windows on its own lane, a long span (an N of megabases) by the whole wave
+    const bool wide = placed && w1 - w0 >= BAI_COOP_WINS;
+    if (placed && !wide) for (uint64_t w = w0; w <= w1; ++w) atomicMin(&d.lin[lo + w], (unsigned long long)vb);
+    for (unsigned long long m = __ballot(wide); m; m &= m - 1) {
+        const int src = __ffsll(m) - 1;
+        const uint64_t a = __shfl((unsigned long long)(lo + w0), src, 64), b = __shfl((unsigned long long)(lo + w1), src, 64), v = __shfl((unsigned long long)vb, src, 64);
+        for (uint64_t w = a + lane; w <= b; w += 64) atomicMin(&d.lin[w], (unsigned long long)v);
+    }
+    // per-reference figures: a wave's records almost always share one reference, and then one lane speaks for all of them
+    const unsigned long long pm = __ballot(placed);
+    const unsigned long long nc = __ballot(active && !placed);
+    if (lane == 0 && nc) atomicAdd(&bst[2], (unsigned long long)__popcll(nc));
+    if (pm) {
+        const int first = __ffsll(pm) - 1;
+        const int32_t t0 = __shfl(f.tid, first, 64);
+        const bool unm = (f.flag & 4u) != 0;
+        if (__all(!placed || f.tid == t0)) {
+            const unsigned long long mu = __ballot(placed && unm);
+            unsigned long long mn = placed ? vb : ~0ull, mx = placed ? ve : 0ull;
+            for (int o = 32; o; o >>= 1) {
+                const unsigned long long a = __shfl_xor(mn, o, 64), b = __shfl_xor(mx, o, 64);
+                mn = a < mn ? a : mn; mx = b > mx ? b : mx;
+            }
+            if (lane == first) {
+                atomicMin(&d.ref_first[t0], mn); atomicMax(&d.ref_last[t0], mx);
+                if (pm & ~mu) atomicAdd(&d.n_map[t0], (unsigned long long)__popcll(pm & ~mu));
+                if (mu) atomicAdd(&d.n_unmap[t0], (unsigned long long)__popcll(mu));
+            }
+        } else if (placed) {
+            atomicMin(&d.ref_first[f.tid], (unsigned long long)vb); atomicMax(&d.ref_last[f.tid], (unsigned long long)ve);
+            atomicAdd(unm ? &d.n_unmap[f.tid] : &d.n_map[f.tid], 1ull);
+        }
+    }
+}
+
+// head[i] = record i opens a chunk; carry_in / carry_out: (key, tid-pos word) of the previous / this batch's last record
+__global__ void k_bai_heads(const unsigned long long *key, const unsigned long long *tp, uint64_t n_rec, uint64_t ord_base, const unsigned long long *carry_in,
+                            unsigned long long *carry_out, unsigned long long *head, unsigned long long *bst)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r > n_rec) return;
+    if (r == n_rec) { head[r] = 0; return; }
+    const unsigned long long pk = r ? key[r - 1] : carry_in[0], pt = r ? tp[r - 1] : carry_in[1];
+    if (tp[r] < pt) atomicMin(&bst[1], (unsigned long long)(ord_base + r));
+    head[r] = key[r] != BAI_NOKEY && key[r] != pk;
+    if (r == n_rec - 1) { carry_out[0] = key[r]; carry_out[1] = tp[r]; }
+}
+
+__global__ void k_bai_chunks(const unsigned long long *key, const unsigned long long *vbeg, const unsigned long long *vend, const unsigned long long *head, const unsigned long long *hidx,
+                             uint64_t n_rec, uint64_t chunk_base, uint64_t cap, unsigned long long *ckey, unsigned long long *cbeg, unsigned long long *cend)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_rec || key[r] == BAI_NOKEY) return;
+    const uint64_t slot = chunk_base + hidx[r] + head[r] - 1;          // a record that continues the previous batch's open run: chunk_base - 1
+    if (slot >= cap) return;
+    if (head[r]) { ckey[slot] = key[r]; cbeg[slot] = vbeg[r]; }
+    if (r == n_rec - 1 || key[r + 1] != key[r]) cend[slot] = vend[r];
+}
+
+__global__ void k_bai_iota(uint32_t *v, uint64_t n)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) v[i] = (uint32_t)i;
+}
+
+// one wave per reference: a window no record touched takes the value of the next touched window above it, 64 windows at a time from the top
+__global__ __launch_bounds__(64) void k_bai_fill(bai_dev d)
+{
+    const int t = blockIdx.x, lane = threadIdx.x;
+    if (t >= d.n_ref) return;
+    const uint64_t lo = d.lin_off[t], n = d.n_intv[t];
+    unsigned long long above = 0;
+    for (uint64_t top = n; top > 0; top = top > 64 ? top - 64 : 0) {
+        const int64_t w = (int64_t)top - 64 + lane;                     // lanes 0..63 hold windows top-64 .. top-1
+        unsigned long long v = w >= 0 ? d.lin[lo + w] : ~0ull;
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long up = __shfl_down(v, o, 64);
+            if (v == ~0ull && lane + o < 64) v = up;
+        }
+        if (v == ~0ull) v = above;
+        if (w >= 0) d.lin[lo + w] = v;
+        above = __shfl(v, top >= 64 ? 0 : (int)(64 - top), 64);       // the lowest window of this tile
+    }
+}
+
+// ---- the region filter: keep[i] = record i of the span overlaps the region (the end as in the index build), klen[i] = its bytes when kept
+__global__ __launch_bounds__(256) void k_bam_region_keep(const uint8_t *s, const uint64_t *rec, uint64_t n_rec, int32_t tid, int64_t beg, int64_t end, unsigned long long *keep,
+                                                         unsigned long long *klen, unsigned long long *bst)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool active = r < n_rec;
+    bai_fields f = {};
+    if (active) f = bai_read(s + rec[r]);
+    const uint64_t reflen = bai_reflen_wave(f.cig, f.n_cig, active, lane);
+    if (r == n_rec) { keep[r] = 0; klen[r] = 0; }
+    if (!active) return;
+    if (!f.ok) atomicOr(&bst[0], BAI_E_CIGAR);
+    const bool k = f.ok && f.tid == tid && (int64_t)f.pos < end && bai_end(f.pos, f.flag, reflen) > beg;
+    keep[r] = k; klen[r] = k ? rec[r + 1] - rec[r] : 0;
+}
+
+// the kept records, bytes unchanged, one wave per record, to dst at the places the two exclusive sums give
+__global__ __launch_bounds__(256) void k_bam_gather(const uint8_t *s, const uint64_t *rec, uint64_t n_rec, const unsigned long long *kidx, const unsigned long long *koff, uint8_t *dst,
+                                                    uint64_t *dst_rec, uint64_t rec_base, uint64_t byte_base)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (r >= n_rec) return;
+    if (r == 0 && lane == 0) dst_rec[rec_base + kidx[n_rec]] = byte_base + koff[n_rec];
+    if (kidx[r + 1] == kidx[r]) return;
+    const uint64_t len = koff[r + 1] - koff[r];
+    const uint8_t *src = s + rec[r];
+    uint8_t *o = dst + byte_base + koff[r];
+    if (lane == 0) dst_rec[rec_base + kidx[r]] = byte_base + koff[r];
+    for (uint64_t i = lane; i < len; i += 64) o[i] = src[i];
+}
+
 // ------------------------------------------------------------------ host: the member chain
 struct BamFile {
     int fd = -1;
@@ -277,7 +445,7 @@ struct slx_bam {
     BamFile f;
     int device = 0;
     hipStream_t st = nullptr;
-    hipEvent_t ev[8] = {};
+    hipEvent_t ev[10] = {};
     std::string text;
     std::vector<std::string> ref_names;
     std::vector<int64_t> ref_lens;
@@ -286,10 +454,21 @@ struct slx_bam {
     uint64_t chunk_bytes = 65536;
     int idx_fail = 0;
     BamDBuf d_comp, d_desc, d_err, d_out, d_guess, d_used, d_exit_a, d_exit_b, d_count, d_base, d_state, d_rec, d_keep, d_blen, d_kidx, d_boff, d_tmp, d_bases, d_offs, d_map;
+    BamDBuf d_cs, d_cr;                                    // region mode: the kept records compacted, and their offsets
     BamHBuf h_comp, h_desc, h_err, h_out, h_rec, h_state, h_map;
-    int64_t c_members_done = 0, c_repaired = 0, c_rounds = 0, c_records = 0;
-    float us[4] = {0, 0, 0, 0};
-    std::vector<BamDBuf *> dbufs() { return {&d_comp, &d_desc, &d_err, &d_out, &d_guess, &d_used, &d_exit_a, &d_exit_b, &d_count, &d_base, &d_state, &d_rec, &d_keep, &d_blen, &d_kidx, &d_boff, &d_tmp, &d_bases, &d_offs, &d_map}; }
+    int64_t c_members_done = 0, c_repaired = 0, c_rounds = 0, c_records = 0, c_region_cand = 0, c_region_kept = 0;
+    float us[5] = {0, 0, 0, 0, 0};
+    const void *cur_stream = nullptr, *cur_rec = nullptr;  // what the current batch points to: d_out / d_rec, or d_cs / d_cr for a region batch
+    // region iteration: the index, the regions in the order given, and their chunks as member spans
+    bool has_bai = false;
+    Bai bai;
+    struct Piece { int64_t region, ma, mb; uint64_t start, tail_cut; };      // members [ma, mb): the first record at start of ma, the last tail_cut bytes of mb - 1 left out
+    std::vector<slx_bam_region> regions;
+    std::vector<Piece> pieces;
+    size_t piece_i = 0;
+    int64_t piece_cur = -1;                                // next member of pieces[piece_i]; -1: not begun
+    bool region_mode = false;
+    std::vector<BamDBuf *> dbufs() { return {&d_comp, &d_desc, &d_err, &d_out, &d_guess, &d_used, &d_exit_a, &d_exit_b, &d_count, &d_base, &d_state, &d_rec, &d_keep, &d_blen, &d_kidx, &d_boff, &d_tmp, &d_bases, &d_offs, &d_map, &d_cs, &d_cr}; }
     std::vector<BamHBuf *> hbufs() { return {&h_comp, &h_desc, &h_err, &h_out, &h_rec, &h_state, &h_map}; }
 };
 
@@ -384,8 +563,8 @@ static int bam_inflate_span(slx_bam *rd, int64_t a, int64_t b, uint64_t dst_off,
     return SLX_OK;
 }
 
-// record starts of d_out[0, n): d_rec gets n_rec + 1 offsets (the last one = end of the last whole record)
-static int bam_index(slx_bam *rd, uint64_t n, int32_t n_ref, uint64_t *n_rec, uint64_t *end, uint64_t *repaired)
+// record starts of d_out[start, start + n), the first record at start: d_rec gets n_rec + 1 offsets from start (the last one = end of the last whole record)
+static int bam_index(slx_bam *rd, uint64_t start, uint64_t n, int32_t n_ref, uint64_t *n_rec, uint64_t *end, uint64_t *repaired)
 {
     hipStream_t st = rd->st;
     const uint64_t chunk = rd->chunk_bytes, K = (n + chunk - 1) / chunk;
@@ -397,7 +576,7 @@ static int bam_index(slx_bam *rd, uint64_t n, int32_t n_ref, uint64_t *n_rec, ui
     hs[0] = 0; hs[1] = 0; hs[2] = ~0ull; hs[3] = 0; hs[4] = 0;
     BAM_HIPCHK(hipMemcpyAsync(ds, hs, 40, hipMemcpyHostToDevice, st));
     BAM_HIPCHK(hipEventRecord(rd->ev[3], st));
-    const uint8_t *s = rd->d_out.as<uint8_t>();
+    const uint8_t *s = rd->d_out.as<uint8_t>() + start;
     const unsigned grid = (unsigned)((K + 63) / 64);
     uint64_t *ex_a = rd->d_exit_a.as<uint64_t>(), *ex_b = rd->d_exit_b.as<uint64_t>();
     k_bam_guess<<<grid, 64, 0, st>>>(s, n, chunk, K, n_ref, rd->idx_fail, rd->d_guess.as<uint64_t>(), rd->d_used.as<uint64_t>(), ex_a, rd->d_count.as<uint32_t>());
@@ -475,7 +654,29 @@ static int bam_parse_header(slx_bam *rd)
     return SLX_OK;
 }
 
-extern "C" int slx_bam_open(const char *path, int device, slx_bam **out)
+static bool file_exists(const std::string &p) { struct stat sb; return stat(p.c_str(), &sb) == 0 && S_ISREG(sb.st_mode); }
+
+// the index next to the file: <path>.bai, then <path> with ".bam" replaced by ".bai"; "" when neither is there
+static std::string bai_beside(const std::string &path)
+{
+    if (file_exists(path + ".bai")) return path + ".bai";
+    if (path.size() > 4 && path.compare(path.size() - 4, 4, ".bam") == 0 && file_exists(path.substr(0, path.size() - 4) + ".bai")) return path.substr(0, path.size() - 4) + ".bai";
+    return "";
+}
+
+static int bam_load_index(slx_bam *rd, const std::string &bai_path)
+{
+    Bai b;
+    BAM_CHK(bai_load_file(bai_path.c_str(), b));
+    if (b.refs.size() != rd->ref_names.size()) {
+        slx_set_error("BAI: '%s' indexes %zu references, the header of '%s' has %zu: not this file's index", bai_path.c_str(), b.refs.size(), rd->f.path.c_str(), rd->ref_names.size());
+        return SLX_EINVAL;
+    }
+    rd->bai = std::move(b); rd->has_bai = true;
+    return SLX_OK;
+}
+
+static int bam_open_impl(const char *path, int device, slx_bam **out, bool try_index)
 {
     if (!out) { slx_set_error("slx_bam_open: rd is null"); return SLX_EINVAL; }
     *out = nullptr;
@@ -487,7 +688,66 @@ extern "C" int slx_bam_open(const char *path, int device, slx_bam **out)
     if (!rd->f.has_eof) fprintf(stderr, "[W::slx_bam_open] EOF marker is absent. The input '%s' is probably truncated\n", path);
     rd->next_member = rd->first_member; rd->carry = rd->carry0;
     rd->us[0] = rd->us[1] = 0;
+    if (try_index) {                     // as sam_index_load in the reference's Open (src/BamReader.cpp:33): a missing index is no error, a wrong one is said and left out
+        const std::string bp = bai_beside(rd->f.path);
+        if (!bp.empty() && bam_load_index(rd, bp) != SLX_OK) fprintf(stderr, "[W::slx_bam_open] index not loaded: %s\n", slx_last_error());
+    }
     *out = rd;
+    return SLX_OK;
+}
+
+extern "C" int slx_bam_open(const char *path, int device, slx_bam **out) { return bam_open_impl(path, device, out, true); }
+
+extern "C" int slx_bam_index_load(slx_bam *rd, const char *bai_path)
+{
+    if (!rd) { slx_set_error("slx_bam_index_load: reader is null"); return SLX_EINVAL; }
+    std::string bp = bai_path ? std::string(bai_path) : bai_beside(rd->f.path);
+    if (bp.empty()) { slx_set_error("BAI: no index beside '%s' (<path>.bai, or .bai in place of .bam)", rd->f.path.c_str()); return SLX_EIO; }
+    return bam_load_index(rd, bp);
+}
+extern "C" int slx_bam_has_index(const slx_bam *rd) { return rd && rd->has_bai ? 1 : 0; }
+
+static void bam_whole_file(slx_bam *rd)
+{
+    rd->region_mode = false; rd->regions.clear(); rd->pieces.clear(); rd->piece_i = 0; rd->piece_cur = -1;
+    rd->next_member = rd->first_member; rd->carry = rd->carry0;
+}
+
+extern "C" int slx_bam_set_regions(slx_bam *rd, const slx_bam_region *regs, int64_t n)
+{
+    if (!rd || n < 0 || (n && !regs)) { slx_set_error("slx_bam_set_regions: null argument"); return SLX_EINVAL; }
+    if (n == 0) { bam_whole_file(rd); return SLX_OK; }
+    if (!rd->has_bai) { slx_set_error("slx_bam_set_regions: '%s' has no index loaded (slx_bam_index_build writes one, slx_bam_index_load reads it)", rd->f.path.c_str()); return SLX_EINVAL; }
+    const int64_t nm = (int64_t)rd->f.mem.size();
+    auto member_at = [&](uint64_t file_off) -> int64_t {                 // the member that begins at file_off; nm for the end of the file; -1: none
+        if (file_off == rd->f.size) return nm;
+        int64_t lo = 0, hi = nm;
+        while (lo < hi) { const int64_t mid = (lo + hi) / 2; if (rd->f.mem[mid].file_off < file_off) lo = mid + 1; else hi = mid; }
+        return lo < nm && rd->f.mem[lo].file_off == file_off ? lo : -1;
+    };
+    std::vector<slx_bam::Piece> pieces;
+    std::vector<std::pair<uint64_t, uint64_t>> ch;
+    for (int64_t i = 0; i < n; ++i) {
+        if (regs[i].tid < 0 || regs[i].tid >= (int32_t)rd->ref_names.size()) { slx_set_error("slx_bam_set_regions: region %lld names reference %d, the header has %zu", (long long)i, regs[i].tid, rd->ref_names.size()); return SLX_EINVAL; }
+        bai_plan(rd->bai, regs[i].tid, regs[i].beg, regs[i].end, ch);
+        for (const auto &c : ch) {
+            slx_bam::Piece P;
+            P.region = i; P.ma = member_at(c.first >> 16); P.start = c.first & 0xffff;
+            const int64_t mv = member_at(c.second >> 16);
+            const uint64_t within = c.second & 0xffff;
+            bool ok = P.ma >= 0 && P.ma < nm && mv >= 0 && (within == 0 || (mv < nm && within <= rd->f.mem[mv].isize));
+            if (ok) {
+                P.mb = within ? mv + 1 : mv;
+                P.tail_cut = within ? rd->f.mem[mv].isize - within : 0;
+                ok = P.mb >= P.ma && P.start <= rd->f.mem[P.ma].isize;
+            }
+            if (!ok) { slx_set_error("BAI: the index does not fit '%s': chunk %llx - %llx names no member of the file", rd->f.path.c_str(), (unsigned long long)c.first, (unsigned long long)c.second); return SLX_EIO; }
+            if (P.mb > P.ma) pieces.push_back(P);
+        }
+    }
+    bam_whole_file(rd);
+    rd->regions.assign(regs, regs + n); rd->pieces.swap(pieces);
+    rd->region_mode = true; rd->carry.clear();
     return SLX_OK;
 }
 
@@ -512,7 +772,7 @@ extern "C" int64_t slx_bam_ref_len(const slx_bam *rd, int i) { return rd && i >=
 extern "C" int slx_bam_rewind(slx_bam *rd)
 {
     if (!rd) { slx_set_error("slx_bam_rewind: reader is null"); return SLX_EINVAL; }
-    rd->next_member = rd->first_member; rd->carry = rd->carry0;
+    bam_whole_file(rd);                  // the regions go too: the reference's Reset reopens the file (src/BamReader.cpp:56-62)
     return SLX_OK;
 }
 
@@ -540,7 +800,127 @@ extern "C" int64_t slx_bam_counter(const slx_bam *rd, const char *name)
     if (k == "us_crc") return (int64_t)rd->us[1];
     if (k == "us_index") return (int64_t)rd->us[2];
     if (k == "us_unpack") return (int64_t)rd->us[3];
+    if (k == "us_region") return (int64_t)rd->us[4];
+    if (k == "regions_done") return !rd->region_mode ? 0 : rd->piece_i < rd->pieces.size() ? rd->pieces[rd->piece_i].region : (int64_t)rd->regions.size();
+    if (k == "region_candidates") return rd->c_region_cand;
+    if (k == "region_kept") return rd->c_region_kept;
     return -1;
+}
+
+// One span of members from a towards lim behind rd->carry: at least one member, then members while the span stays within max_bytes; a span without one whole
+// record doubles.  The first record stands at start; when the span reaches lim, its last tail_cut bytes are left out.  On return d_out[start, *n) holds the
+// span, d_rec the n_rec + 1 record offsets from start, *end the bytes of the whole records (from start).
+static int bam_span(slx_bam *rd, int64_t max_bytes, int64_t a, int64_t lim, uint64_t start, uint64_t tail_cut, int64_t *done_out, uint64_t *n_out, uint64_t *n_rec, uint64_t *end,
+                    uint64_t *repaired)
+{
+    hipStream_t st = rd->st;
+    if (max_bytes < 1) max_bytes = 1;
+    uint64_t total = rd->carry.size();
+    BAM_CHK(rd->d_out.ensure(total + 8));
+    if (total) BAM_HIPCHK(hipMemcpyAsync(rd->d_out.p, rd->carry.data(), total, hipMemcpyHostToDevice, st));
+    BAM_HIPCHK(hipStreamSynchronize(st));
+    int64_t done = a, b = a;
+    *n_rec = 0; *end = 0; *repaired = 0;
+    for (;;) {
+        // the span: at least one member, then while it stays within max_bytes; a span without one whole record doubles
+        uint64_t bytes = total;
+        if (b == done) { while (b < lim && (b == done || bytes + rd->f.mem[b].isize <= (uint64_t)max_bytes)) bytes += rd->f.mem[b++].isize; }
+        uint64_t span = 0;
+        for (int64_t i = done; i < b; ++i) span += rd->f.mem[i].isize;
+        BAM_CHK(rd->d_out.ensure(total + span + 8, st, total));
+        BAM_CHK(bam_inflate_span(rd, done, b, total, total + span));
+        total += span; done = b;
+        const uint64_t cut = done >= lim ? tail_cut : 0;
+        if (total < start + cut) { slx_set_error("BAM: '%s': the index does not fit the file (a chunk of %llu bytes begins at %llu and leaves out %llu)", rd->f.path.c_str(), (unsigned long long)total, (unsigned long long)start, (unsigned long long)cut); return SLX_EIO; }
+        *n_out = total - cut;
+        BAM_CHK(bam_index(rd, start, *n_out - start, (int32_t)rd->ref_names.size(), n_rec, end, repaired));
+        if (*n_rec || done >= lim) break;
+        b = std::min(lim, done + std::max<int64_t>(1, done - a));
+    }
+    *done_out = done;
+    return SLX_OK;
+}
+
+// rd->carry = d_out[from, upto), enqueued
+static int bam_take_carry(slx_bam *rd, uint64_t from, uint64_t upto)
+{
+    rd->carry.resize(upto - from);
+    if (upto > from) BAM_HIPCHK(hipMemcpyAsync(rd->carry.data(), rd->d_out.as<uint8_t>() + from, upto - from, hipMemcpyDeviceToHost, rd->st));
+    return SLX_OK;
+}
+
+// a batch of the regions: spans of the pieces' members, their records tested against the region and the kept ones compacted behind one another in d_cs / d_cr
+static int bam_next_regions(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
+{
+    typedef unsigned long long ull;
+    hipStream_t st = rd->st;
+    if (max_bytes < 1) max_bytes = 1;
+    BAM_CHK(rd->d_state.ensure(64)); BAM_CHK(rd->h_state.ensure(64));
+    ull *hs = rd->h_state.as<ull>(), *ds = rd->d_state.as<ull>();
+    uint64_t kept = 0, bytes = 0, used = 0, repaired = 0;
+    int64_t members = 0;
+    while (rd->piece_i < rd->pieces.size()) {
+        const slx_bam::Piece &P = rd->pieces[rd->piece_i];
+        if (rd->piece_cur < 0) { rd->piece_cur = P.ma; rd->carry.clear(); }
+        const int64_t a = rd->piece_cur;
+        // as many regions as fit max_bytes; a batch without a kept record goes on, since n_records == 0 is the end of the last region
+        if (kept && used + rd->carry.size() + rd->f.mem[a].isize > (uint64_t)max_bytes) break;
+        const int64_t room = kept && used < (uint64_t)max_bytes ? max_bytes - (int64_t)used : max_bytes;
+        const uint64_t start = a == P.ma ? P.start : 0;
+        int64_t done = a;
+        uint64_t n = 0, n_rec = 0, end = 0, rep = 0;
+        BAM_CHK(bam_span(rd, room, a, P.mb, start, P.tail_cut, &done, &n, &n_rec, &end, &rep));
+        for (int64_t i = a; i < done; ++i) used += rd->f.mem[i].isize;
+        members += done - a; repaired += rep;
+        if (done >= P.mb) {
+            if (start + end != n) { slx_set_error("BAM: '%s': the index does not fit the file (the chunk that ends in the member at %llu ends inside a record)", rd->f.path.c_str(), (unsigned long long)rd->f.mem[P.mb - 1].file_off); return SLX_EIO; }
+            rd->carry.clear();
+        } else BAM_CHK(bam_take_carry(rd, start + end, n));
+        if (n_rec) {
+            const slx_bam_region &g = rd->regions[P.region];
+            for (BamDBuf *b : {&rd->d_keep, &rd->d_blen, &rd->d_kidx, &rd->d_boff}) BAM_CHK(b->ensure(8 * (n_rec + 1)));
+            BAM_HIPCHK(hipMemsetAsync(ds + 5, 0, 8, st));
+            BAM_HIPCHK(hipEventRecord(rd->ev[7], st));
+            const uint8_t *s = rd->d_out.as<uint8_t>() + start;
+            const uint64_t *rec = rd->d_rec.as<uint64_t>();
+            k_bam_region_keep<<<(unsigned)((n_rec + 1 + 255) / 256), 256, 0, st>>>(s, rec, n_rec, g.tid, g.beg, g.end, rd->d_keep.as<ull>(), rd->d_blen.as<ull>(), ds + 5);
+            BAM_HIPCHK(hipGetLastError());
+            size_t tb = 0;
+            BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, rd->d_keep.as<ull>(), rd->d_kidx.as<ull>(), (int)(n_rec + 1), st));
+            BAM_CHK(rd->d_tmp.ensure(tb + 8));
+            BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(rd->d_tmp.p, tb, rd->d_keep.as<ull>(), rd->d_kidx.as<ull>(), (int)(n_rec + 1), st));
+            BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(rd->d_tmp.p, tb, rd->d_blen.as<ull>(), rd->d_boff.as<ull>(), (int)(n_rec + 1), st));
+            BAM_HIPCHK(hipMemcpyAsync(hs + 5, rd->d_kidx.as<ull>() + n_rec, 8, hipMemcpyDeviceToHost, st));
+            BAM_HIPCHK(hipMemcpyAsync(hs + 6, rd->d_boff.as<ull>() + n_rec, 8, hipMemcpyDeviceToHost, st));
+            BAM_HIPCHK(hipMemcpyAsync(hs + 7, ds + 5, 8, hipMemcpyDeviceToHost, st));
+            BAM_HIPCHK(slx_wait_stream(st));
+            if (hs[7]) { slx_set_error("BAM: '%s': a record's name and CIGAR pass its block_size", rd->f.path.c_str()); return SLX_EIO; }
+            const uint64_t kn = hs[5], kb = hs[6];
+            BAM_CHK(rd->d_cs.ensure(bytes + kb + 8, st, bytes)); BAM_CHK(rd->d_cr.ensure(8 * (kept + kn + 1), st, 8 * kept));
+            k_bam_gather<<<(unsigned)((n_rec + 3) / 4), 256, 0, st>>>(s, rec, n_rec, rd->d_kidx.as<ull>(), rd->d_boff.as<ull>(), rd->d_cs.as<uint8_t>(), rd->d_cr.as<uint64_t>(), kept, bytes);
+            BAM_HIPCHK(hipGetLastError());
+            BAM_HIPCHK(hipEventRecord(rd->ev[8], st));
+            BAM_HIPCHK(slx_wait_stream(st));
+            rd->us[4] += ev_us(rd->ev[7], rd->ev[8]);
+            kept += kn; bytes += kb;
+            rd->c_region_cand += (int64_t)n_rec; rd->c_region_kept += (int64_t)kn;
+        } else BAM_HIPCHK(slx_wait_stream(st));
+        if (done >= P.mb) { ++rd->piece_i; rd->piece_cur = -1; }
+        else { rd->piece_cur = done; if (kept) break; used = 0; }
+    }
+    rd->c_repaired += (int64_t)repaired; rd->c_records += (int64_t)kept;
+    if (kept) {
+        BAM_CHK(rd->h_out.ensure(bytes + 8)); BAM_CHK(rd->h_rec.ensure(8 * (kept + 1)));
+        BAM_HIPCHK(hipMemcpyAsync(rd->h_out.p, rd->d_cs.p, bytes, hipMemcpyDeviceToHost, st));
+        BAM_HIPCHK(hipMemcpyAsync(rd->h_rec.p, rd->d_cr.p, 8 * (kept + 1), hipMemcpyDeviceToHost, st));
+        BAM_HIPCHK(slx_wait_stream(st));
+    }
+    out->n_records = (int64_t)kept; out->n_bytes = (int64_t)bytes;
+    out->stream = rd->h_out.as<uint8_t>(); out->rec_off = rd->h_rec.as<uint64_t>();
+    out->d_stream = rd->d_cs.p; out->d_rec_off = rd->d_cr.p;
+    out->n_members = members; out->n_repaired_chunks = (int64_t)repaired;
+    rd->cur_stream = rd->d_cs.p; rd->cur_rec = rd->d_cr.p;
+    return SLX_OK;
 }
 
 extern "C" int slx_bam_next(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
@@ -548,32 +928,15 @@ extern "C" int slx_bam_next(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
     if (!rd || !out) { slx_set_error("slx_bam_next: null argument"); return SLX_EINVAL; }
     memset(out, 0, sizeof *out);
     BAM_HIPCHK(hipSetDevice(rd->device));
+    rd->us[0] = rd->us[1] = rd->us[2] = rd->us[4] = 0;
+    if (rd->region_mode) return bam_next_regions(rd, max_bytes, out);
     const int64_t nm = (int64_t)rd->f.mem.size();
     const int64_t a = rd->next_member;
-    rd->us[0] = rd->us[1] = rd->us[2] = 0;
     if (a >= nm && rd->carry.empty()) return SLX_OK;
-    if (max_bytes < 1) max_bytes = 1;
     hipStream_t st = rd->st;
-    uint64_t total = rd->carry.size();
-    BAM_CHK(rd->d_out.ensure(total + 8));
-    if (total) BAM_HIPCHK(hipMemcpyAsync(rd->d_out.p, rd->carry.data(), total, hipMemcpyHostToDevice, st));
-    BAM_HIPCHK(hipStreamSynchronize(st));
-    int64_t done = a, b = a;
-    uint64_t n_rec = 0, end = 0, repaired = 0;
-    for (;;) {
-        // the span: at least one member, then while it stays within max_bytes; a span without one whole record doubles
-        uint64_t bytes = total;
-        if (b == done) { while (b < nm && (b == done || bytes + rd->f.mem[b].isize <= (uint64_t)max_bytes)) bytes += rd->f.mem[b++].isize; }
-        else bytes = total;
-        uint64_t span = 0;
-        for (int64_t i = done; i < b; ++i) span += rd->f.mem[i].isize;
-        BAM_CHK(rd->d_out.ensure(total + span + 8, st, total));
-        BAM_CHK(bam_inflate_span(rd, done, b, total, total + span));
-        total += span; done = b;
-        BAM_CHK(bam_index(rd, total, (int32_t)rd->ref_names.size(), &n_rec, &end, &repaired));
-        if (n_rec || done >= nm) break;
-        b = std::min(nm, done + std::max<int64_t>(1, done - a));
-    }
+    int64_t done = a;
+    uint64_t total = 0, n_rec = 0, end = 0, repaired = 0;
+    BAM_CHK(bam_span(rd, max_bytes, a, nm, 0, 0, &done, &total, &n_rec, &end, &repaired));
     if (!n_rec && total) {
         slx_set_error("BAM: '%s' ends inside a record (%llu bytes after the last whole record)", rd->f.path.c_str(), (unsigned long long)total);
         return SLX_EIO;
@@ -582,22 +945,188 @@ extern "C" int slx_bam_next(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
     BAM_CHK(rd->h_out.ensure(end + 8)); BAM_CHK(rd->h_rec.ensure(8 * (n_rec + 1)));
     if (end) BAM_HIPCHK(hipMemcpyAsync(rd->h_out.p, rd->d_out.p, end, hipMemcpyDeviceToHost, st));
     if (n_rec) BAM_HIPCHK(hipMemcpyAsync(rd->h_rec.p, rd->d_rec.p, 8 * (n_rec + 1), hipMemcpyDeviceToHost, st));
-    rd->carry.resize(total - end);
-    if (total > end) BAM_HIPCHK(hipMemcpyAsync(rd->carry.data(), rd->d_out.as<uint8_t>() + end, total - end, hipMemcpyDeviceToHost, st));
+    BAM_CHK(bam_take_carry(rd, end, total));
     BAM_HIPCHK(slx_wait_stream(st));
     rd->c_repaired += (int64_t)repaired; rd->c_records += (int64_t)n_rec;
     out->n_records = (int64_t)n_rec; out->n_bytes = (int64_t)end;
     out->stream = rd->h_out.as<uint8_t>(); out->rec_off = rd->h_rec.as<uint64_t>();
     out->d_stream = rd->d_out.p; out->d_rec_off = rd->d_rec.p;
     out->n_members = done - a; out->n_repaired_chunks = (int64_t)repaired;
+    rd->cur_stream = rd->d_out.p; rd->cur_rec = rd->d_rec.p;
     return SLX_OK;
 }
+
+// ------------------------------------------------------------------ the BAI build
+namespace {
+struct BaiBuild {
+    BamDBuf ne_start, ne_file, lin_off, lin, first, last, n_map, n_unmap, n_intv, bst, carry, key, tp, vbeg, vend, head, hidx, ckey, cbeg, cend, skey, sidx_in, sidx, tmp;
+    ~BaiBuild() { for (BamDBuf *b : {&ne_start, &ne_file, &lin_off, &lin, &first, &last, &n_map, &n_unmap, &n_intv, &bst, &carry, &key, &tp, &vbeg, &vend, &head, &hidx, &ckey, &cbeg, &cend, &skey, &sidx_in, &sidx, &tmp}) b->release(); }
+};
+void put_u32(std::string &o, uint32_t v) { o.append((const char *)&v, 4); }
+void put_u64(std::string &o, uint64_t v) { o.append((const char *)&v, 8); }
+}
+
+// the whole file through the reader's inflate, CRC and record-index kernels, batch by batch, and the index kernels behind them; bai: the file's bytes
+static int bai_build_body(slx_bam *rd, int64_t batch_bytes, BaiBuild &B, std::string &bai)
+{
+    typedef unsigned long long ull;
+    hipStream_t st = rd->st;
+    const int64_t nm = (int64_t)rd->f.mem.size();
+    const int32_t n_ref = (int32_t)rd->ref_names.size();
+    std::vector<uint64_t> start_all(nm + 1, 0), ne_start, ne_file, lin_off(n_ref + 1, 0);
+    uint64_t behind = 0;
+    for (int64_t i = 0; i < nm; ++i) {
+        const slx_bam_member &m = rd->f.mem[i];
+        start_all[i + 1] = start_all[i] + m.isize;
+        if (m.isize) { ne_start.push_back(start_all[i]); ne_file.push_back(m.file_off); behind = m.file_off + m.data_off + m.data_len + 8; }
+    }
+    // windows of a reference: its length's, and one to spare; a record that passes them is refused (BAI_E_SPAN)
+    for (int32_t t = 0; t < n_ref; ++t) lin_off[t + 1] = lin_off[t] + ((uint64_t)std::max<int64_t>(rd->ref_lens[t], 0) >> 14) + 2;
+    const uint64_t nn = ne_start.size(), n_win = lin_off[n_ref], R = (uint64_t)std::max(n_ref, 1);
+    auto up = [&](BamDBuf &b, const void *src, size_t bytes) -> int {
+        BAM_CHK(b.ensure(bytes + 8));
+        if (bytes) BAM_HIPCHK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st));
+        return SLX_OK;
+    };
+    auto fill = [&](BamDBuf &b, int byte, size_t bytes) -> int {
+        BAM_CHK(b.ensure(bytes + 8));
+        BAM_HIPCHK(hipMemsetAsync(b.p, byte, bytes + 8, st));
+        return SLX_OK;
+    };
+    auto down = [&](void *dst, const void *src, size_t bytes) -> int {
+        if (bytes) BAM_HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
+        return SLX_OK;
+    };
+    BAM_CHK(up(B.ne_start, ne_start.data(), 8 * nn)); BAM_CHK(up(B.ne_file, ne_file.data(), 8 * nn)); BAM_CHK(up(B.lin_off, lin_off.data(), 8 * (size_t)(n_ref + 1)));
+    BAM_CHK(fill(B.lin, 0xff, 8 * n_win)); BAM_CHK(fill(B.first, 0xff, 8 * R)); BAM_CHK(fill(B.last, 0, 8 * R)); BAM_CHK(fill(B.n_map, 0, 8 * R)); BAM_CHK(fill(B.n_unmap, 0, 8 * R));
+    BAM_CHK(fill(B.n_intv, 0, 4 * R));
+    const ull bst0[3] = {0, ~0ull, 0}, carry0[4] = {BAI_NOKEY, 0, BAI_NOKEY, 0};
+    BAM_CHK(up(B.bst, bst0, sizeof bst0)); BAM_CHK(up(B.carry, carry0, sizeof carry0));
+    BAM_HIPCHK(hipStreamSynchronize(st));                  // (the uploads read this frame's memory)
+    bai_dev d;
+    d.ne_start = B.ne_start.as<uint64_t>(); d.ne_file = B.ne_file.as<uint64_t>(); d.nn = nn; d.total = start_all[nm]; d.behind = behind;
+    d.lin_off = B.lin_off.as<uint64_t>(); d.lin = B.lin.as<ull>(); d.ref_first = B.first.as<ull>(); d.ref_last = B.last.as<ull>(); d.n_map = B.n_map.as<ull>(); d.n_unmap = B.n_unmap.as<ull>();
+    d.n_intv = B.n_intv.as<uint32_t>(); d.n_ref = n_ref;
+    BAM_CHK(rd->h_state.ensure(64));
+    ull *hs = rd->h_state.as<ull>(), *bst = B.bst.as<ull>();
+    uint64_t chunk_base = 0, ord_base = 0;
+    int flip = 0;
+    for (;;) {
+        const int64_t a = rd->next_member;
+        if (a >= nm && rd->carry.empty()) break;
+        const uint64_t base_off = start_all[a] - rd->carry.size();
+        int64_t done = a;
+        uint64_t total = 0, n = 0, end = 0, rep = 0;
+        BAM_CHK(bam_span(rd, batch_bytes, a, nm, 0, 0, &done, &total, &n, &end, &rep));
+        if (!n && total) { slx_set_error("BAM: '%s' ends inside a record (%llu bytes after the last whole record)", rd->f.path.c_str(), (unsigned long long)total); return SLX_EIO; }
+        rd->next_member = done;
+        BAM_CHK(bam_take_carry(rd, end, total));
+        BAM_HIPCHK(slx_wait_stream(st));
+        if (!n) break;
+        for (BamDBuf *b : {&B.key, &B.tp, &B.vbeg, &B.vend, &B.head, &B.hidx}) BAM_CHK(b->ensure(8 * (n + 1)));
+        for (BamDBuf *b : {&B.ckey, &B.cbeg, &B.cend}) BAM_CHK(b->ensure(8 * (chunk_base + n + 1), st, 8 * chunk_base));
+        const uint64_t cap = chunk_base + n + 1;
+        const uint8_t *s = rd->d_out.as<uint8_t>();
+        const uint64_t *rec = rd->d_rec.as<uint64_t>();
+        BAM_HIPCHK(hipEventRecord(rd->ev[7], st));
+        k_bai_rec<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(s, rec, n, base_off, d, B.key.as<ull>(), B.tp.as<ull>(), B.vbeg.as<ull>(), B.vend.as<ull>(), bst);
+        BAM_HIPCHK(hipGetLastError());
+        k_bai_heads<<<(unsigned)((n + 1 + 255) / 256), 256, 0, st>>>(B.key.as<ull>(), B.tp.as<ull>(), n, ord_base, B.carry.as<ull>() + 2 * flip, B.carry.as<ull>() + 2 * (flip ^ 1), B.head.as<ull>(), bst);
+        BAM_HIPCHK(hipGetLastError());
+        size_t tb = 0;
+        BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, B.head.as<ull>(), B.hidx.as<ull>(), (int)(n + 1), st));
+        BAM_CHK(B.tmp.ensure(tb + 8));
+        BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(B.tmp.p, tb, B.head.as<ull>(), B.hidx.as<ull>(), (int)(n + 1), st));
+        k_bai_chunks<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(B.key.as<ull>(), B.vbeg.as<ull>(), B.vend.as<ull>(), B.head.as<ull>(), B.hidx.as<ull>(), n, chunk_base, cap, B.ckey.as<ull>(),
+                                                                  B.cbeg.as<ull>(), B.cend.as<ull>());
+        BAM_HIPCHK(hipGetLastError());
+        BAM_HIPCHK(hipEventRecord(rd->ev[8], st));
+        BAM_CHK(down(hs, B.hidx.as<ull>() + n, 8)); BAM_CHK(down(hs + 1, bst, 16));
+        BAM_HIPCHK(slx_wait_stream(st));
+        rd->us[4] += ev_us(rd->ev[7], rd->ev[8]);
+        if (hs[2] != ~0ull) { slx_set_error("BAM: '%s' is not coordinate-sorted: record %llu sorts before its predecessor; no index written", rd->f.path.c_str(), hs[2]); return SLX_EINVAL; }
+        if (hs[1] & BAI_E_CIGAR) { slx_set_error("BAM: '%s': a record's name and CIGAR pass its block_size", rd->f.path.c_str()); return SLX_EIO; }
+        if (hs[1] & BAI_E_TID) { slx_set_error("BAM: '%s': a record names a reference outside the header's %d", rd->f.path.c_str(), n_ref); return SLX_EIO; }
+        if (hs[1] & BAI_E_SPAN) { slx_set_error("BAM: '%s': a record reaches past the end of its reference; no index written", rd->f.path.c_str()); return SLX_EINVAL; }
+        chunk_base += hs[0]; ord_base += n; flip ^= 1;
+        rd->c_records += (int64_t)n; rd->c_repaired += (int64_t)rep;
+    }
+    // chunks by (tid, bin); the radix sort is stable, so inside a bin they stay in file order, which is the order of their begins
+    const uint64_t nc = chunk_base;
+    std::vector<ull> skey(nc), cbeg(nc), cend(nc), lin(n_win), first(R), last(R), n_map(R), n_unmap(R);
+    std::vector<uint32_t> sidx(nc), n_intv(R);
+    ull n_no_coor = 0;
+    if (nc) {
+        if (nc >= (1ull << 31)) { slx_set_error("BAI: %llu chunks", (ull)nc); return SLX_EUNSUPPORTED; }
+        BAM_CHK(B.skey.ensure(8 * nc)); BAM_CHK(B.sidx_in.ensure(4 * nc)); BAM_CHK(B.sidx.ensure(4 * nc));
+        k_bai_iota<<<(unsigned)((nc + 255) / 256), 256, 0, st>>>(B.sidx_in.as<uint32_t>(), nc);
+        BAM_HIPCHK(hipGetLastError());
+        size_t tb = 0;
+        BAM_HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, B.ckey.as<ull>(), B.skey.as<ull>(), B.sidx_in.as<uint32_t>(), B.sidx.as<uint32_t>(), (int)nc, 0, 64, st));
+        BAM_CHK(B.tmp.ensure(tb + 8));
+        BAM_HIPCHK(hipcub::DeviceRadixSort::SortPairs(B.tmp.p, tb, B.ckey.as<ull>(), B.skey.as<ull>(), B.sidx_in.as<uint32_t>(), B.sidx.as<uint32_t>(), (int)nc, 0, 64, st));
+        BAM_CHK(down(skey.data(), B.skey.p, 8 * nc)); BAM_CHK(down(sidx.data(), B.sidx.p, 4 * nc)); BAM_CHK(down(cbeg.data(), B.cbeg.p, 8 * nc)); BAM_CHK(down(cend.data(), B.cend.p, 8 * nc));
+    }
+    if (n_ref) {
+        k_bai_fill<<<(unsigned)n_ref, 64, 0, st>>>(d);
+        BAM_HIPCHK(hipGetLastError());
+        BAM_CHK(down(lin.data(), B.lin.p, 8 * n_win)); BAM_CHK(down(first.data(), B.first.p, 8 * R)); BAM_CHK(down(last.data(), B.last.p, 8 * R));
+        BAM_CHK(down(n_map.data(), B.n_map.p, 8 * R)); BAM_CHK(down(n_unmap.data(), B.n_unmap.p, 8 * R)); BAM_CHK(down(n_intv.data(), B.n_intv.p, 4 * R));
+    }
+    BAM_CHK(down(&n_no_coor, bst + 2, 8));
+    BAM_HIPCHK(slx_wait_stream(st));
+    // the host only lays the bytes out: per reference its bins in ascending number, the pseudo-bin last, then the windows
+    bai.assign("BAI\1", 4);
+    put_u32(bai, (uint32_t)n_ref);
+    uint64_t c = 0;
+    for (int32_t t = 0; t < n_ref; ++t) {
+        if (n_map[t] + n_unmap[t] == 0) { put_u32(bai, 0); put_u32(bai, 0); continue; }
+        uint64_t e = c, n_bin = 0;
+        while (e < nc && (int32_t)(skey[e] >> 32) == t) { if (e == c || skey[e] != skey[e - 1]) ++n_bin; ++e; }
+        put_u32(bai, (uint32_t)n_bin + 1);
+        while (c < e) {
+            uint64_t f = c;
+            while (f < e && skey[f] == skey[c]) ++f;
+            put_u32(bai, (uint32_t)skey[c]); put_u32(bai, (uint32_t)(f - c));
+            for (; c < f; ++c) { put_u64(bai, cbeg[sidx[c]]); put_u64(bai, cend[sidx[c]]); }
+        }
+        put_u32(bai, BAI_META_BIN); put_u32(bai, 2);
+        put_u64(bai, first[t]); put_u64(bai, last[t]); put_u64(bai, n_map[t]); put_u64(bai, n_unmap[t]);
+        put_u32(bai, n_intv[t]);
+        for (uint32_t w = 0; w < n_intv[t]; ++w) put_u64(bai, lin[lin_off[t] + w]);
+    }
+    put_u64(bai, n_no_coor);
+    return SLX_OK;
+}
+
+extern "C" int slx_bam_index_build_ex(const char *bam_path, int device, const char *bai_path, int64_t batch_bytes, int64_t chunk_bytes)
+{
+    slx_bam *rd = nullptr;
+    BAM_CHK(bam_open_impl(bam_path, device, &rd, false));
+    if (chunk_bytes >= 64) rd->chunk_bytes = (uint64_t)chunk_bytes;
+    std::string bai;
+    int rc;
+    {
+        BaiBuild B;
+        rc = bai_build_body(rd, batch_bytes > 0 ? batch_bytes : (int64_t)64 << 20, B, bai);
+        (void)hipStreamSynchronize(rd->st);
+    }
+    slx_bam_close(rd);
+    if (rc != SLX_OK) return rc;
+    const std::string out = bai_path ? std::string(bai_path) : std::string(bam_path) + ".bai";
+    FILE *f = fopen(out.c_str(), "wb");
+    if (!f) { slx_set_error("BAI: cannot write '%s'", out.c_str()); return SLX_EIO; }
+    const bool ok = fwrite(bai.data(), 1, bai.size(), f) == bai.size();
+    if (fclose(f) != 0 || !ok) { slx_set_error("BAI: cannot write '%s'", out.c_str()); return SLX_EIO; }
+    return SLX_OK;
+}
+extern "C" int slx_bam_index_build(const char *bam_path, int device, const char *bai_path) { return slx_bam_index_build_ex(bam_path, device, bai_path, 0, 0); }
 
 extern "C" int slx_bam_reads_device(slx_bam *rd, const slx_bam_batch *batch, int skip_flags, int original_strand, void **d_bases, void **d_offs, int64_t *n_reads,
                                     const int64_t **rec_of_read)
 {
     if (!rd || !batch || !d_bases || !d_offs || !n_reads) { slx_set_error("slx_bam_reads_device: null argument"); return SLX_EINVAL; }
-    if (batch->d_stream != rd->d_out.p || batch->d_rec_off != rd->d_rec.p) { slx_set_error("slx_bam_reads_device: the batch is not the reader's current one"); return SLX_EINVAL; }
+    if (!rd->cur_stream || batch->d_stream != rd->cur_stream || batch->d_rec_off != rd->cur_rec) { slx_set_error("slx_bam_reads_device: the batch is not the reader's current one"); return SLX_EINVAL; }
     BAM_HIPCHK(hipSetDevice(rd->device));
     hipStream_t st = rd->st;
     const uint64_t n = (uint64_t)batch->n_records;
@@ -608,8 +1137,8 @@ extern "C" int slx_bam_reads_device(slx_bam *rd, const slx_bam_batch *batch, int
     hs[2] = ~0ull;
     BAM_HIPCHK(hipMemcpyAsync(ds + 2, hs + 2, 8, hipMemcpyHostToDevice, st));
     BAM_HIPCHK(hipEventRecord(rd->ev[5], st));
-    const uint8_t *s = rd->d_out.as<uint8_t>();
-    const uint64_t *rec = rd->d_rec.as<uint64_t>();
+    const uint8_t *s = (const uint8_t *)rd->cur_stream;
+    const uint64_t *rec = (const uint64_t *)rd->cur_rec;
     k_bam_keep<<<(unsigned)((n + 1 + 255) / 256), 256, 0, st>>>(s, rec, n, (uint32_t)skip_flags & 0xffffu, rd->d_keep.as<ull>(), rd->d_blen.as<ull>(), ds);
     BAM_HIPCHK(hipGetLastError());
     size_t tb = 0, tb2 = 0;
