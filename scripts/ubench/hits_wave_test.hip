@@ -1,12 +1,14 @@
 // Standalone harness for a wave-per-read form of k_hits (the glue's std::sort of a read's hits by (mapq desc, rid, pos) + the two secondary filters, src/BWAAligner.cpp:133-146):
 // synthetic reads with 13..1500 hits, some with tied keys; the kernel's order and kept count against the same algorithm on the host.
-//   hipcc --offload-arch=gfx950 -O3 -o /tmp/hits_wave_test scripts/ubench/hits_wave_test.hip && /tmp/hits_wave_test [variant]
+// The slot is taken with wave_take (dev_wave.h), as in the library.  variant 0: block barriers, 1: wave barriers.
+//   hipcc --offload-arch=gfx950 -O3 -Iseqlib_amd/csrc -o /tmp/hits_wave_test scripts/ubench/hits_wave_test.hip && /tmp/hits_wave_test [variant]
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
 #include <vector>
+#include "dev_wave.h"
 
 struct DHit { long long pos; int rid, flag, mapq, score, nm, n_cigar; long long cig_start; };
 #define N_MAX 2048
@@ -20,12 +22,7 @@ __global__ void __launch_bounds__(64) k_hits_wave(const DHit *hits, const long l
     const int lane = threadIdx.x;
     if (mode < 0) return;
     for (;;) {
-        int slot = 0;
-        int l0 = lane;
-        if (VARIANT < 2) asm volatile("" : "+v"(l0));          // the lane number is made opaque INSIDE the loop: with a loop-invariant `lane == 0` the compiler unswitched the loop on it
-                                                                // (lanes 1..63 got a copy of the loop in which slot stays 0 and readfirstlane reads lane 1: read 0 for ever)
-        if (l0 == 0) slot = (int)atomicAdd(queue, 1u);
-        slot = __builtin_amdgcn_readfirstlane(slot);
+        const int slot = (int)wave_take(queue, 1u);
         if (slot >= n_reads) break;
         const int r = slot;
         const DHit *H = hits + off[r];
@@ -105,6 +102,7 @@ __global__ void __launch_bounds__(64) k_hits_wave(const DHit *hits, const long l
 int main(int argc, char **argv)
 {
     const int variant = argc > 1 ? atoi(argv[1]) : 0;
+    if (variant != 0 && variant != 1) { fprintf(stderr, "variant: 0 or 1\n"); return 2; }
     const int n_reads = argc > 2 ? atoi(argv[2]) : 20000;
     std::mt19937 rng(7);
     std::vector<long long> off(n_reads + 1, 0);
@@ -126,8 +124,7 @@ int main(int argc, char **argv)
     fprintf(stderr, "setup done\n");
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     hipEventRecord(e0);
-    if (variant == 2) hipLaunchKernelGGL(k_hits_wave<2>, dim3(1024), dim3(64), 0, 0, d_hits, d_off, d_nh, d_out, d_order, n_reads, d_q, 0.9, 10, mode);
-    else if (variant == 0) hipLaunchKernelGGL(k_hits_wave<0>, dim3(1024), dim3(64), 0, 0, d_hits, d_off, d_nh, d_out, d_order, n_reads, d_q, 0.9, 10, mode);
+    if (variant == 0) hipLaunchKernelGGL(k_hits_wave<0>, dim3(1024), dim3(64), 0, 0, d_hits, d_off, d_nh, d_out, d_order, n_reads, d_q, 0.9, 10, mode);
     else hipLaunchKernelGGL(k_hits_wave<1>, dim3(1024), dim3(64), 0, 0, d_hits, d_off, d_nh, d_out, d_order, n_reads, d_q, 0.9, 10, mode);
     hipEventRecord(e1);
     const hipError_t e = hipDeviceSynchronize();

@@ -27,7 +27,7 @@ def build(force=False, verbose=False):
     hdr_align = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc")) and not is_fml(f) and not is_bam(f)] + [os.path.join(ROOT, "include", "seqlib_amd.h")]
     hdr_bam = [os.path.join(CSRC, f) for f in ("dev_inflate.h", "dev_bamidx.h", "dev_bai.h", "bai_host.h", "slx_internal.h")] + [os.path.join(ROOT, "include", f) for f in ("seqlib_amd.h", "seqlib_amd_bam.h")]
     hdr_fml = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h") and is_fml(f)] + \
-              [os.path.join(CSRC, "slx_internal.h"), os.path.join(ROOT, "include", "seqlib_amd.h"), os.path.join(ROOT, "include", "seqlib_amd_fml.h")]
+              [os.path.join(CSRC, "slx_internal.h"), os.path.join(CSRC, "dev_wave.h"), os.path.join(ROOT, "include", "seqlib_amd.h"), os.path.join(ROOT, "include", "seqlib_amd_fml.h")]
     objs, procs = [], []
     os.makedirs(os.path.join(HERE, "build"), exist_ok=True)
     for s in SOURCES:                      # the translation units compile side by side

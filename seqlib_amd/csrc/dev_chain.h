@@ -15,10 +15,8 @@
 // would all diverge from each other and run serially, whereas alone in a wave a heavy read costs only its own time.
 __device__ __forceinline__ int next_slot(unsigned int *queue, int per_wave = 0)
 {
-    unsigned int base = 0;
     const int lane = threadIdx.x & 63;
-    if (lane == 0) base = atomicAdd(queue, per_wave ? 1u : 64u);
-    base = __shfl(base, 0, 64);
+    const unsigned int base = wave_take(queue, per_wave ? 1u : 64u);
     if (per_wave) return lane == 0 ? (int)base : 0x7fffffff;
     return (int)(base + lane);
 }
@@ -32,11 +30,6 @@ struct ReadWS {               // views into the per-seed-slot arrays for one rea
     __device__ __forceinline__ int s_qbeg(int s) const { return QP_HI(s_ql[s]); }
     __device__ __forceinline__ int s_len(int s) const { return QP_LO(s_ql[s]); }
 };
-
-__device__ __forceinline__ uint64_t rfl_u64(uint64_t v)
-{
-    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32 | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-}
 
 __device__ __forceinline__ ReadWS make_ws(const Chunk &ck, int r);
 

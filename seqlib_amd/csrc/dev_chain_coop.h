@@ -287,9 +287,7 @@ __global__ void __launch_bounds__(64) k_chain_coop(DevFM<I> fm, DevRef R, Chunk 
     const int lane = threadIdx.x;
     const int n_todo = __builtin_amdgcn_readfirstlane((int)*n_slots);
     for (;;) {
-        int slot = 0;
-        if (lane == 0) slot = (int)atomicAdd(queue, 1u);
-        slot = __builtin_amdgcn_readfirstlane(slot);
+        const int slot = (int)wave_take(queue, 1u);
         if (slot >= n_todo) break;
         const int r = order ? order[slot] : slot;
         const bool mine = !FINAL || __builtin_amdgcn_readfirstlane(ck.n_chain[r]) == -2;

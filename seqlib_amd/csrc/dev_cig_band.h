@@ -321,14 +321,10 @@ static __device__ __noinline__ bool dev_cig_band_job(const DevRef &R, const Chun
                     continue;
                 }
                 __syncthreads();
-                if (threadIdx.x == 0) SB->off = atomicAdd(ck.zused, need);
+                if (block_tid() == 0) SB->off = atomicAdd(ck.zused, need);
                 __syncthreads();
                 off = SB->off;
-            } else {
-            if (lane == 0) off = atomicAdd(ck.zused, need);
-            off = ((unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(off >> 32)) << 32) |
-                  (unsigned int)__builtin_amdgcn_readfirstlane((int)(off & 0xffffffffull));
-            }
+            } else off = wave_take_u64(ck.zused, need);
             if (off + need > ck.zcap) { if (lane == 0 && wave0) atomicOr(ck.flags, OVF_ZARENA); return true; }
             z = ck.zarena + off;
             const int cols = 2 * ww + 1;
@@ -359,11 +355,8 @@ static __device__ __noinline__ bool dev_cig_band_job(const DevRef &R, const Chun
         dev_traceback_wave(z, n_col, lq, rlen, w_used, lane, [&](int, int) { ++n_ops; });
     }
     n_ops = __builtin_amdgcn_readfirstlane(n_ops);
-    unsigned long long base = 0;
     const unsigned long long need = (unsigned long long)n_ops + 2;
-    if (lane == 0) base = atomicAdd(ck.cigused, need);
-    base = ((unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(base >> 32)) << 32) |
-           (unsigned int)__builtin_amdgcn_readfirstlane((int)(base & 0xffffffffull));
+    const unsigned long long base = wave_take_u64(ck.cigused, need);
     if (base + need > ck.cigcap) { if (lane == 0) atomicOr(ck.flags, OVF_CIGAR); return true; }
     uint32_t *cg = ck.cigpool + base + 1;
     if (valid) {
@@ -393,9 +386,7 @@ __global__ void __launch_bounds__(64) k_cig_band(DevRef R, Chunk ck, DevOpt dopt
     const int lane = threadIdx.x;
     const unsigned int n_jobs = *fl.n_dp;
     for (;;) {
-        unsigned int t = 0;
-        if (lane == 0) t = atomicAdd(fl.q_dp, 1u);
-        t = (unsigned int)__builtin_amdgcn_readfirstlane((int)t);
+        const unsigned int t = wave_take(fl.q_dp, 1u);
         if (t >= n_jobs) break;
         const uint32_t slot = fl.dp_list[t];
         if (!dev_cig_band_job<false>(R, ck, dopt.o, fl, slot, lane) && lane == 0) rest[atomicAdd(n_rest, 1u)] = slot;
@@ -513,9 +504,7 @@ __global__ void __launch_bounds__(GB_THREADS) k_regs_wave_long(DevRef R, Chunk c
     WaveScorerLong sc{R, dopt.o, ck, lane, eh_h, eh_e, &SB, pm.jobs ? &pm : nullptr, &cur_r};
     const int n_todo = __builtin_amdgcn_readfirstlane((int)*n_slots);
     for (;;) {
-        int slot = 0;
-        if (lane == 0) slot = (int)atomicAdd(queue, 1u);
-        slot = __builtin_amdgcn_readfirstlane(slot);
+        const int slot = (int)wave_take(queue, 1u);
         if (slot >= n_todo) break;
         const int r = order ? order[slot] : slot;
         cur_r = r;

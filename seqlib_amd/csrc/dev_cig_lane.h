@@ -97,11 +97,7 @@ __device__ __forceinline__ unsigned long long lane_wave_alloc(unsigned long long
     unsigned long long incl = bytes;
     for (int d = 1; d < WAVE; d <<= 1) { const unsigned long long u = __shfl_up(incl, d, WAVE); if (lane >= d) incl += u; }
     const unsigned long long total = __shfl(incl, WAVE - 1, WAVE);
-    unsigned long long base = 0;
-    if (total) {
-        if (lane == 0) base = atomicAdd(ctr, total);
-        base = __shfl(base, 0, WAVE);
-    }
+    const unsigned long long base = total ? wave_take_u64(ctr, total) : 0ull;
     return base + incl - bytes;
 }
 
@@ -121,9 +117,7 @@ __global__ void __launch_bounds__(64) k_cig_lanes(DevRef R, Chunk ck, DevOpt dop
     uint8_t *zown = nullptr;                 // IL: the wave's block (256-byte aligned) and the words per lane it holds
     unsigned int zown_words = 0;
     for (;;) {
-        unsigned int base = 0;
-        if (lane == 0) base = atomicAdd(queue, (unsigned int)WAVE);
-        base = (unsigned int)__builtin_amdgcn_readfirstlane((int)base);
+        const unsigned int base = wave_take(queue, (unsigned int)WAVE);
         if (base >= n_jobs) break;
         const bool live = base + (unsigned int)lane < n_jobs;
         const uint32_t slot = live ? lane_list[base + lane] : 0u;
@@ -183,9 +177,7 @@ __global__ void __launch_bounds__(64) k_cig_lanes(DevRef R, Chunk ck, DevOpt dop
                 if (words > zown_words && words < std_words) words = std_words;
                 if (words > zown_words) {                             // a new block (the old one stays where it is: the arena only grows within a chunk)
                     const unsigned long long bytes = (unsigned long long)words * (WAVE * 4ull) + 255ull;
-                    unsigned long long at = 0;
-                    if (lane == 0) at = atomicAdd(ck.zused, bytes);
-                    at = rfl_u64(at);
+                    const unsigned long long at = wave_take_u64(ck.zused, bytes);
                     if (at + bytes > ck.zcap) { zown = nullptr; zown_words = 0; }
                     else { zown = ck.zarena + ((at + 255ull) & ~255ull); zown_words = words; }
                 }

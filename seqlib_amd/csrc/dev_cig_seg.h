@@ -125,10 +125,7 @@ __global__ void __launch_bounds__(GB_THREADS) k_gseg_run(DevRef R, Chunk ck, Dev
     __shared__ GbShared S;
     __shared__ unsigned int s_unit;
     for (;;) {
-        __syncthreads();
-        if (threadIdx.x == 0) s_unit = atomicAdd(&P.cnt[2], 1u);
-        __syncthreads();
-        const unsigned int u = s_unit;
+        const unsigned int u = block_take(&P.cnt[2], 1u, &s_unit);
         if (u >= n_units) break;
         const GUnit v = P.units[u];
         const GJob x = P.gjobs[v.job_t];
@@ -221,10 +218,7 @@ __global__ void __launch_bounds__(GB_THREADS) k_cig_band_block(DevRef R, Chunk c
     const unsigned int n_jobs = *fl.n_dp < n_block ? *fl.n_dp : n_block;
     if (blockIdx.x < n_block_blocks)
         for (;;) {
-            __syncthreads();
-            if (threadIdx.x == 0) s_t = atomicAdd(queue, 1u);
-            __syncthreads();
-            const unsigned int t = s_t;
+            const unsigned int t = block_take(queue, 1u, &s_t);
             if (t >= n_jobs) break;
             const uint32_t slot = fl.dp_list[t];
             CigSeg cs;
@@ -235,9 +229,7 @@ __global__ void __launch_bounds__(GB_THREADS) k_cig_band_block(DevRef R, Chunk c
     const int lane = threadIdx.x & (WAVE - 1);
     const unsigned int n_all = *fl.n_dp;
     for (;;) {
-        unsigned int t = 0;
-        if (lane == 0) t = atomicAdd(fl.q_dp, 1u);
-        t = (unsigned int)__builtin_amdgcn_readfirstlane((int)t);
+        const unsigned int t = wave_take(fl.q_dp, 1u);
         if (t >= n_all) break;
         const uint32_t slot = fl.dp_list[t];
         if (!dev_cig_band_job<false>(R, ck, dopt.o, fl, slot, lane) && lane == 0) rest[atomicAdd(n_rest, 1u)] = slot;
@@ -363,10 +355,7 @@ __global__ void __launch_bounds__(GB_THREADS) k_pseg_join(DevRef R, Chunk ck, De
     __shared__ unsigned int s_job;
     int *scratch = P.scratch + (size_t)blockIdx.x * GSEG_WIN;
     for (;;) {
-        __syncthreads();
-        if (threadIdx.x == 0) s_job = atomicAdd(&P.cnt[3], 1u);
-        __syncthreads();
-        const unsigned int t = s_job;
+        const unsigned int t = block_take(&P.cnt[3], 1u, &s_job);
         if (t >= n_jobs) break;
         const GJob x = P.gjobs[t];
         const GQ qf{ck.codes + x.q_off, x.lq, x.rev != 0};

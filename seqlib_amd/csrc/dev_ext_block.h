@@ -377,10 +377,7 @@ __global__ void __launch_bounds__(XB_THREADS) k_ext_block(DevRef R, Chunk ck, De
     else { eh_h = sh_dyn; eh_e = sh_dyn + ck.long_stride; }
     const unsigned int n_jobs = job_list ? *n_list : (*n_top < cap ? *n_top : cap);
     for (;;) {
-        __syncthreads();
-        if (threadIdx.x == 0) s_job = atomicAdd(queue, 1u);
-        __syncthreads();
-        const unsigned int k = s_job;
+        const unsigned int k = block_take(queue, 1u, &s_job);
         if (k >= n_jobs) break;
         const unsigned int job = job_list ? job_list[k] : k;
         const FirstJob j = jobs[job];

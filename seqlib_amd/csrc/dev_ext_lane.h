@@ -269,9 +269,7 @@ __global__ void __launch_bounds__(64) k_ext_lanes(DevRef R, Chunk ck, DevOpt dop
     const unsigned int nh = (unsigned int)__builtin_amdgcn_readfirstlane((int)*n_heavy);
     const unsigned int n_jobs = nh ? (unsigned int)__builtin_amdgcn_readfirstlane((int)job_off[nh]) : 0u;
     for (;;) {
-        unsigned int base = 0;
-        if (lane == 0) base = atomicAdd(queue, (unsigned int)WAVE);
-        base = (unsigned int)__builtin_amdgcn_readfirstlane((int)base);
+        const unsigned int base = wave_take(queue, (unsigned int)WAVE);
         if (base >= n_jobs) break;
         const unsigned int job = base + (unsigned int)lane;
         if (job < n_jobs) {
@@ -354,9 +352,7 @@ __global__ void __launch_bounds__(64) k_first_lanes(DevRef R, Chunk ck, DevOpt d
     row.init(lane_lds, cols, lane);
     const unsigned int n_jobs = (unsigned int)__builtin_amdgcn_readfirstlane((int)*n_list);
     for (;;) {
-        unsigned int base = 0;
-        if (lane == 0) base = atomicAdd(queue, (unsigned int)WAVE);
-        base = (unsigned int)__builtin_amdgcn_readfirstlane((int)base);
+        const unsigned int base = wave_take(queue, (unsigned int)WAVE);
         if (base >= n_jobs) break;
         const unsigned int t = base + (unsigned int)lane;
         if (t < n_jobs) {

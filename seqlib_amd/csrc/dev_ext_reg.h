@@ -426,9 +426,7 @@ __global__ void __launch_bounds__(64, EXT_MIN_WAVES) k_extend_reg(DevRef R, Chun
     const int n_todo = __builtin_amdgcn_readfirstlane((int)*n_slots);
     const int n_head = first ? __builtin_amdgcn_readfirstlane((int)*n_first) : 0;
     while (true) {
-        int slot = 0;
-        if (lane == 0) slot = (int)atomicAdd(queue, 1u);
-        slot = __builtin_amdgcn_readfirstlane(slot);
+        const int slot = (int)wave_take(queue, 1u);
         if (slot >= n_todo) break;
         const int r = first ? (slot < n_head ? first[slot] : order[slot - n_head]) : (order ? order[slot] : slot);
         const bool dbg = ck.dbg_cyc && ck.dbg_stage == 1;
@@ -951,9 +949,7 @@ __global__ void __launch_bounds__(64, EXT_JOB_WAVES) k_extend_cand(DevRef R, Chu
     const unsigned int nh = (unsigned int)__builtin_amdgcn_readfirstlane((int)*n_heavy);
     const unsigned int n_jobs = nh ? (unsigned int)__builtin_amdgcn_readfirstlane((int)job_off[nh]) : 0u;
     for (;;) {
-        unsigned int job = 0;
-        if (lane == 0) job = atomicAdd(queue, 1u);
-        job = (unsigned int)__builtin_amdgcn_readfirstlane((int)job);
+        const unsigned int job = wave_take(queue, 1u);
         if (job >= n_jobs) break;
         unsigned int lo = 0, hi = nh;                                // last slot whose first job is <= job
         while (hi - lo > 1) { const unsigned int mid = (lo + hi) >> 1; if (job_off[mid] <= job) lo = mid; else hi = mid; }
@@ -1075,10 +1071,8 @@ __global__ void __launch_bounds__(64, EXT_JOB_WAVES) k_ext_first(DevRef R, Chunk
     if (n_jobs > cap) n_jobs = cap;                  // (reads whose slots pass the table end are not prepared either)
     if (dp_list) n_jobs = (unsigned int)__builtin_amdgcn_readfirstlane((int)*n_dp);       // only the jobs k_first_diag left (dev_ext_lane.h)
     for (;;) {
-        unsigned int base = 0;
         constexpr unsigned int BATCH = MAXQ > 704 ? 1u : (unsigned int)FIRST_BATCH;          // (a contig's extension is milliseconds: one per fetch)
-        if (lane == 0) base = atomicAdd(queue, BATCH);
-        base = (unsigned int)__builtin_amdgcn_readfirstlane((int)base);
+        const unsigned int base = wave_take(queue, BATCH);
         if (base >= n_jobs) break;
         const unsigned int end = base + BATCH < n_jobs ? base + BATCH : n_jobs;
         for (unsigned int k = base; k < end; ++k) {

@@ -172,10 +172,7 @@ __global__ void __launch_bounds__(XB_THREADS) k_xseg_run(DevRef R, Chunk ck, Dev
     __shared__ XbShared S;
     __shared__ unsigned int s_unit;
     for (;;) {
-        __syncthreads();
-        if (threadIdx.x == 0) s_unit = atomicAdd(&P.cnt[2], 1u);
-        __syncthreads();
-        const unsigned int u = s_unit;
+        const unsigned int u = block_take(&P.cnt[2], 1u, &s_unit);
         if (u >= n_units) break;
         const XUnit v = P.units[u];
         const XJob x = P.xjobs[v.job_k];
@@ -198,9 +195,7 @@ __global__ void __launch_bounds__(XB_THREADS, 5) k_xseg_run_w(DevRef R, Chunk ck
     __shared__ XbShared S[XB_WAVES];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & (WAVE - 1);
     for (;;) {
-        unsigned int u = 0;
-        if (lane == 0) u = atomicAdd(&P.cnt[2], 1u);
-        u = (unsigned int)__builtin_amdgcn_readfirstlane((int)u);
+        const unsigned int u = wave_take(&P.cnt[2], 1u);
         if (u >= n_units) break;
         const XUnit v = P.units[u];
         const XJob x = P.xjobs[v.job_k];
@@ -354,10 +349,7 @@ __global__ void __launch_bounds__(XB_THREADS) k_xseg_join(DevRef R, Chunk ck, De
     else { eh_h = sh_dyn; eh_e = sh_dyn + ck.long_stride; }
     int *scratch = P.scratch + (size_t)blockIdx.x * XSEG_WIN;
     for (;;) {
-        __syncthreads();
-        if (threadIdx.x == 0) s_job = atomicAdd(&P.cnt[3], 1u);
-        __syncthreads();
-        const unsigned int k = s_job;
+        const unsigned int k = block_take(&P.cnt[3], 1u, &s_job);
         if (k >= n_jobs) break;
         const int stage = P.state[k].stage;
         if (stage == 9) continue;

@@ -424,9 +424,7 @@ __global__ void __launch_bounds__(64) k_regs_wave(DevRef R, Chunk ck, DevOpt dop
     const MatRows mr = make_matrows(dopt.o.mat);
     const int n_todo = __builtin_amdgcn_readfirstlane((int)*n_slots);
     for (;;) {
-        int slot = 0;
-        if (lane == 0) slot = (int)atomicAdd(queue, 1u);
-        slot = __builtin_amdgcn_readfirstlane(slot);
+        const int slot = (int)wave_take(queue, 1u);
         if (slot >= n_todo) break;
         const int r = order ? order[slot] : slot;
         const int nr = __builtin_amdgcn_readfirstlane(ck.n_reg[r]);
@@ -659,10 +657,7 @@ static __device__ __noinline__ void dev_cig_dp_job(const DevRef &R, const Chunk 
             const unsigned long long need = (unsigned long long)n_col * (unsigned long long)rlen;
             if (need <= ws.z_own_cap) z = ws.z_own;                  // (a wider band of the same job overwrites the narrower one's bytes)
             else {
-                unsigned long long off = 0;
-                if (lane == 0) off = atomicAdd(ck.zused, need);
-                off = ((unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(off >> 32)) << 32) |
-                      (unsigned int)__builtin_amdgcn_readfirstlane((int)(off & 0xffffffffull));
+                const unsigned long long off = wave_take_u64(ck.zused, need);
                 if (off + need > ck.zcap) { if (lane == 0) atomicOr(ck.flags, OVF_ZARENA); return; }
                 z = ck.zarena + off;
             }
@@ -688,9 +683,7 @@ static __device__ __noinline__ void dev_cig_dp_job(const DevRef &R, const Chunk 
     const unsigned long long need = (unsigned long long)n_ops + 2;
     if (ws.cig_next + need > ws.cig_end) {               // reserve ahead (what is left of the old reservation stays unused)
         const unsigned long long take = need > CIG_WAVE_WORDS ? need : (unsigned long long)CIG_WAVE_WORDS;
-        if (lane == 0) base = atomicAdd(ck.cigused, take);
-        base = ((unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(base >> 32)) << 32) |
-               (unsigned int)__builtin_amdgcn_readfirstlane((int)(base & 0xffffffffull));
+        base = wave_take_u64(ck.cigused, take);
         if (base + take > ck.cigcap) { if (lane == 0) atomicOr(ck.flags, OVF_CIGAR); return; }
         ws.cig_next = base; ws.cig_end = base + take;
     }
@@ -731,16 +724,11 @@ __global__ void __launch_bounds__(64, CIG_MIN_WAVES) k_cig_dp(DevRef R, Chunk ck
     CigWaveState ws;
     ws.z_own = nullptr; ws.z_own_cap = 0; ws.cig_next = ws.cig_end = 0;
     if (blockIdx.x < (n_jobs + CIG_BATCH - 1) / CIG_BATCH) {   // (a wave that will find the queue empty takes nothing)
-        unsigned long long off = 0;
-        if (lane == 0) off = atomicAdd(ck.zused, (unsigned long long)CIG_WAVE_Z);
-        off = ((unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(off >> 32)) << 32) |
-              (unsigned int)__builtin_amdgcn_readfirstlane((int)(off & 0xffffffffull));
+        const unsigned long long off = wave_take_u64(ck.zused, (unsigned long long)CIG_WAVE_Z);
         if (off + CIG_WAVE_Z <= ck.zcap) { ws.z_own = ck.zarena + off; ws.z_own_cap = CIG_WAVE_Z; }
     }
     for (;;) {
-        unsigned int t0 = 0;
-        if (lane == 0) t0 = atomicAdd(fl.q_dp, (unsigned int)CIG_BATCH);
-        t0 = (unsigned int)__builtin_amdgcn_readfirstlane((int)t0);
+        const unsigned int t0 = wave_take(fl.q_dp, (unsigned int)CIG_BATCH);
         if (t0 >= n_jobs) break;
         const unsigned int t1 = t0 + CIG_BATCH < n_jobs ? t0 + CIG_BATCH : n_jobs;
         for (unsigned int t = t0; t < t1; ++t) dev_cig_dp_job<MAXQ>(R, ck, dopt.o, mr, fl, fl.dp_list[t], lane, ws);
@@ -760,13 +748,7 @@ __global__ void __launch_bounds__(64) k_hits_wave(Chunk ck, const int *list, con
     const int lane = threadIdx.x;
     const int n_todo = __builtin_amdgcn_readfirstlane((int)*n_list);
     for (;;) {
-        int slot = 0;
-        int l0 = lane;
-        asm volatile("" : "+v"(l0));          // the lane number is made opaque INSIDE the loop.  With the loop-invariant `lane == 0` the compiler unswitched this loop on it: lanes 1..63
-                                              // got a copy of the loop in which slot stays 0 and readfirstlane reads lane 1 -- read 0 for ever (the round's first version of this kernel
-                                              // hung; scripts/ubench/hits_wave_test.hip reproduces it with VARIANT 2 and holds the kernel against std::stable_sort on the host)
-        if (l0 == 0) slot = (int)atomicAdd(queue, 1u);
-        slot = __builtin_amdgcn_readfirstlane(slot);
+        const int slot = (int)wave_take(queue, 1u);          // (dev_wave.h: this is the loop the compiler once unswitched on `lane == 0`)
         if (slot >= n_todo) break;
         const int r = list[slot];
         ReadWS w = make_ws(ck, r);

@@ -14,6 +14,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "dev_wave.h"
 
 struct FmlSlot { unsigned long long key, cnt; };      // key + 1 (0 = empty); cnt = occurrences | high-quality occurrences << 32
 
@@ -950,9 +951,7 @@ static __global__ void __launch_bounds__(256, FML_EC_WAVES) k_fml_ec(const FmlSl
     const FmlEcMem sc = fml_ec_mem(gsc);
     unsigned int *wW = gsc.W - lane;          // the wave's words: base i of lane j at wW[FML_L(i) + j]
     while (true) {
-        unsigned long long r0 = 0;
-        if (lane == 0) r0 = atomicAdd(next, 64ULL);
-        r0 = __shfl(r0, 0);
+        const unsigned long long r0 = wave_take_u64(next, 64ULL);
         if ((long long)r0 >= n_reads) break;
         const long long r = (long long)r0 + lane;
         const bool live = r < n_reads;

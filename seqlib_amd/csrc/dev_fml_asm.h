@@ -12,6 +12,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "dev_wave.h"
 
 #define FML_SEED_MAX 16          // bases per seed key: 3 bits each + the window tag in the top 16 bits
 
@@ -126,7 +127,8 @@ __device__ __forceinline__ bool fml_same(const unsigned char *x, const unsigned 
 // (u, v, length) triples, a wave reserving room for its lanes' finds with one atomic; cnt[u] counts them per source.
 #define FML_TRI_CHUNK 1024          // triples a wave reserves at a time: one atomic on the shared counter per chunk, not per round (12.7 M strings x 2 rounds of
                                     // same-address atomics serialise in one L2 channel at ~10 ns each: that, not the probing, was 3/4 of this kernel's time)
-static __global__ void __launch_bounds__(256) k_asm_join(const unsigned char *text, const FmlStr *strs, long long n_str, int kk, int min_match,
+// (7 waves per SIMD = the 72 VGPRs the kernel has always had; unasked, the allocator drifts to 74 and 6 waves: profiles/NOTES_wave_take.md)
+static __global__ void __launch_bounds__(256, 7) k_asm_join(const unsigned char *text, const FmlStr *strs, long long n_str, int kk, int min_match,
                                                          const unsigned long long *keys, const unsigned int *vals, const unsigned long long *hkey, const unsigned int *hval, unsigned int hmask,
                                                          int *rep, unsigned char *contained, unsigned int *cnt, FmlTriple *tri, unsigned long long tri_cap, unsigned long long *tri_n)
 {
@@ -168,10 +170,8 @@ static __global__ void __launch_bounds__(256) k_asm_join(const unsigned char *te
         if (total) {
             if ((unsigned int)total > my_left) {          // a new stretch; what is left of the old one is marked empty (u = -1: k_asm_scatter skips it)
                 for (unsigned int i = (unsigned int)lane; i < my_left; i += 64) if (my_base + i < tri_cap) tri[my_base + i] = FmlTriple{-1, 0, 0};
-                unsigned long long nb = 0;
                 const unsigned int want = total > FML_TRI_CHUNK ? (unsigned int)total : FML_TRI_CHUNK;
-                if (lane == 0) nb = atomicAdd(tri_n, (unsigned long long)want);
-                my_base = __shfl(nb, 0); my_left = want;
+                my_base = wave_take_u64(tri_n, (unsigned long long)want); my_left = want;
             }
             const unsigned long long base = my_base + (unsigned long long)(incl - mine);
             for (int j = 0; j < mine; ++j) if (base + j < tri_cap) tri[base + j] = found[j];
@@ -246,9 +246,7 @@ static __global__ void __launch_bounds__(256) k_asm_reduce(const unsigned char *
     const unsigned long long m = __ballot(keep);
     const int n_keep = __popcll(m);
     if ((unsigned int)n_keep > my_left) {
-        unsigned long long nb = 0;
-        if (lane == 0) nb = atomicAdd(out_n, (unsigned long long)FML_OUT_CHUNK);
-        my_base = __shfl(nb, 0); my_left = FML_OUT_CHUNK;
+        my_base = wave_take_u64(out_n, (unsigned long long)FML_OUT_CHUNK); my_left = FML_OUT_CHUNK;
     }
     if (lane == 0) { n_irr[u] = (unsigned int)n_keep; irr_off[u] = my_base; }
     if (keep) out[my_base + __popcll(m & ((1ULL << lane) - 1))] = FmlEdge{sv, sl};
@@ -406,9 +404,8 @@ static __global__ void __launch_bounds__(256) k_asm_huge_emit(const int *list, c
     int keep = 0;
     for (int j = lane; j < d; j += 64) keep += fl[j] == 0;
     for (int o = 32; o > 0; o >>= 1) keep += __shfl_xor(keep, o);
-    unsigned long long at = 0;
-    if (lane == 0) { at = atomicAdd(out_n, (unsigned long long)keep); n_irr[u] = (unsigned int)keep; irr_off[u] = at; }
-    at = __shfl(at, 0);
+    const unsigned long long at = wave_take_u64(out_n, (unsigned long long)keep);
+    if (lane == 0) { n_irr[u] = (unsigned int)keep; irr_off[u] = at; }
     int done = 0;
     for (int j0 = 0; j0 < d; j0 += 64) {
         const int j = j0 + lane;

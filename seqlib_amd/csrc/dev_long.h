@@ -101,9 +101,7 @@ __global__ void __launch_bounds__(64) k_flt_seeds(DevRef R, Chunk ck, DevOpt dop
     const int lane = threadIdx.x;
     const unsigned int n_todo = *n_list;
     for (;;) {
-        unsigned int t = 0;
-        if (lane == 0) t = atomicAdd(queue, 1u);
-        t = (unsigned int)__builtin_amdgcn_readfirstlane((int)t);
+        const unsigned int t = wave_take(queue, 1u);
         if (t >= n_todo) break;
         const int r = list[t];
         ReadWS w = make_ws_uniform(ck, r);

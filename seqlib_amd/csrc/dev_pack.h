@@ -19,11 +19,12 @@ typedef uint32_t qp_t;
 #define QP_KEEP_HI(x) ((x) & ~(qp_t)QP_LOW)
 
 #ifdef __HIPCC__
+#include "dev_wave.h"
 // the same word in every lane, pinned to scalar registers
 __device__ __forceinline__ qp_t qp_uniform(qp_t v)
 {
 #ifdef SLX_WIDE
-    return (qp_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32 | (qp_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    return rfl_u64(v);
 #else
     return (qp_t)__builtin_amdgcn_readfirstlane((int)v);
 #endif

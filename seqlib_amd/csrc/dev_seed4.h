@@ -297,12 +297,7 @@ __global__ void __launch_bounds__(128) k_seed2_select(DevFM<I> fm, Chunk ck, Dev
         uint32_t incl = want;
         for (int d = 1; d < 64; d <<= 1) { const uint32_t u = (uint32_t)__shfl_up((int)incl, d, 64); if ((int)(threadIdx.x & 63) >= d) incl += u; }
         const uint32_t total = (uint32_t)__shfl((int)incl, 63, 64);
-        uint32_t wbase = 0;
-        if (total) {
-            if ((threadIdx.x & 63) == 0) wbase = atomicAdd(n_items, total);
-            wbase = (uint32_t)__shfl((int)wbase, 0, 64);
-            base = wbase + incl - want;
-        }
+        if (total) base = wave_take(n_items, total) + incl - want;
     }
     if (!live || !mask) return;
     if (!whole && cnt && base + cnt <= cap_items) {
@@ -534,7 +529,7 @@ __global__ void SEED4_VGPR_ATTR __launch_bounds__(128, (sizeof(I) == 8 ? SEED4_M
             }
             if (pool_next == pool_end && res_next != res_end) { pool_next = res_next; pool_end = res_end; res_next = res_end = 0; }
             if (res_next == res_end && !exhausted) {
-                if (lane == 0) pend_base = atomicAdd(queue, (unsigned int)pool);
+                if (wave_lane() == 0) pend_base = atomicAdd(queue, (unsigned int)pool);          // (deferred wave_take: read one round later, at `pending` above, to hide the atomic's latency)
                 pending = true;
             }
             if (phase == S4_INIT) {                     // offsets requested one round ago
@@ -807,9 +802,7 @@ __global__ void __launch_bounds__(64) k_seed2_coop(DevFM<I> fm, DevRef R, Chunk 
     const int K = (fm.lut && fm.lut_k <= opt.min_seed_len) ? fm.lut_k : 0;
     const LutE<I> *lut = (const LutE<I> *)fm.lut;
     for (;;) {
-        uint32_t u = 0;
-        if (lane == 0) u = atomicAdd(queue, 1u);
-        u = (uint32_t)__builtin_amdgcn_readfirstlane((int)u);
+        const uint32_t u = wave_take(queue, 1u);
         if (u >= n_it) break;
         const uint32_t it = items[u];
         const uint32_t r = it >> 6;
