@@ -14,6 +14,9 @@
 // CRAM needs htslib's codec stack and reference access: Open() fails loudly for it.  BuildIndex() writes <file>.bai for a closed, coordinate-sorted
 // BAM: the index is built on the GPU (slx_bam_index_build, include/seqlib_amd_bam.h); false with "Failed to create index" for SAM output, an unsorted file
 // or without a GPU.
+// UseGpu() before Open() moves the BGZF side of a BAM writer to the GPU (slx_bgzf_*, include/seqlib_amd_bam.h): DEFLATE, CRC32 and framing run there, the
+// host serialises records and compresses nothing.  The member cutting is the same, the compressed bytes are the GPU encoder's.  No fallback: without a
+// GPU Open() then returns false.  Without UseGpu() the writer is what it was: zlib on the calling thread, no GPU touched.
 #pragma once
 #include <cstdio>
 #include <algorithm>
@@ -51,15 +54,32 @@ public:
 
     void SetHeader(const BamHeader &h) { hdr = h; }
     BamHeader Header() const { return hdr; }
-    bool IsOpen() const { return fop != nullptr; }
+    bool IsOpen() const { return fop != nullptr || gz != nullptr; }
+
+    // BAM only, before Open(): the BGZF members are compressed on GPU `device` (-1: the current one) instead of by zlib on the calling thread
+    bool UseGpu(int device = -1)
+    {
+        if (IsOpen()) { std::cerr << "BamWriter::UseGpu - call it before Open()" << std::endl; return false; }
+        if (output_format != "wb") { std::cerr << "BamWriter::UseGpu - only BAM output is compressed on the GPU" << std::endl; return false; }
+        use_gpu = true; gpu_device = device;
+        return true;
+    }
 
     bool Open(const std::string &f)
     {
-        if (fop) return false;                       // don't reopen
+        if (IsOpen()) return false;                  // don't reopen
         m_out = f;
         if (output_format == "wc") {
             std::cerr << "BamWriter::Open - CRAM output needs htslib; not available in the MI355X drop-in" << std::endl;
             return false;
+        }
+        if (use_gpu) {
+            if (slx_bgzf_open(f.c_str(), gpu_device, &gz) != SLX_OK) {
+                std::cerr << "BamWriter::Open - " << slx_last_error() << std::endl;
+                gz = nullptr;
+                return false;
+            }
+            return true;
         }
         fop = (f == "-") ? stdout : std::fopen(f.c_str(), "wb");
         if (!fop) return false;
@@ -73,7 +93,7 @@ public:
             std::cerr << "BamWriter::WriteHeader - No header supplied. Provide with SetWriteHeader" << std::endl;
             return false;
         }
-        if (!fop) {
+        if (!IsOpen()) {
             std::cerr << "BamWriter::WriteHeader - Output not open for writing. Open with Open()" << std::endl;
             return false;
         }
@@ -89,13 +109,14 @@ public:
             h += nm; h.push_back('\0');
             put32(h, (uint32_t)hdr.GetSequenceLength(i));
         }
+        if (gz) return gpu_ok(slx_bgzf_write(gz, h.data(), (int64_t)h.size())) && gpu_ok(slx_bgzf_flush(gz));
         if (!bgzf_write(h.data(), h.size())) return false;
         return bgzf_flush();                         // htslib starts the records in a fresh block
     }
 
     bool WriteRecord(const BamRecord &r)
     {
-        if (!fop) return false;
+        if (!IsOpen()) return false;
         const bam1_t *b = r.raw();
         if (!b) return false;
         if (output_format == "w") {
@@ -103,24 +124,37 @@ public:
             if (!format_sam(b, line)) return false;
             return std::fwrite(line.data(), 1, line.size(), fop) == line.size();
         }
-        const bam1_core_t &c = b->core;
         std::string rec;
         rec.reserve(36 + (size_t)b->l_data);
-        put32(rec, (uint32_t)(32 + b->l_data));
-        put32(rec, (uint32_t)c.tid);
-        put32(rec, (uint32_t)c.pos);
-        put32(rec, (uint32_t)reg2bin(c.pos, bam_endpos(b)) << 16 | (uint32_t)c.qual << 8 | (uint32_t)(c.l_qname & 0xff));
-        put32(rec, (uint32_t)c.flag << 16 | (uint32_t)(c.n_cigar & 0xffff));
-        put32(rec, (uint32_t)c.l_qseq);
-        put32(rec, (uint32_t)c.mtid);
-        put32(rec, (uint32_t)c.mpos);
-        put32(rec, (uint32_t)c.isize);
-        rec.append((const char *)b->data, (size_t)b->l_data);
+        put_record(b, rec);
+        if (gz) return gpu_ok(slx_bgzf_write(gz, rec.data(), (int64_t)rec.size()));
         return bgzf_write(rec.data(), rec.size());
+    }
+
+    // every record of the vector, in order.  Host path: WriteRecord one by one.  GPU path: the records serialised into one reused buffer, one slx_bgzf_write.
+    bool WriteRecords(const BamRecordPtrVector &recs)
+    {
+        if (!IsOpen()) return false;
+        if (!gz) {
+            for (const BamRecordPtr &r : recs) if (!r || !WriteRecord(*r)) return false;
+            return true;
+        }
+        many.clear();
+        for (const BamRecordPtr &r : recs) {
+            const bam1_t *b = r ? r->raw() : nullptr;
+            if (!b) return false;
+            put_record(b, many);
+        }
+        return gpu_ok(slx_bgzf_write(gz, many.data(), (int64_t)many.size()));
     }
 
     bool Close()
     {
+        if (gz) {
+            const bool ok = gpu_ok(slx_bgzf_close(gz));      // the last member, the EOF block; the handle is freed
+            gz = nullptr;
+            return ok;
+        }
         if (!fop) return false;
         bool ok = true;
         if (output_format == "wb") {
@@ -135,7 +169,7 @@ public:
 
     bool BuildIndex() const
     {
-        if (fop) { std::cerr << "Trying to index open BAM. Close first with Close()" << std::endl; return false; }
+        if (IsOpen()) { std::cerr << "Trying to index open BAM. Close first with Close()" << std::endl; return false; }
         if (m_out.empty()) { std::cerr << "Trying to make index, but no BAM specified" << std::endl; return false; }
         if (output_format != "wb" || m_out == "-" || slx_bam_index_build(m_out.c_str(), -1, nullptr) != SLX_OK) {
             std::cerr << "Failed to create index" << (output_format == "wb" && m_out != "-" ? std::string(": ") + slx_last_error() : std::string()) << std::endl;
@@ -147,7 +181,7 @@ public:
 
     friend std::ostream &operator<<(std::ostream &out, const BamWriter &b)
     {
-        if (b.fop) out << "Write format: " << (b.output_format == "w" ? "SAM" : "BAM");
+        if (b.IsOpen()) out << "Write format: " << (b.output_format == "w" ? "SAM" : "BAM");
         return out << " Write file " << b.m_out;
     }
 
@@ -201,6 +235,26 @@ public:
 
 private:
     static void put32(std::string &s, uint32_t v) { char b[4] = {(char)v, (char)(v >> 8), (char)(v >> 16), (char)(v >> 24)}; s.append(b, 4); }
+    // one BAM record (SAMv1 4.2) appended to rec: block_size, the fixed fields, the bam1_t::data image
+    static void put_record(const bam1_t *b, std::string &rec)
+    {
+        const bam1_core_t &c = b->core;
+        put32(rec, (uint32_t)(32 + b->l_data));
+        put32(rec, (uint32_t)c.tid);
+        put32(rec, (uint32_t)c.pos);
+        put32(rec, (uint32_t)reg2bin(c.pos, bam_endpos(b)) << 16 | (uint32_t)c.qual << 8 | (uint32_t)(c.l_qname & 0xff));
+        put32(rec, (uint32_t)c.flag << 16 | (uint32_t)(c.n_cigar & 0xffff));
+        put32(rec, (uint32_t)c.l_qseq);
+        put32(rec, (uint32_t)c.mtid);
+        put32(rec, (uint32_t)c.mpos);
+        put32(rec, (uint32_t)c.isize);
+        rec.append((const char *)b->data, (size_t)b->l_data);
+    }
+    static bool gpu_ok(int rc)
+    {
+        if (rc != SLX_OK) std::cerr << "BamWriter - " << slx_last_error() << std::endl;
+        return rc == SLX_OK;
+    }
     template <typename T> static T rd(const uint8_t *p) { T v; std::memcpy(&v, p, sizeof(T)); return v; }
     static int reg2bin(int64_t beg, int64_t end)     // SAMv1 5.3
     {
@@ -292,6 +346,10 @@ private:
     FILE *fop = nullptr;
     BamHeader hdr;
     mutable std::string blk;        // uncompressed bytes of the BGZF block being filled
+    bool use_gpu = false;           // UseGpu(): the BGZF side runs on the GPU
+    int gpu_device = -1;
+    slx_bgzf *gz = nullptr;         // the open GPU writer
+    std::string many;               // WriteRecords' reused buffer
 };
 
 }  // namespace SeqLib

@@ -18,6 +18,13 @@
  *   slx_bam_set_regions   BamReader::SetRegion / SetRegions (sam_itr_queryi per region)    src/BamReader.cpp:64-102, 104-137
  *   slx_bam_index_build   BamWriter::BuildIndex (sam_index_build)                          src/BamWriter.cpp
  *   slx_bai_query, slx_bai_stats, slx_bai_free   (new) the index on the host, for tests and tools
+ * and of the BGZF writer (slx_bgzf_*: DEFLATE, CRC32 and framing on the GPU; the host compresses nothing):
+ *   slx_bgzf_open         BamWriter::Open (hts_open "wb")                    SeqLib/BamWriter.h:10-136, src/BamWriter.cpp:69-89
+ *   slx_bgzf_write        BamWriter::WriteHeader / WriteRecord (sam_hdr_write, sam_write1: the bytes they hand to bgzf_write)   src/BamWriter.cpp:14-33, 103-113
+ *   slx_bgzf_write_device (new) the same for bytes that already lie in HBM, e.g. slx_bam_batch.d_stream; no reference counterpart
+ *   slx_bgzf_flush        the bgzf_flush behind sam_hdr_write: the records start in a member of their own       src/BamWriter.cpp:26
+ *   slx_bgzf_close        BamWriter::Close (sam_close: the last member and the EOF block)                       src/BamWriter.cpp:35-44
+ *   slx_bgzf_set, slx_bgzf_counter   (new) knobs and diagnostics
  *
  * The BAI index is restated from SAMv1 section 5.2; where it leaves a choice the rule is htslib's:
  *   end of a record   pos + reference length of the CIGAR (M D N = X); pos + 1 when that is 0 or the record carries 0x4
@@ -30,7 +37,7 @@
  * Not done: htslib's post-pass that merges chunks lying in one BGZF block and lifts sparse bins into their parents (the index is valid without it,
  * byte parity with `samtools index` is not claimed), and CSI.
  *
- * No CPU fallback: without a GPU slx_bam_open, slx_bam_inflate_file and slx_bam_index_build return SLX_ENODEVICE.  Not carried: CRAM, SAM text, CSI.
+ * No CPU fallback: without a GPU slx_bam_open, slx_bam_inflate_file, slx_bam_index_build and slx_bgzf_open return SLX_ENODEVICE.  Not carried: CRAM, SAM text, CSI.
  */
 #ifndef SEQLIB_AMD_BAM_H
 #define SEQLIB_AMD_BAM_H
@@ -126,6 +133,29 @@ void slx_bam_members_free(slx_bam_member *members);
 /* every member of any BGZF file through k_bgzf_inflate + k_bgzf_crc into the host buffer dst (cap bytes); no BAM parsing.  *n = inflated size (also
  * when cap is too small: SLX_EINVAL) */
 int  slx_bam_inflate_file(const char *path, int device, void *dst, uint64_t cap, uint64_t *n);
+
+/* ---- the BGZF writer.  The file is the concatenation of the writes in call order, cut into members of 0xff00 bytes from the start of the stream and from
+ * every flush (SeqLib::BamWriter's cutting), each member deflated (one dynamic-code block, or a stored one where that is not smaller), CRC-summed and
+ * framed on the GPU by k_bgzf_deflate / k_bgzf_trailer / k_bgzf_pack; one device-to-host copy of exactly the file bytes and one fwrite per batch.
+ * The bytes of the file depend only on the byte stream and the flush points: not on how the stream was split over calls, not on host or device origin,
+ * not on batch_bytes, and they are the same on every run.  Errors are sticky: after the first one every call returns it, and slx_bgzf_close returns it.
+ * A handle is not usable after slx_bgzf_close, which frees it (there is no "write to a closed writer": the handle is gone). */
+typedef struct slx_bgzf slx_bgzf;
+/* "-" = stdout; device < 0: the current device.  SLX_ENODEVICE without a GPU, and then no file is created; SLX_EIO: the file cannot be created */
+int  slx_bgzf_open(const char *path, int device, slx_bgzf **w);
+/* n host bytes; returns once they are staged in HBM (p may be reused).  Whole batches are compressed and written while later calls stage.  SLX_EINVAL: n < 0 */
+int  slx_bgzf_write(slx_bgzf *w, const void *p, int64_t n);
+/* the same for n bytes in the writer's device's HBM */
+int  slx_bgzf_write_device(slx_bgzf *w, const void *d_p, int64_t n);
+/* ends the member being filled: the next byte written starts a new one.  Nothing pending: no member */
+int  slx_bgzf_flush(slx_bgzf *w);
+/* flush, the 28-byte EOF block, close the file, free the handle.  Returns the first error of the writer's life (SLX_EIO: a failed fwrite; SLX_ENODEVICE: HIP) */
+int  slx_bgzf_close(slx_bgzf *w);
+/* "batch_bytes" (64 MiB; >= 0xff00): staged bytes that make a batch */
+int  slx_bgzf_set(slx_bgzf *w, const char *key, int64_t value);
+/* over the writer's life, of the batches handed over so far (the call waits for the one in flight): "members", "stored_members", "bytes_in", "bytes_out", and
+ * kernel times from HIP events in microseconds "us_deflate", "us_crc", "us_gather"; -1 = unknown name */
+int64_t slx_bgzf_counter(const slx_bgzf *w, const char *name);
 
 #ifdef __cplusplus
 }

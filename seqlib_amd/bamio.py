@@ -17,6 +17,8 @@ EXPORTS = [
 ]
 # the host-only BAI helpers of the same header
 BAI_EXPORTS = ["slx_bai_query", "slx_bai_stats", "slx_bai_free"]
+# the BGZF writer of the same header (checked by tests/test_bgzf_writer.py)
+BGZF_EXPORTS = ["slx_bgzf_open", "slx_bgzf_write", "slx_bgzf_write_device", "slx_bgzf_flush", "slx_bgzf_close", "slx_bgzf_set", "slx_bgzf_counter"]
 
 
 class Member(C.Structure):
@@ -68,6 +70,14 @@ def lib():
         L.slx_bai_stats.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.slx_bai_free.argtypes = [C.c_void_p]
         L.slx_bai_free.restype = None
+        L.slx_bgzf_open.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
+        L.slx_bgzf_write.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
+        L.slx_bgzf_write_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        L.slx_bgzf_flush.argtypes = [C.c_void_p]
+        L.slx_bgzf_close.argtypes = [C.c_void_p]
+        L.slx_bgzf_set.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
+        L.slx_bgzf_counter.argtypes = [C.c_void_p, C.c_char_p]
+        L.slx_bgzf_counter.restype = C.c_int64
         _READY = True
     return L
 
@@ -170,3 +180,38 @@ class Reader:
         db, do, n, m = C.c_void_p(), C.c_void_p(), C.c_int64(0), C.POINTER(C.c_int64)()
         _ffi.check(lib().slx_bam_reads_device(self.h, C.byref(self.batch), skip_flags, 1 if original_strand else 0, C.byref(db), C.byref(do), C.byref(n), C.byref(m)))
         return db.value, do.value, n.value, [m[i] for i in range(n.value)]
+
+
+class Writer:
+    """slx_bgzf handle: a BGZF file compressed on the GPU.  close() frees the handle; the object is not usable afterwards."""
+
+    def __init__(self, path, device=-1):
+        self.h = C.c_void_p()
+        _ffi.check(lib().slx_bgzf_open(str(path).encode(), device, C.byref(self.h)))
+
+    def write(self, data):
+        _ffi.check(lib().slx_bgzf_write(self.h, bytes(data), len(data)))
+
+    def write_device(self, ptr, n):
+        """n bytes at the device pointer ptr (an int, e.g. Batch.d_stream)"""
+        _ffi.check(lib().slx_bgzf_write_device(self.h, ptr, n))
+
+    def flush(self):
+        _ffi.check(lib().slx_bgzf_flush(self.h))
+
+    def set(self, key, value):
+        _ffi.check(lib().slx_bgzf_set(self.h, key.encode(), value))
+
+    def counter(self, name):
+        return int(lib().slx_bgzf_counter(self.h, name.encode()))
+
+    def close(self):
+        if self.h:
+            h, self.h = self.h, None
+            _ffi.check(lib().slx_bgzf_close(h))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
