@@ -17,6 +17,10 @@
 // one after another (the aligner's own lock): concurrent callers get correct results, not concurrent GPU work --
 // use alignSequences for throughput.
 // Limit of the GPU path, reported by an exception: reads longer than SLX_MAX_READ_LEN.
+//
+// alignToBam (new) is the file -> align -> file form: the records of alignSequences are built on the GPU from the device-resident hits (slx_rec_build,
+// include/seqlib_amd_rec.h) and handed to a UseGpu() BamWriter where they lie (BamWriter::WriteDevice); no BamRecord is made and the host copies nothing down.
+// From the same lrand48 state the file is byte for byte the one alignSequences + WriteRecords of every read's vector, in order, write through such a writer.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -43,9 +47,11 @@
 #include <sched.h>
 #endif
 #include "seqlib_amd.h"
+#include "seqlib_amd_rec.h"
 #include "SeqLib/BWAIndex.h"
 #include "SeqLib/BamRecord.h"
 #include "SeqLib/BamReader.h"
+#include "SeqLib/BamWriter.h"
 #include "SeqLib/UnalignedSequence.h"
 
 namespace SeqLib {
@@ -199,6 +205,8 @@ public:
     {
         try { Flush(); } catch (...) {}          // calls still queued by alignSequenceAsync
         for (Staging &st : stage_) { slx_host_free(st.bases); slx_host_free(st.offs); }
+        for (Staging &st : name_stage_) { slx_host_free(st.bases); slx_host_free(st.offs); }
+        if (rec_) slx_rec_free(rec_);
         if (al_) slx_aligner_free(al_);
         if (al2_) slx_aligner_free(al2_);
     }
@@ -361,6 +369,138 @@ public:
             slx_hits_free(&h);
         }
     }
+    // ---- straight to BAM (new): alignment, record construction and BGZF on the GPU ----------------------------
+    // The records alignSequences(reads, ...) would produce, written to `w` in read order without ever existing on the host: per chunk the reads and names go up
+    // from pinned staging (packed by the host threads while the chunk before is on the GPU), slx_align_batch_device leaves the hits in HBM, slx_rec_build turns them
+    // into the record stream and w.WriteDevice stages it for the GPU deflater.  Read i takes lrand48 draw i of the call, as in alignSequences.  Returns the number of
+    // records written.  Throws as alignSequences does; std::invalid_argument for a writer that is not an open BAM writer with UseGpu(), with UseBwaMemRecords(true)
+    // (XA / SA / MD are host-built) and for a multi-device aligner; std::runtime_error when a read cannot be a BAM record (a name beyond 254 bytes, more than 65 535
+    // CIGAR operations): nothing of that chunk is written and the writer stays usable.  Comments (BC:Z) are not carried.
+    size_t alignToBam(const UnalignedSequenceVector &reads, BamWriter &w, bool hardclip, double keepSecFrac, int maxSecondary) const
+    {
+        check_bam_target(w);
+        if (index_->IsEmpty() || reads.empty()) return 0;
+        Flush();
+        slx_aligner *al = handle();
+        slx_rec *rb = builder();
+        const int64_t n = (int64_t)reads.size();
+        uint64_t state;
+        {
+            std::lock_guard<std::mutex> g(rng_mutex());
+            state = slx_lrand48_peek_libc();
+            slx_lrand48_skip_libc((uint64_t)n);
+        }
+        std::lock_guard<std::mutex> batch(batch_mu_);
+        const int64_t chunk = std::max<int64_t>(1024, env_long("SEQLIB_AMD_CHUNK", 8000000));
+        const int64_t n_chunks = (n + chunk - 1) / chunk;
+        const unsigned cpus = detail::effective_cpus();
+        unsigned T = (unsigned)env_long("SEQLIB_AMD_THREADS", (long)cpus);
+        T = std::max(1u, std::min(T, 512u));
+        if (n < 8192) T = 1;
+        detail::TaskPool pool(T);
+        const int parts = (int)std::min<int64_t>(std::max<int64_t>((int64_t)T * 4, 16), std::max<int64_t>(1, std::min(n, chunk) / 2048));
+        std::vector<uint64_t> pb[2], pn[2];
+        std::shared_ptr<detail::TaskPool::Group> packed[2];
+        auto grow = [](Staging &S, size_t n_reads, uint64_t bytes) {
+            if (n_reads + 1 > S.cap_reads) {
+                slx_host_free(S.offs); S.cap_reads = 0;
+                S.offs = static_cast<uint64_t *>(slx_host_alloc((n_reads + 1) * 8));
+                if (!S.offs) throw std::bad_alloc();
+                S.cap_reads = n_reads + 1;
+            }
+            if (bytes + 64 > S.cap_bases) {
+                slx_host_free(S.bases); S.cap_bases = 0;
+                const size_t want = (size_t)(bytes + bytes / 8 + 4096);
+                S.bases = static_cast<char *>(slx_host_alloc(want));
+                if (!S.bases) throw std::bad_alloc();
+                S.cap_bases = want;
+            }
+        };
+        // chunk c into slot c & 1: sizes per part, their running sums, then the bytes (the last step is left running: the GPU call of the chunk before overlaps it)
+        auto submit_pack = [&](int64_t c) {
+            const int s = (int)(c & 1);
+            const int64_t lo = c * chunk, m = std::min(n, lo + chunk) - lo;
+            pb[s].assign((size_t)parts + 1, 0); pn[s].assign((size_t)parts + 1, 0);
+            pool.wait(pool.submit(parts, [&, s, lo, m](int t) {
+                uint64_t tb = 0, tn = 0;
+                for (int64_t i = lo + m * t / parts; i < lo + m * (t + 1) / parts; ++i) { tb += reads[(size_t)i].Seq.size(); tn += reads[(size_t)i].Name.size(); }
+                pb[s][(size_t)t + 1] = tb; pn[s][(size_t)t + 1] = tn;
+            }, true));
+            for (int t = 0; t < parts; ++t) { pb[s][(size_t)t + 1] += pb[s][(size_t)t]; pn[s][(size_t)t + 1] += pn[s][(size_t)t]; }
+            grow(stage_[s], (size_t)m, pb[s][(size_t)parts]);
+            grow(name_stage_[s], (size_t)m, pn[s][(size_t)parts]);
+            packed[s] = pool.submit(parts, [&, s, lo, m](int t) {
+                Staging &B = stage_[s], &N = name_stage_[s];
+                uint64_t ob = pb[s][(size_t)t], on = pn[s][(size_t)t];
+                const int64_t a = m * t / parts, b = m * (t + 1) / parts;
+                for (int64_t i = a; i < b; ++i) {
+                    const UnalignedSequence &us = reads[(size_t)(lo + i)];
+                    B.offs[i] = ob; N.offs[i] = on;
+                    std::memcpy(B.bases + ob, us.Seq.data(), us.Seq.size()); ob += us.Seq.size();
+                    std::memcpy(N.bases + on, us.Name.data(), us.Name.size()); on += us.Name.size();
+                }
+                if (b == m) { B.offs[m] = ob; N.offs[m] = on; }
+            }, true);
+        };
+        size_t written = 0;
+        submit_pack(0);
+        try {
+            for (int64_t c = 0; c < n_chunks; ++c) {
+                const int s = (int)(c & 1);
+                const int64_t lo = c * chunk, m = std::min(n, lo + chunk) - lo;
+                pool.wait(packed[s]); packed[s].reset();
+                void *d_bases = nullptr, *d_offs = nullptr, *d_names = nullptr, *d_name_offs = nullptr;
+                throw_rc(slx_rec_upload(rb, stage_[s].bases, stage_[s].offs, name_stage_[s].bases, name_stage_[s].offs, m, &d_bases, &d_offs, &d_names, &d_name_offs));
+                if (c + 1 < n_chunks) submit_pack(c + 1);          // (the other slot: its chunk has gone up and through)
+                slx_hits dh;
+                throw_rc(slx_align_batch_device(al, &memopt_, d_bases, d_offs, m, state, (uint64_t)lo, hardclip ? 1 : 0, keepSecFrac, maxSecondary, &dh));
+                slx_rec_batch rbat;
+                throw_rc(slx_rec_build(rb, &dh, d_bases, d_offs, d_names, d_name_offs, hardclip ? 1 : 0, &rbat));
+                if (rbat.n_bytes && !w.WriteDevice(rbat.d_stream, rbat.n_bytes)) throw std::runtime_error(std::string("BWAAligner::alignToBam: ") + slx_last_error());
+                written += (size_t)rbat.n_records;
+            }
+        } catch (...) {
+            for (auto &g : packed) if (g) { try { pool.wait(g); } catch (...) {} }
+            throw;
+        }
+        return written;
+    }
+    // The same from a BAM file: the loop of alignSequences(BamReader&) with the records built where the hits lie; the names come from the batch's records in HBM
+    // (slx_rec_build_from_bam), nothing is uploaded and nothing but the compressed file comes down.
+    size_t alignToBam(BamReader &reader, BamWriter &w, bool hardclip, double keepSecFrac, int maxSecondary, int skip_flags = 0x900, bool original_strand = false) const
+    {
+        check_bam_target(w);
+        if (index_->IsEmpty() || !reader.IsOpen()) return 0;
+        if (reader.cur_ < (size_t)reader.batch_.n_records) throw std::logic_error("BWAAligner::alignToBam(BamReader&): the reader is inside a batch that Next() began to serve");
+        Flush();
+        slx_aligner *al = handle();
+        slx_rec *rb = builder();
+        size_t written = 0;
+        for (;;) {
+            slx_bam_batch b;
+            if (!reader.fetch(b)) throw std::runtime_error(std::string("BWAAligner::alignToBam(BamReader&): ") + slx_last_error());
+            if (b.n_records == 0) break;
+            void *d_bases = nullptr, *d_offs = nullptr;
+            int64_t n = 0;
+            throw_rc(slx_bam_reads_device(reader.rd_, &b, skip_flags, original_strand ? 1 : 0, &d_bases, &d_offs, &n, nullptr));
+            if (n == 0) continue;
+            uint64_t state;
+            {
+                std::lock_guard<std::mutex> g(rng_mutex());
+                state = slx_lrand48_peek_libc();
+                slx_lrand48_skip_libc((uint64_t)n);
+            }
+            slx_hits dh;
+            throw_rc(slx_align_batch_device(al, &memopt_, d_bases, d_offs, n, state, 0, hardclip ? 1 : 0, keepSecFrac, maxSecondary, &dh));
+            slx_rec_batch rbat;
+            throw_rc(slx_rec_build_from_bam(rb, &dh, reader.rd_, &b, hardclip ? 1 : 0, &rbat));
+            if (rbat.n_bytes && !w.WriteDevice(rbat.d_stream, rbat.n_bytes)) throw std::runtime_error(std::string("BWAAligner::alignToBam(BamReader&): ") + slx_last_error());
+            written += (size_t)rbat.n_records;
+        }
+        return written;
+    }
+    // slx_rec_counter of this aligner's record builder ("records", "bytes", "us_size", "us_fill", ...); -1 before the first alignToBam
+    int64_t RecordBuilderCounter(const char *name) const { return rec_ ? slx_rec_counter(rec_, name) : -1; }
     // ---- deferred per-read calls (new): the reference's calling convention at batch speed ----------------
     // Every reference caller loops `alignSequence` over its reads (README.md:174-180, src/seqtools/seqtools.cpp:198-210).  Here one such
     // call is one GPU round trip (~1 ms: dozens of launches for one read), so a loop over 10^6 reads is slower than the CPU library.
@@ -424,6 +564,26 @@ private:
     struct Staging { char *bases = nullptr; uint64_t *offs = nullptr; size_t cap_bases = 0, cap_reads = 0; };
     mutable Staging stage_[4];                 // pinned staging of the chunked batch path (kept between calls): two slots per call in flight
     mutable std::mutex batch_mu_;              // one chunked batch at a time per aligner (they share the staging)
+    mutable Staging name_stage_[2];            // alignToBam: the names of a chunk, laid out like its bases (stage_[0], stage_[1])
+    mutable slx_rec *rec_ = nullptr;           // alignToBam's record builder, bound to al_
+    mutable std::once_flag rec_once_;
+
+    slx_rec *builder() const
+    {
+        slx_aligner *al = handle();
+        if (n_dev_ > 1) throw std::invalid_argument("BWAAligner::alignToBam: a multi-device aligner merges its hits on the host; use one device");
+        std::call_once(rec_once_, [&]() {
+            slx_rec *rb = nullptr;
+            throw_rc(slx_rec_create(al, &rb));
+            rec_ = rb;
+        });
+        return rec_;
+    }
+    void check_bam_target(const BamWriter &w) const
+    {
+        if (!w.IsGpuBam()) throw std::invalid_argument("BWAAligner::alignToBam: the writer must be an open BAM writer with UseGpu() (records are handed over in HBM)");
+        if (memopt_.flag & SLX_F_REG2SAM) throw std::invalid_argument("BWAAligner::alignToBam: UseBwaMemRecords records carry host-built XA / SA / MD tags; use alignSequences + WriteRecords");
+    }
 
     static long env_long(const char *name, long dflt)
     {

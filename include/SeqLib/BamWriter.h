@@ -148,6 +148,19 @@ public:
         return gpu_ok(slx_bgzf_write(gz, many.data(), (int64_t)many.size()));
     }
 
+    // n bytes of block_size-prefixed records that already lie in the HBM of the writer's GPU (slx_rec_build's stream, a reader's slx_bam_batch.d_stream): staged by
+    // slx_bgzf_write_device without a host copy; the caller's buffer is free again when the call returns.  Only a BAM writer opened after UseGpu() takes them:
+    // false with a message for a SAM writer, a host-zlib writer and a closed writer.
+    bool WriteDevice(const void *d, int64_t n)
+    {
+        if (output_format != "wb") { std::cerr << "BamWriter::WriteDevice - only BAM output takes records from the GPU" << std::endl; return false; }
+        if (!IsOpen()) { std::cerr << "BamWriter::WriteDevice - Output not open for writing. Open with Open()" << std::endl; return false; }
+        if (!gz) { std::cerr << "BamWriter::WriteDevice - the writer compresses on the host; call UseGpu() before Open()" << std::endl; return false; }
+        return gpu_ok(slx_bgzf_write_device(gz, d, n));
+    }
+    bool IsGpuBam() const { return gz != nullptr; }           // an open BAM writer whose BGZF side runs on the GPU
+    int64_t GpuCounter(const char *name) const { return gz ? slx_bgzf_counter(gz, name) : -1; }          // slx_bgzf_counter of the open GPU writer
+
     bool Close()
     {
         if (gz) {

@@ -1139,6 +1139,8 @@ extern "C" void slx_hits_free(slx_hits *h)
     memset(h, 0, sizeof *h);
 }
 
+int slx_aligner_device_of(const slx_aligner *al) { return !al || al->is_group ? -1 : al->device; }
+
 // ---------------------------------------------------------------- packed image for the RCCL gather
 extern "C" uint64_t slx_hits_packed_size(const slx_hits *h)
 {

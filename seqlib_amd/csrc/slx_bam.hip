@@ -458,6 +458,7 @@ struct slx_bam {
     BamHBuf h_comp, h_desc, h_err, h_out, h_rec, h_state, h_map;
     int64_t c_members_done = 0, c_repaired = 0, c_rounds = 0, c_records = 0, c_region_cand = 0, c_region_kept = 0;
     float us[5] = {0, 0, 0, 0, 0};
+    const void *map_stream = nullptr; int64_t map_reads = 0; // the batch slx_bam_reads_device last unpacked (d_bases, d_offs, d_map hold its reads), and how many
     const void *cur_stream = nullptr, *cur_rec = nullptr;  // what the current batch points to: d_out / d_rec, or d_cs / d_cr for a region batch
     // region iteration: the index, the regions in the order given, and their chunks as member spans
     bool has_bai = false;
@@ -919,7 +920,7 @@ static int bam_next_regions(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
     out->stream = rd->h_out.as<uint8_t>(); out->rec_off = rd->h_rec.as<uint64_t>();
     out->d_stream = rd->d_cs.p; out->d_rec_off = rd->d_cr.p;
     out->n_members = members; out->n_repaired_chunks = (int64_t)repaired;
-    rd->cur_stream = rd->d_cs.p; rd->cur_rec = rd->d_cr.p;
+    rd->cur_stream = rd->d_cs.p; rd->cur_rec = rd->d_cr.p; rd->map_stream = nullptr;
     return SLX_OK;
 }
 
@@ -952,7 +953,7 @@ extern "C" int slx_bam_next(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
     out->stream = rd->h_out.as<uint8_t>(); out->rec_off = rd->h_rec.as<uint64_t>();
     out->d_stream = rd->d_out.p; out->d_rec_off = rd->d_rec.p;
     out->n_members = done - a; out->n_repaired_chunks = (int64_t)repaired;
-    rd->cur_stream = rd->d_out.p; rd->cur_rec = rd->d_rec.p;
+    rd->cur_stream = rd->d_out.p; rd->cur_rec = rd->d_rec.p; rd->map_stream = nullptr;
     return SLX_OK;
 }
 
@@ -1131,6 +1132,7 @@ extern "C" int slx_bam_reads_device(slx_bam *rd, const slx_bam_batch *batch, int
     hipStream_t st = rd->st;
     const uint64_t n = (uint64_t)batch->n_records;
     typedef unsigned long long ull;
+    rd->map_stream = nullptr;
     for (BamDBuf *b : {&rd->d_keep, &rd->d_blen, &rd->d_kidx, &rd->d_boff}) BAM_CHK(b->ensure(8 * (n + 1)));
     BAM_CHK(rd->d_state.ensure(64)); BAM_CHK(rd->h_state.ensure(64));
     ull *hs = rd->h_state.as<ull>(), *ds = rd->d_state.as<ull>();
@@ -1165,8 +1167,16 @@ extern "C" int slx_bam_reads_device(slx_bam *rd, const slx_bam_batch *batch, int
     BAM_HIPCHK(slx_wait_stream(st));
     rd->us[3] = ev_us(rd->ev[5], rd->ev[6]);
     *d_bases = rd->d_bases.p; *d_offs = rd->d_offs.p; *n_reads = (int64_t)nr;
+    rd->map_stream = rd->cur_stream; rd->map_reads = (int64_t)nr;
     if (rec_of_read) *rec_of_read = rd->h_map.as<int64_t>();
     return SLX_OK;
+}
+
+bool slx_reader_device_reads(const slx_bam *rd, const void *batch_d_stream, const void **d_bases, const void **d_offs, const int64_t **d_rec_of_read, int64_t *n_reads, int *device)
+{
+    if (!rd || !rd->map_stream || rd->map_stream != batch_d_stream || rd->map_stream != rd->cur_stream) return false;
+    *d_bases = rd->d_bases.p; *d_offs = rd->d_offs.p; *d_rec_of_read = rd->d_map.as<int64_t>(); *n_reads = rd->map_reads; *device = rd->device;
+    return true;
 }
 
 // a device-resident result of slx_align_batch_device as a host result: one packed image (slx_hits_pack's layout, seqlib_amd.h) in HBM, one copy down

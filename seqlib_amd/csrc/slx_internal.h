@@ -64,3 +64,10 @@ static inline hipError_t slx_wait_stream(hipStream_t st)
 int slx_gpu_build_fm(slx_index *idx, const uint8_t *text, uint64_t n);
 // the same for texts of 2^32 - 1 symbols and more (slx_index_gpu64.hip); also taken for small texts when SLX_BUILD64 is set (test hook)
 int slx_gpu_build_fm64(slx_index *idx, const uint8_t *text, uint64_t n);
+
+// what the record builder (slx_rec.hip) needs of the other handles
+struct slx_aligner;
+struct slx_bam;
+int slx_aligner_device_of(const slx_aligner *al);          // the device of a single-device aligner; -1 for a group handle
+// the reads slx_bam_reads_device last unpacked for the batch whose d_stream is batch_d_stream: bases, offsets, record of read (all in HBM) and their number; false when there are none
+bool slx_reader_device_reads(const slx_bam *rd, const void *batch_d_stream, const void **d_bases, const void **d_offs, const int64_t **d_rec_of_read, int64_t *n_reads, int *device);
