@@ -456,7 +456,7 @@ public:
                 throw_rc(slx_align_batch_device(al, &memopt_, d_bases, d_offs, m, state, (uint64_t)lo, hardclip ? 1 : 0, keepSecFrac, maxSecondary, &dh));
                 slx_rec_batch rbat;
                 throw_rc(slx_rec_build(rb, &dh, d_bases, d_offs, d_names, d_name_offs, hardclip ? 1 : 0, &rbat));
-                if (rbat.n_bytes && !w.WriteDevice(rbat.d_stream, rbat.n_bytes)) throw std::runtime_error(std::string("BWAAligner::alignToBam: ") + slx_last_error());
+                if (rbat.n_bytes && !w.WriteDevice(rbat.d_stream, rbat.n_bytes, rbat.d_rec_off, rbat.n_records)) throw std::runtime_error(std::string("BWAAligner::alignToBam: ") + slx_last_error());
                 written += (size_t)rbat.n_records;
             }
         } catch (...) {
@@ -494,7 +494,7 @@ public:
             throw_rc(slx_align_batch_device(al, &memopt_, d_bases, d_offs, n, state, 0, hardclip ? 1 : 0, keepSecFrac, maxSecondary, &dh));
             slx_rec_batch rbat;
             throw_rc(slx_rec_build_from_bam(rb, &dh, reader.rd_, &b, hardclip ? 1 : 0, &rbat));
-            if (rbat.n_bytes && !w.WriteDevice(rbat.d_stream, rbat.n_bytes)) throw std::runtime_error(std::string("BWAAligner::alignToBam(BamReader&): ") + slx_last_error());
+            if (rbat.n_bytes && !w.WriteDevice(rbat.d_stream, rbat.n_bytes, rbat.d_rec_off, rbat.n_records)) throw std::runtime_error(std::string("BWAAligner::alignToBam(BamReader&): ") + slx_last_error());
             written += (size_t)rbat.n_records;
         }
         return written;

@@ -206,6 +206,7 @@ public:
     int32_t PositionEnd() const { return b ? (int32_t)bam_endpos(b.get()) : -1; }
     int32_t ChrID() const { return b ? b->core.tid : -1; }
     int32_t MateChrID() const { return b ? b->core.mtid : -1; }
+    int32_t MatePosition() const { return b ? (int32_t)b->core.mpos : -1; }
     int32_t MapQuality() const { return b ? b->core.qual : -1; }
     std::string Qname() const { return std::string(bam_get_qname(b)); }
     uint32_t AlignmentFlag() const { return b->core.flag; }
@@ -292,5 +293,19 @@ private:
 };
 
 typedef std::vector<BamRecord> BamRecordVector;
+
+// comparisons for std::sort over records (/root/reference/SeqLib/BamRecord.h:681-717): by (ChrID, Position) -- ChrID as signed, so unplaced records (-1) sort
+// first here, where BamWriter::SortByCoordinate puts them last as a sorted file wants -- and by the mate's.  Host only.
+namespace BamRecordSort {
+struct ByReadPosition {
+    bool operator()(const BamRecord &a, const BamRecord &b) const { return a.ChrID() != b.ChrID() ? a.ChrID() < b.ChrID() : a.Position() < b.Position(); }
+};
+struct ByReadPositionPtr {
+    bool operator()(const BamRecord *a, const BamRecord *b) const { return ByReadPosition()(*a, *b); }
+};
+struct ByMatePosition {
+    bool operator()(const BamRecord &a, const BamRecord &b) const { return a.MateChrID() != b.MateChrID() ? a.MateChrID() < b.MateChrID() : a.MatePosition() < b.MatePosition(); }
+};
+}  // namespace BamRecordSort
 
 }  // namespace SeqLib

@@ -17,6 +17,10 @@
 // UseGpu() before Open() moves the BGZF side of a BAM writer to the GPU (slx_bgzf_*, include/seqlib_amd_bam.h): DEFLATE, CRC32 and framing run there, the
 // host serialises records and compresses nothing.  The member cutting is the same, the compressed bytes are the GPU encoder's.  No fallback: without a
 // GPU Open() then returns false.  Without UseGpu() the writer is what it was: zlib on the calling thread, no GPU touched.
+// SortByCoordinate() after UseGpu() and before Open() makes the file coordinate-sorted (slx_sort_*, include/seqlib_amd_sort.h): WriteHeader() writes the header
+// with SO:coordinate, the records of WriteRecord(s) and WriteDevice go into a sorter in HBM in call order, Close() sorts them there -- tid ascending as unsigned,
+// then pos, ties in call order -- and writes them; BuildIndex() afterwards succeeds.  Everything must fit the sorter's budget in HBM (half of what is free at
+// Open()); what does not is refused by the write that passes it.  No host fallback.  Without SortByCoordinate() the writer behaves exactly as before.
 #pragma once
 #include <cstdio>
 #include <algorithm>
@@ -29,6 +33,7 @@
 #include "SeqLib/BamHeader.h"
 #include "SeqLib/BamRecord.h"
 #include "seqlib_amd_bam.h"
+#include "seqlib_amd_sort.h"
 
 namespace SeqLib {
 
@@ -65,6 +70,18 @@ public:
         return true;
     }
 
+    // after UseGpu(), before Open(): the records are coordinate-sorted in HBM at Close() (see the top of the file)
+    bool SortByCoordinate()
+    {
+        if (IsOpen()) { std::cerr << "BamWriter::SortByCoordinate - call it before Open()" << std::endl; return false; }
+        if (output_format != "wb") { std::cerr << "BamWriter::SortByCoordinate - only BAM output is sorted on the GPU" << std::endl; return false; }
+        if (!use_gpu) { std::cerr << "BamWriter::SortByCoordinate - the records are sorted on the GPU; call UseGpu() first (no host fallback)" << std::endl; return false; }
+        sort_on = true;
+        return true;
+    }
+    bool IsSorting() const { return sorter != nullptr; }      // an open writer that sorts
+    int64_t SortCounter(const char *name) const { return sorter ? slx_sort_counter(sorter, name) : -1; }          // slx_sort_counter of the open sorting writer
+
     bool Open(const std::string &f)
     {
         if (IsOpen()) return false;                  // don't reopen
@@ -79,6 +96,14 @@ public:
                 gz = nullptr;
                 return false;
             }
+            if (sort_on && slx_sort_create(gpu_device, &sorter) != SLX_OK) {
+                std::cerr << "BamWriter::Open - " << slx_last_error() << std::endl;
+                sorter = nullptr;
+                (void)slx_bgzf_close(gz); gz = nullptr;
+                std::remove(f.c_str());
+                return false;
+            }
+            sort_buf.clear(); sort_off.assign(1, 0);
             return true;
         }
         fop = (f == "-") ? stdout : std::fopen(f.c_str(), "wb");
@@ -97,7 +122,12 @@ public:
             std::cerr << "BamWriter::WriteHeader - Output not open for writing. Open with Open()" << std::endl;
             return false;
         }
-        const std::string text = hdr.AsString();
+        std::string text = hdr.AsString();
+        if (sorter) {                                // SO:coordinate by the rule of slx_sort_header
+            std::string so((size_t)slx_sort_header(text.data(), (int64_t)text.size(), nullptr, 0), '\0');
+            (void)slx_sort_header(text.data(), (int64_t)text.size(), &so[0], (int64_t)so.size());
+            text.swap(so);
+        }
         if (output_format == "w") return std::fwrite(text.data(), 1, text.size(), fop) == text.size();
         std::string h("BAM\1", 4);
         put32(h, (uint32_t)text.size());
@@ -124,6 +154,7 @@ public:
             if (!format_sam(b, line)) return false;
             return std::fwrite(line.data(), 1, line.size(), fop) == line.size();
         }
+        if (sorter) { put_record(b, sort_buf); sort_off.push_back(sort_buf.size()); return sort_buf.size() < SORT_STAGE || sort_flush(); }
         std::string rec;
         rec.reserve(36 + (size_t)b->l_data);
         put_record(b, rec);
@@ -138,6 +169,14 @@ public:
         if (!gz) {
             for (const BamRecordPtr &r : recs) if (!r || !WriteRecord(*r)) return false;
             return true;
+        }
+        if (sorter) {                                // serialised with the offsets slx_sort_add_host wants; handed over a stage at a time
+            for (const BamRecordPtr &r : recs) {
+                const bam1_t *b = r ? r->raw() : nullptr;
+                if (!b) return false;
+                put_record(b, sort_buf); sort_off.push_back(sort_buf.size());
+            }
+            return sort_buf.size() < SORT_STAGE || sort_flush();
         }
         many.clear();
         for (const BamRecordPtr &r : recs) {
@@ -156,7 +195,15 @@ public:
         if (output_format != "wb") { std::cerr << "BamWriter::WriteDevice - only BAM output takes records from the GPU" << std::endl; return false; }
         if (!IsOpen()) { std::cerr << "BamWriter::WriteDevice - Output not open for writing. Open with Open()" << std::endl; return false; }
         if (!gz) { std::cerr << "BamWriter::WriteDevice - the writer compresses on the host; call UseGpu() before Open()" << std::endl; return false; }
+        if (sorter) { std::cerr << "BamWriter::WriteDevice - a sorting writer needs the records' offsets: use WriteDevice(d, n, d_rec_off, n_records)" << std::endl; return false; }
         return gpu_ok(slx_bgzf_write_device(gz, d, n));
+    }
+    // the same with the records' n_records + 1 uint64 offsets in HBM (slx_rec_batch.d_rec_off, slx_bam_batch.d_rec_off): a sorting writer keeps the records in its
+    // sorter (slx_sort_add_device), any other GPU writer ignores the offsets and does what WriteDevice(d, n) does
+    bool WriteDevice(const void *d, int64_t n, const void *d_rec_off, int64_t n_records)
+    {
+        if (!sorter) return WriteDevice(d, n);
+        return sort_flush() && gpu_ok(slx_sort_add_device(sorter, d, n, d_rec_off, n_records));          // (what the host wrote before comes before)
     }
     bool IsGpuBam() const { return gz != nullptr; }           // an open BAM writer whose BGZF side runs on the GPU
     int64_t GpuCounter(const char *name) const { return gz ? slx_bgzf_counter(gz, name) : -1; }          // slx_bgzf_counter of the open GPU writer
@@ -164,7 +211,12 @@ public:
     bool Close()
     {
         if (gz) {
-            const bool ok = gpu_ok(slx_bgzf_close(gz));      // the last member, the EOF block; the handle is freed
+            bool ok = true;
+            if (sorter) {                                    // the sort, and the sorted stream into the writer
+                ok = sort_flush() && gpu_ok(slx_sort_finish(sorter, gz));
+                slx_sort_free(sorter); sorter = nullptr;
+            }
+            ok = gpu_ok(slx_bgzf_close(gz)) && ok;           // the last member, the EOF block; the handle is freed
             gz = nullptr;
             return ok;
         }
@@ -268,6 +320,14 @@ private:
         if (rc != SLX_OK) std::cerr << "BamWriter - " << slx_last_error() << std::endl;
         return rc == SLX_OK;
     }
+    // the records serialised so far into the sorter
+    bool sort_flush()
+    {
+        if (sort_off.size() <= 1) return true;
+        const bool ok = gpu_ok(slx_sort_add_host(sorter, sort_buf.data(), (int64_t)sort_buf.size(), sort_off.data(), (int64_t)sort_off.size() - 1));
+        sort_buf.clear(); sort_off.assign(1, 0);
+        return ok;
+    }
     template <typename T> static T rd(const uint8_t *p) { T v; std::memcpy(&v, p, sizeof(T)); return v; }
     static int reg2bin(int64_t beg, int64_t end)     // SAMv1 5.3
     {
@@ -363,6 +423,11 @@ private:
     int gpu_device = -1;
     slx_bgzf *gz = nullptr;         // the open GPU writer
     std::string many;               // WriteRecords' reused buffer
+    static constexpr size_t SORT_STAGE = (size_t)16 << 20;          // serialised bytes that make one slx_sort_add_host
+    bool sort_on = false;           // SortByCoordinate()
+    slx_sort *sorter = nullptr;     // of the open sorting writer
+    std::string sort_buf;           // records serialised for the sorter, and their offsets
+    std::vector<uint64_t> sort_off;
 };
 
 }  // namespace SeqLib

@@ -3,9 +3,10 @@
 (zlib, one process per slice of members).  The reads are windows of a reference FASTA (default tests/golden/tiny.fa) with 1 % substitutions, half of
 them reverse-complemented, stored as unmapped records -- so the same file feeds BWAAligner::alignSequences(BamReader&) with that reference's index.
 --sorted writes the coordinate-sorted variant tools/bamregion_bench.cpp takes: the same windows as mapped records (150M, 0x10 on half of them) at the
-place they were cut from, in (reference, position) order; without the option the output is what it always was.
+place they were cut from, in (reference, position) order; --shuffled writes the same mapped records in random order (SO:unsorted), the input of
+tools/bamsort_bench.cpp; without either option the output is what it always was.
 
-    python scripts/make_bench_bam.py out.bam [--records 2000000] [--ref tests/golden/tiny.fa] [--procs 8] [--seed 1] [--sorted]
+    python scripts/make_bench_bam.py out.bam [--records 2000000] [--ref tests/golden/tiny.fa] [--procs 8] [--seed 1] [--sorted | --shuffled]
 """
 import argparse
 import os
@@ -106,6 +107,7 @@ def main():
     ap.add_argument("--procs", type=int, default=8)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--sorted", action="store_true", help="mapped records in coordinate order (the input of tools/bamregion_bench.cpp)")
+    ap.add_argument("--shuffled", action="store_true", help="the mapped records of --sorted in random order (the input of tools/bamsort_bench.cpp)")
     o = ap.parse_args()
     names, seqs = [], []
     for ln in open(o.ref):
@@ -118,19 +120,21 @@ def main():
     for i, c in enumerate("ACGT"):
         lut[ord(c)] = i
     ref = lut[np.frombuffer("".join(seqs).encode(), dtype=np.uint8)]
-    text = "@HD\tVN:1.6\tSO:%s\n" % ("coordinate" if o.sorted else "unsorted") + "".join("@SQ\tSN:%s\tLN:%d\n" % (n, len(s)) for n, s in zip(names, seqs))
+    text = "@HD\tVN:1.6\tSO:%s\n" % ("coordinate" if o.sorted and not o.shuffled else "unsorted") + "".join("@SQ\tSN:%s\tLN:%d\n" % (n, len(s)) for n, s in zip(names, seqs))
     hdr = b"BAM\1" + struct.pack("<I", len(text)) + text.encode() + struct.pack("<I", len(names))
     for n, s in zip(names, seqs):
         hdr += struct.pack("<I", len(n) + 1) + n.encode() + b"\0" + struct.pack("<I", len(s))
     per = 200000                                         # records per job
     jobs = [(min(per, o.records - f), f, ref, o.seed * 100003 + f) for f in range(0, o.records, per)]
-    if o.sorted:
+    if o.sorted or o.shuffled:
         # places in the concatenated reference, in order; a window that would cross into the next sequence is pulled back to end with its own
         ends = np.cumsum([len(s) for s in seqs])
         g = np.sort(np.random.default_rng(o.seed).integers(0, len(ref) - L, size=o.records))
         tid = np.searchsorted(ends, g, side="right")
         g = np.minimum(g, ends[tid] - L)
         order = np.lexsort((g, tid))
+        if o.shuffled:
+            order = order[np.random.default_rng(o.seed + 7).permutation(len(order))]
         g, tid = g[order], tid[order]
         pos = g - (ends[tid] - np.array([len(s) for s in seqs])[tid])
         jobs = [j + (tid[j[1]:j[1] + j[0]], (g[j[1]:j[1] + j[0]], pos[j[1]:j[1] + j[0]])) for j in jobs]
