@@ -29,6 +29,10 @@ struct ReadWS {               // views into the per-seed-slot arrays for one rea
     int cap;
     __device__ __forceinline__ int s_qbeg(int s) const { return QP_HI(s_ql[s]); }
     __device__ __forceinline__ int s_len(int s) const { return QP_LO(s_ql[s]); }
+    // as the storage of dev_chain_body: the lists are written where the later kernels read them, any number of seeds and chains
+    static constexpr bool in_lds = false;
+    __device__ __forceinline__ bool full(int, int) const { return false; }
+    __device__ __forceinline__ void commit(int, int) const {}
 };
 
 __device__ __forceinline__ ReadWS make_ws(const Chunk &ck, int r);
@@ -62,7 +66,8 @@ __device__ __forceinline__ ReadWS make_ws(const Chunk &ck, int r)
 }
 
 // mem_chain_weight
-__device__ inline int dev_chain_weight(const ReadWS &w, int c)
+template <typename W>
+__device__ inline int dev_chain_weight(const W &w, int c)
 {
     int64_t end = 0;
     int wt = 0, tmp;
@@ -83,18 +88,20 @@ __device__ inline int dev_chain_weight(const ReadWS &w, int c)
     return wt < 1 << 30 ? wt : (1 << 30) - 1;
 }
 
-// mem_chain + mem_chain_flt for one read on ONE lane (the light-read path, and the fallback of the cooperative kernel)
-template <typename I>
-__device__ void dev_chain_read(const DevFM<I> &fm, const DevRef &R, const Chunk &ck, const slx_opt &opt, int r)
+// mem_chain + mem_chain_flt for one read on ONE lane, written once against the storage W of the read's lists: ReadWS (the seed-slot
+// columns in HBM, above) or LdsWS (the lane's slice of LDS, dev_chain_lds.h), which holds a bounded number of seeds and chains and writes
+// the columns the later kernels read once, at the end (commit).  false = W is full and NOTHING of this read has been written to HBM:
+// the caller runs the read again on ReadWS.
+template <typename I, typename W>
+__device__ __forceinline__ bool dev_chain_body(const DevFM<I> &fm, const DevRef &R, const Chunk &ck, const slx_opt &opt, int r, W &w)
 {
-        ReadWS w = make_ws(ck, r);
         const int len = (int)(ck.offs[r + 1] - ck.offs[r]);
         const int n_intv = (int)ck.intv_n[r];
         const qp_t *iinfo = (const qp_t *)ck.intv_info + (size_t)r * ck.cap_intv;
         const I *ix0 = (const I *)ck.intv_x0 + (size_t)r * ck.cap_intv;
         const I *ix2 = (const I *)ck.intv_x2 + (size_t)r * ck.cap_intv;
         int ns = 0, nc = 0;                      // seeds stored, chains
-        int *ord = w.ia;                         // chain handles ordered by pos: bwa's kbtree while it is a single leaf (<= 9 chains)
+        auto ord = w.ia;                         // chain handles ordered by pos: bwa's kbtree while it is a single leaf (<= 9 chains)
         KbTree kb;                               // ... and the tree itself from the 10th chain on (dev_kbtree.h), nodes in the region slots
         bool tree = false;
         // the chain touched last, in registers: a read from unique sequence has one chain that every seed is tested against, and each test
@@ -142,6 +149,7 @@ __device__ void dev_chain_read(const DevFM<I> &fm, const DevRef &R, const Chunk 
                         else {
                             const int64_t x = qbeg - l_qbeg, y = rbeg - l_rbeg;
                             if (y >= 0 && x - y <= opt.w && y - x <= opt.w && x - l_len < opt.max_chain_gap && y - l_len < opt.max_chain_gap) {
+                                if (w.full(ns, c)) return false;
                                 const int s = ns++;
                                 const qp_t ql = QP_PACK(qbeg, slen);
                                 w.s_rbeg[s] = rbeg; w.s_ql[s] = ql; w.s_next[s] = -1; if (w.s_score) w.s_score[s] = slen;
@@ -154,13 +162,16 @@ __device__ void dev_chain_read(const DevFM<I> &fm, const DevRef &R, const Chunk 
                     }
                 }
                 if (to_add) {
+                    if (w.full(ns, nc)) return false;
                     const int s = ns++, c = nc;
                     w.s_rbeg[s] = rbeg; w.s_ql[s] = QP_PACK(qbeg, slen); w.s_next[s] = -1; if (w.s_score) w.s_score[s] = slen;
                     w.c_pos[c] = rbeg; w.c_head[c] = w.c_tail[c] = s; w.c_n[c] = 1; w.c_rid[c] = rid;
                     cc = c; cc_tail = s; cc_n = 1; cc_rid = rid; cc_fql = cc_lql = QP_PACK(qbeg, slen); cc_frb = cc_lrb = rbeg;
+                    if constexpr (!W::in_lds) {      // (an LDS slice is full before the leaf is: full() above)
                     if (!tree && nc == 2 * KB_T - 1) { kb.from_array((int *)w.regs, ord, w.c_pos, nc); tree = true; }   // the leaf is full: it splits now
                     if (tree) kb.put(rbeg, c);
-                    else {
+                    }
+                    if (!tree) {
                         for (int m = nc; m > lo + 1; --m) ord[m] = ord[m - 1];
                         ord[lo + 1] = c;
                     }
@@ -168,11 +179,11 @@ __device__ void dev_chain_read(const DevFM<I> &fm, const DevRef &R, const Chunk 
                 }
             }
         }
-        if (tree) kb.traverse(ord);              // __kb_traverse: the order mem_chain_flt receives the chains in
+        if constexpr (!W::in_lds) if (tree) kb.traverse(ord);              // __kb_traverse: the order mem_chain_flt receives the chains in
         ck.frac_rep[r] = (float)ck.l_rep[r] / len;
         // ---------------- mem_chain_flt
         int n_chn = 0;
-        int *a = w.ia;                           // chains in pos order, then sorted by weight
+        auto a = w.ia;                           // chains in pos order, then sorted by weight
         for (int i = 0; i < nc; ++i) {
             const int c = a[i];
             w.c_first[c] = -1; w.c_kept[c] = 0;
@@ -182,7 +193,7 @@ __device__ void dev_chain_read(const DevFM<I> &fm, const DevRef &R, const Chunk 
         int n_out = 0;
         if (n_chn > 0) {
             ks_introsort_idx(n_chn, a, [&](int x, int y) { return w.c_w[x] > w.c_w[y]; });
-            int *kept = w.ib, n_kept = 0;        // positions in a[] of non-overlapping chains
+            auto kept = w.ib; int n_kept = 0;    // positions in a[] of non-overlapping chains
             auto cbeg = [&](int c) { return w.s_qbeg(w.c_head[c]); };
             auto cend = [&](int c) { return w.s_qbeg(w.c_tail[c]) + w.s_len(w.c_tail[c]); };
             w.c_kept[a[0]] = 3;
@@ -259,7 +270,17 @@ __device__ void dev_chain_read(const DevFM<I> &fm, const DevRef &R, const Chunk 
                 for (int s = w.c_head[c]; s >= 0; s = w.s_next[s]) w.c_w[off++] = s;
             }
         }
+        w.commit(ns, nc);
         ck.n_chain[r] = n_out;                   // kept chains, in extension order, are a[0..n_out)
+        return true;
+}
+
+// ... on the seed-slot columns in HBM (k_chain, and the fallback of the cooperative kernel)
+template <typename I>
+__device__ void dev_chain_read(const DevFM<I> &fm, const DevRef &R, const Chunk &ck, const slx_opt &opt, int r)
+{
+    ReadWS w = make_ws(ck, r);
+    dev_chain_body<I>(fm, R, ck, opt, r, w);
 }
 
 template <typename I>

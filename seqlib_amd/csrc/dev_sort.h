@@ -8,15 +8,16 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-template <typename LT>
-__device__ void ks_insertsort_idx(int *s, int *t, LT lt)
+// (P: where the handles are kept -- an int pointer, or anything that walks and indexes like one, such as a column of a lane's LDS slice)
+template <typename P, typename LT>
+__device__ void ks_insertsort_idx(P s, P t, LT lt)
 {
-    for (int *i = s + 1; i < t; ++i)
-        for (int *j = i; j > s && lt(*j, *(j - 1)); --j) { int sw = *j; *j = *(j - 1); *(j - 1) = sw; }
+    for (P i = s + 1; i < t; ++i)
+        for (P j = i; j > s && lt(*j, *(j - 1)); --j) { int sw = *j; *j = *(j - 1); *(j - 1) = sw; }
 }
 
-template <typename LT>
-__device__ void ks_combsort_idx(int n, int *a, LT lt)
+template <typename P, typename LT>
+__device__ void ks_combsort_idx(int n, P a, LT lt)
 {
     const double shrink = 1.2473309501039786540366528676643;
     int do_swap, gap = n;
@@ -26,16 +27,16 @@ __device__ void ks_combsort_idx(int n, int *a, LT lt)
             if (gap == 9 || gap == 10) gap = 11;
         }
         do_swap = 0;
-        for (int *i = a; i < a + n - gap; ++i) {
-            int *j = i + gap;
+        for (P i = a; i < a + (n - gap); ++i) {
+            P j = i + gap;
             if (lt(*j, *i)) { int tmp = *i; *i = *j; *j = tmp; do_swap = 1; }
         }
     } while (do_swap || gap > 2);
     if (gap != 1) ks_insertsort_idx(a, a + n, lt);
 }
 
-template <typename LT>
-__device__ void ks_introsort_idx(int n, int *a, LT lt)
+template <typename P, typename LT>
+__device__ void ks_introsort_idx(int n, P a, LT lt)
 {
     if (n < 1) return;
     if (n == 2) {

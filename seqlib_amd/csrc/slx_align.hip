@@ -31,6 +31,7 @@
 #include "dev_ext_seg.h"
 #include "dev_fin2.h"
 #include "dev_chain_coop.h"
+#include "dev_chain_lds.h"
 #include "dev_long.h"
 #include "dev_cig_lane.h"
 #include "dev_cig_band.h"
@@ -484,6 +485,7 @@ extern "C" int slx_aligner_set(slx_aligner *al, const char *key, int64_t value)
     else if (!strcmp(key, "cig_lanes")) al->cig_lanes = value != 0;
     else if (!strcmp(key, "first_diag")) al->first_diag = value != 0;
     else if (!strcmp(key, "first_lanes")) al->first_lanes = value != 0;
+    else if (!strcmp(key, "chain_lds")) al->chain_lds = value != 0;
     else if (!strcmp(key, "lane_narrow")) al->lane_narrow = value != 0;
     else if (!strcmp(key, "lane_pad")) al->lane_pad = (int)value;
     else if (!strcmp(key, "cand_lane_seeds")) { if (value < 1) return SLX_EINVAL; al->cand_lane_seeds = (int)value; }
@@ -578,6 +580,13 @@ extern "C" int64_t slx_aligner_counter(const slx_aligner *al, const char *key)
             if (al->is_group) for (const slx_aligner *sub : al->subs) take(sub); else take(al);
             return v;
         }
+        if (!strcmp(key, "chain_lds_bail") || !strcmp(key, "chain_lds_reads")) {          // last batch: reads k_chain_lds gave up and ran again on the HBM columns / reads it finished in LDS
+            long long v = 0;
+            const int which = key[10] == 'r';
+            auto take = [&](const slx_aligner *a) { for (const Worker *wk : a->workers) v += (long long)wk->chain_stat[which]; };
+            if (al->is_group) for (const slx_aligner *sub : al->subs) take(sub); else take(al);
+            return v;
+        }
         if (!strcmp(key, "retries")) {          // chunks run again after an overflow of their work areas (interval lists, traceback arena, CIGAR pool) since the aligner was created
             long long v = 0;
             if (al->is_group) for (const slx_aligner *sub : al->subs) v += sub->n_retries; else v = al->n_retries;
@@ -656,6 +665,7 @@ static int worker_run(slx_aligner *al, Worker *wk, const slx_opt *opt, const uin
     for (int i = 0; i < SLX_N_PROBES; ++i) wk->probe_ms[i] = 0;
     wk->n_chunks = 0;
     for (long long &c : wk->cnt) c = 0;
+    wk->chain_stat[0] = wk->chain_stat[1] = 0;
     int rc;
     const int64_t n_part = r_hi - r_lo;
     if ((rc = wk->o_hit_off.ensure(((size_t)n_part + 1) * 8)) != SLX_OK) return rc;

@@ -544,6 +544,29 @@ static void launch_tail(slx_aligner *al, Worker *wk, const Chunk &ck, const DevO
 struct CvtI32U64 { __host__ __device__ unsigned long long operator()(int v) const { return (unsigned long long)v; } };
 
 // wave-cooperative chaining of the heavy list, then (a few blocks, normally nothing to do) the reads whose chains outgrew the LDS table
+// Chaining of the reads on `order` (null: all of them), one lane per read: in LDS where the chunk allows it (dev_chain_lds.h: no per-seed
+// scores, i.e. no long reads, and not one read per wave -- a small chunk's 64 slices would serve one lane each), with k_chain behind it
+// for the reads the LDS pass leaves; else every read on k_chain.
+template <typename I>
+static void launch_chain(slx_aligner *al, Worker *wk, const Chunk &ck, const DevOpt &dopt, const DevFM<I> &fm, hipStream_t st, const int *order, unsigned int *q,
+                         const unsigned int *n_slots, int n, int grid, int bs)
+{
+#ifndef SLX_WIDE
+    if (al->chain_lds && !ck.s_score && ck.spread <= 1) {
+        const size_t slice = LdsWS<I, CHAIN_LDS_SEEDS>::bytes();
+        const int waves_cu = std::max(1, (int)((160u << 10) / slice));
+        int *left = wk->chain_left.as<int>();        // (n entries: run_chunk)
+        hipLaunchKernelGGL(k_chain_lds<I>, dim3(std::max(1, std::min(n / 64 + 1, al->n_cu * waves_cu))), dim3(64), slice, st, fm, al->ref, ck, dopt, order, q + 0, n_slots,
+                           left, q + 52, q + 50);
+        // (how many reads are left is known on the device only, so this launch has k_chain's usual grid: with nothing on the list every wave makes one fetch-add
+        // and leaves.  The list is in the order the reads were given up, not the input order the light list has: results do not depend on the order, and the reads on it are all of the long kind, so a wave's lanes still hold reads of like weight.)
+        hipLaunchKernelGGL(k_chain<I>, dim3(grid), dim3(bs), 0, st, fm, al->ref, ck, dopt, (const int *)left, q + 53, (const unsigned int *)(q + 52), 0);
+        return;
+    }
+#endif
+    hipLaunchKernelGGL(k_chain<I>, dim3(grid), dim3(bs), 0, st, fm, al->ref, ck, dopt, order, q + 0, n_slots, ck.spread > 1 ? 1 : 0);
+}
+
 template <typename I>
 static void launch_coop(slx_aligner *al, Worker *wk, const Chunk &ck, const DevOpt &dopt, const DevFM<I> &fm, hipStream_t st, unsigned int *q,
                         unsigned int *counts, int n, bool both_tables = false)
@@ -765,6 +788,7 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
         unsigned int *q = wk->queues.as<unsigned int>();
         unsigned int *counts = q + 24;          // [0] light (or all) reads, [1] heavy reads
         ENS(part_flag, (size_t)n * 4); ENS(part_pos, (size_t)n * 4); ENS(order_in, (size_t)n * 4); ENS(order_out, (size_t)n * 4);
+        if (al->chain_lds) ENS(chain_left, (size_t)n * 4);
         {   // scan_tmp must hold the scans of launch_tail / the partition below
             size_t tb = 0;
             HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, wk->part_flag.as<unsigned int>(), wk->part_pos.as<unsigned int>(), n + 1, st));
@@ -788,12 +812,12 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
                 HIPCHK(hipcub::DeviceScan::ExclusiveSum(wk->scan_tmp.p, tb, wk->part_flag.as<unsigned int>(), wk->part_pos.as<unsigned int>(), n, st));
                 hipLaunchKernelGGL(k_part_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, wk->part_flag.as<unsigned int>(),
                                    wk->part_pos.as<unsigned int>(), n, wk->order_in.as<int>(), wk->order_out.as<int>(), counts);
-                hipLaunchKernelGGL(k_chain<I>, dim3(spread > 1 ? seed_grid : grid), dim3(bs), 0, st, fm, al->ref, ck, dopt, wk->order_in.as<int>(), q + 0, counts, spread > 1 ? 1 : 0);
+                launch_chain<I>(al, wk, ck, dopt, fm, st, wk->order_in.as<int>(), q, counts, n, spread > 1 ? seed_grid : grid, bs);
                 launch_coop<I>(al, wk, ck, dopt, fm, st, q, counts, n, max_len > 704);
                 hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(1), 0, st, counts, (unsigned int)n);      // the stages below take every read in input order
             } else {
             hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(1), 0, st, counts, (unsigned int)n);
-            hipLaunchKernelGGL(k_chain<I>, dim3(spread > 1 ? seed_grid : grid), dim3(bs), 0, st, fm, al->ref, ck, dopt, (const int *)nullptr, q + 0, counts, spread > 1 ? 1 : 0);
+            launch_chain<I>(al, wk, ck, dopt, fm, st, (const int *)nullptr, q, counts, n, spread > 1 ? seed_grid : grid, bs);
             }
             if (has_long) {   // mem_flt_chained_seeds
                 hipLaunchKernelGGL(k_long_list, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ck, dopt, wk->long_list.as<int>(), q + 16);
@@ -882,7 +906,7 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
                                    wk->order_bin.as<int>());
                 light = wk->order_bin.as<int>();
             } else (void)hipGetLastError();
-            hipLaunchKernelGGL(k_chain<I>, dim3(grid), dim3(bs), 0, st, fm, al->ref, ck, dopt, light, q + 0, counts, 0);
+            launch_chain<I>(al, wk, ck, dopt, fm, st, light, q, counts, n, grid, bs);
             launch_coop<I>(al, wk, ck, dopt, fm, st, q, counts, n);
             (void)hipEventRecord(wk->ev_probe[2], st);
             if (use_cand) {
@@ -1023,7 +1047,8 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
         ms.src[2] = (const unsigned int *)ck.flags; ms.words[2] = 1;
         ms.src[3] = wk->queues.as<unsigned int>() + 46; ms.words[3] = 1;          // reads k_regs deferred to the wave kernel
         ms.src[4] = wk->queues.as<unsigned int>() + 48; ms.words[4] = 1;          // reads k_hits left to k_hits_wave
-        ms.n = 5;
+        ms.src[5] = wk->queues.as<unsigned int>() + 50; ms.words[5] = 2;          // reads k_chain_lds started over on the HBM columns, reads it finished in LDS
+        ms.n = 6;
         hipLaunchKernelGGL(k_mail, dim3(1), dim3(64), 0, st, ms, wk->h_mail);
     }
     HIPCHK(slx_wait_stream(st));
@@ -1031,6 +1056,7 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
     const uint32_t fl = wk->h_mail[4];
     wk->fin_stat[0] += wk->h_mail[5]; wk->fin_stat[1] += wk->h_mail[6];
     if (fl) { *flags_out = fl; return SLX_OK; }
+    wk->chain_stat[0] += wk->h_mail[7]; wk->chain_stat[1] += wk->h_mail[8];
     // grow the outputs and compact
     const size_t H = (size_t)*hit_base + Hc, C = (size_t)*cig_base + Cc;
 #define GROW(buf, bytes, keep) if ((rc = wk->buf.grow((size_t)(bytes), (size_t)(keep), st)) != SLX_OK) return rc
