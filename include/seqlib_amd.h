@@ -151,6 +151,12 @@ void slx_aligner_free(slx_aligner *al);
  *   "cig_lane_il" 0|1 (1)     k_cig_lanes keeps the traceback bytes of a wave's 64 jobs lane-interleaved in one block of the arena (0: a row-major stretch per job)
  *   "regs_sorted", "chain_sorted" 0|1 (0)   experiments kept for their A/B (profiles/r06_knob_ab.txt): reads binned by size before the lane-per-read kernels -- slower
  *   "keep_stages" 1           test hook: keep what slx_debug_stage reads
+ *   "z_start", "cig_start"    test hooks (0 = off): bytes of the traceback arena / words of the CIGAR pool the first attempt of every chunk runs with, in place of the
+ *                             budgets (no per-read term, no floor, no padding), so that a small batch takes the overflow-and-retry path: the chunk doubles what
+ *                             overflowed and runs again, at most 12 times (then SLX_ENOMEM), and the aligner remembers what the batch needed.  A knob left at 0 while
+ *                             the other is set keeps its pool's budget; setting either forgets what the hook learnt.  While the hook is on, 1 MiB behind each pool is
+ *                             filled with a pattern before every attempt and compared after it: slx_aligner_counter "guard_dirty" = bytes found changed since the
+ *                             aligner was created (a kernel that lets a job write past its cap), "ovf_sites" = which checks raised the overflow (OVS_* bits, dev_types.h)
  * Returns SLX_EINVAL for an unknown key or a value out of range. */
 int  slx_aligner_set(slx_aligner *al, const char *key, int64_t value);
 

@@ -325,7 +325,7 @@ static __device__ __noinline__ bool dev_cig_band_job(const DevRef &R, const Chun
                 __syncthreads();
                 off = SB->off;
             } else off = wave_take_u64(ck.zused, need);
-            if (off + need > ck.zcap) { if (lane == 0 && wave0) atomicOr(ck.flags, OVF_ZARENA); return true; }
+            if (off + need > ck.zcap) { if (lane == 0 && wave0) atomicOr(ck.flags, OVF_ZARENA | (BLOCK ? OVS_Z_BAND_BLOCK : OVS_Z_BAND)); return true; }
             z = ck.zarena + off;
             const int cols = 2 * ww + 1;
             if constexpr (BLOCK) {
@@ -357,7 +357,7 @@ static __device__ __noinline__ bool dev_cig_band_job(const DevRef &R, const Chun
     n_ops = __builtin_amdgcn_readfirstlane(n_ops);
     const unsigned long long need = (unsigned long long)n_ops + 2;
     const unsigned long long base = wave_take_u64(ck.cigused, need);
-    if (base + need > ck.cigcap) { if (lane == 0) atomicOr(ck.flags, OVF_CIGAR); return true; }
+    if (base + need > ck.cigcap) { if (lane == 0) atomicOr(ck.flags, OVF_CIGAR | OVS_C_BAND); return true; }
     uint32_t *cg = ck.cigpool + base + 1;
     if (valid) {
         int wp = n_ops;

@@ -187,7 +187,7 @@ __global__ void __launch_bounds__(64) k_cig_lanes(DevRef R, Chunk ck, DevOpt dop
                 z_ok = off + need <= ck.zcap;
             }
             if (going) {
-                if (!z_ok) { atomicOr(ck.flags, OVF_ZARENA); going = false; failed = true; }
+                if (!z_ok) { atomicOr(ck.flags, OVF_ZARENA | OVS_Z_LANE); going = false; failed = true; }
                 else {
                     z = IL ? zown + 4 * lane : ck.zarena + off;
                     n_col = z_stride;
@@ -213,7 +213,7 @@ __global__ void __launch_bounds__(64) k_cig_lanes(DevRef R, Chunk ck, DevOpt dop
         const unsigned long long cneed = emit ? (unsigned long long)n_ops + 2 : 0ull;
         const unsigned long long cbase = lane_wave_alloc(ck.cigused, cneed, lane);
         if (!emit) continue;
-        if (cbase + cneed > ck.cigcap) { atomicOr(ck.flags, OVF_CIGAR); continue; }
+        if (cbase + cneed > ck.cigcap) { atomicOr(ck.flags, OVF_CIGAR | OVS_C_LANE); continue; }
         uint32_t *cg = ck.cigpool + cbase + 1;
         if (valid) {
             if (ops_in_lds) for (int k = 0; k < n_ops; ++k) cg[k] = row[(n_ops - 1 - k) * WAVE];

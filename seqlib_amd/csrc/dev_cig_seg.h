@@ -84,7 +84,7 @@ __global__ void k_gseg_plan(DevRef R, Chunk ck, DevOpt dopt, FinLists fl, unsign
     if (x.n_seg >= 2) {
         const unsigned long long need = (unsigned long long)g.n_col * (unsigned long long)g.rlen;
         const unsigned long long off = atomicAdd(ck.zused, need);
-        if (off + need > ck.zcap) { atomicOr(ck.flags, OVF_ZARENA); x.n_seg = 0; }          // (the chunk is run again with a larger arena)
+        if (off + need > ck.zcap) { atomicOr(ck.flags, OVF_ZARENA | OVS_Z_SEG); x.n_seg = 0; }          // (the chunk is run again with a larger arena)
         else {
             x.z_off = off;
             x.seg_base = (int)atomicAdd(&P.cnt[0], (unsigned int)x.n_seg);

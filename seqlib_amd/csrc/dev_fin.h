@@ -127,7 +127,7 @@ __device__ GenCig dev_gen_cigar2(const DevRef &R, const slx_opt &o, const Chunk 
         if (want_z) {
             const unsigned long long need = (unsigned long long)g.n_col * (unsigned long long)rlen;
             const unsigned long long off = atomicAdd(ck.zused, need);
-            if (off + need > ck.zcap) { atomicOr(ck.flags, OVF_ZARENA); g.valid = false; return g; }
+            if (off + need > ck.zcap) { atomicOr(ck.flags, OVF_ZARENA | OVS_Z_GEN); g.valid = false; return g; }
             g.z = ck.zarena + off;
         }
         g.score = dev_ksw_global2(l_query, qf, rlen, tf, o, w, g.z, g.n_col, eh_h, eh_e);

@@ -506,7 +506,7 @@ __global__ void __launch_bounds__(256) k_cig_fast(DevRef R, Chunk ck, FinLists f
         }
         h.nm = nm;
         const unsigned long long base = wave_fetch_add_u64(ck.cigused, 3ull);
-        if (base + 3 > ck.cigcap) { atomicOr(ck.flags, OVF_CIGAR); continue; }
+        if (base + 3 > ck.cigcap) { atomicOr(ck.flags, OVF_CIGAR | OVS_C_FAST); continue; }
         ck.cigpool[base + 1] = (uint32_t)lq << 4;
         dev_finish_hit(R, ck, j, l_query, h, (int64_t)base + 1, 1);
         ck.hits[slot] = h;
@@ -567,7 +567,7 @@ __global__ void __launch_bounds__(256) k_cig_fast_coop(DevRef R, Chunk ck, FinLi
         DHit h = ck.hits[slot];
         h.nm = s_nm[wv][lane];
         const unsigned long long cbase = wave_fetch_add_u64(ck.cigused, 3ull);
-        if (cbase + 3 > ck.cigcap) { atomicOr(ck.flags, OVF_CIGAR); continue; }
+        if (cbase + 3 > ck.cigcap) { atomicOr(ck.flags, OVF_CIGAR | OVS_C_FAST_COOP); continue; }
         ck.cigpool[cbase + 1] = (uint32_t)lq << 4;
         dev_finish_hit(R, ck, j, l_query, h, (int64_t)cbase + 1, 1);
         ck.hits[slot] = h;
@@ -658,7 +658,7 @@ static __device__ __noinline__ void dev_cig_dp_job(const DevRef &R, const Chunk 
             if (need <= ws.z_own_cap) z = ws.z_own;                  // (a wider band of the same job overwrites the narrower one's bytes)
             else {
                 const unsigned long long off = wave_take_u64(ck.zused, need);
-                if (off + need > ck.zcap) { if (lane == 0) atomicOr(ck.flags, OVF_ZARENA); return; }
+                if (off + need > ck.zcap) { if (lane == 0) atomicOr(ck.flags, OVF_ZARENA | OVS_Z_DP); return; }
                 z = ck.zarena + off;
             }
             if (2 * ww + 1 <= WAVE && lq <= (MAXQ + 2 + WAVE - 1) / WAVE * WAVE)
@@ -684,7 +684,7 @@ static __device__ __noinline__ void dev_cig_dp_job(const DevRef &R, const Chunk 
     if (ws.cig_next + need > ws.cig_end) {               // reserve ahead (what is left of the old reservation stays unused)
         const unsigned long long take = need > CIG_WAVE_WORDS ? need : (unsigned long long)CIG_WAVE_WORDS;
         base = wave_take_u64(ck.cigused, take);
-        if (base + take > ck.cigcap) { if (lane == 0) atomicOr(ck.flags, OVF_CIGAR); return; }
+        if (base + take > ck.cigcap) { if (lane == 0) atomicOr(ck.flags, OVF_CIGAR | OVS_C_DP); return; }
         ws.cig_next = base; ws.cig_end = base + take;
     }
     base = ws.cig_next; ws.cig_next += need;
@@ -726,6 +726,7 @@ __global__ void __launch_bounds__(64, CIG_MIN_WAVES) k_cig_dp(DevRef R, Chunk ck
     if (blockIdx.x < (n_jobs + CIG_BATCH - 1) / CIG_BATCH) {   // (a wave that will find the queue empty takes nothing)
         const unsigned long long off = wave_take_u64(ck.zused, (unsigned long long)CIG_WAVE_Z);
         if (off + CIG_WAVE_Z <= ck.zcap) { ws.z_own = ck.zarena + off; ws.z_own_cap = CIG_WAVE_Z; }
+        else if (lane == 0) atomicOr(ck.flags + 1, OVS_Z_DP_WAVE);          // (no OVF_* bit, and not in the flag word: see dev_types.h)
     }
     for (;;) {
         const unsigned int t0 = wave_take(fl.q_dp, (unsigned int)CIG_BATCH);

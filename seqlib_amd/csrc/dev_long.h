@@ -160,7 +160,7 @@ __global__ void __launch_bounds__(128) k_cig_long(DevRef R, Chunk ck, DevOpt dop
         }
         const unsigned long long need = (unsigned long long)n_ops + 2;
         const unsigned long long base = atomicAdd(ck.cigused, need);
-        if (base + need > ck.cigcap) { atomicOr(ck.flags, OVF_CIGAR); continue; }
+        if (base + need > ck.cigcap) { atomicOr(ck.flags, OVF_CIGAR | OVS_C_LONG); continue; }
         uint32_t *cg = ck.cigpool + base + 1;
         if (g.valid) {
             if (g.fast) cg[0] = (uint32_t)g.qlen << 4;

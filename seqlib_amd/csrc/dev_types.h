@@ -16,6 +16,25 @@ enum : uint32_t {
     ERR_LOGLUT = 1u << 4,    // log() argument outside the host-built table
     ERR_INTERNAL = 1u << 5,
 };
+// Which check raised OVF_ZARENA / OVF_CIGAR: every site ORs its own bit (8..23) into the flag word in the same atomic as the OVF_* bit, so the host can
+// tell a test which of the overflow paths a batch took (slx_aligner_counter "ovf_sites").  The host decides on the low bits alone.
+enum : uint32_t {
+    OVS_Z_GEN = 1u << 8,         // dev_gen_cigar2 (dev_fin.h), the lane-per-job alignments of k_cig_long
+    OVS_Z_BAND = 1u << 9,        // dev_cig_band_job (dev_cig_band.h), one wave per job
+    OVS_Z_BAND_BLOCK = 1u << 10, // ... and its four-wave block form (k_cig_band_block)
+    OVS_Z_SEG = 1u << 11,        // k_gseg_plan (dev_cig_seg.h): the stretch of a job cut into segments
+    OVS_Z_LANE = 1u << 12,       // k_cig_lanes (dev_cig_lane.h): the wave's lane-interleaved block, or its row-major stretches
+    OVS_Z_DP = 1u << 13,         // dev_cig_dp_job (dev_fin2.h): a job larger than the wave's own stretch
+    OVS_Z_DP_WAVE = 1u << 14,    // k_cig_dp (dev_fin2.h): a wave got no stretch of its own.  Raises no OVF_* bit and goes to the word BEHIND the flags
+                                 // (ck.flags[1], which no flag test reads): the wave's jobs then take from the shared arena, and those takes report
+    OVS_C_BAND = 1u << 15,       // dev_cig_band_job, both forms (wave 0 writes the record)
+    OVS_C_LANE = 1u << 16,       // k_cig_lanes
+    OVS_C_LONG = 1u << 17,       // k_cig_long (dev_long.h)
+    OVS_C_FAST = 1u << 18,       // k_cig_fast (dev_fin2.h)
+    OVS_C_FAST_COOP = 1u << 19,  // k_cig_fast_coop
+    OVS_C_DP = 1u << 20,         // dev_cig_dp_job: the words a wave reserves ahead
+    OVS_MASK = 0xffffu << 8,
+};
 
 struct DevRef {               // packed reference + contig table (bntseq_t)
     const uint8_t *pac;       // forward strand, 2 bit/base

@@ -531,6 +531,11 @@ extern "C" int slx_aligner_set(slx_aligner *al, const char *key, int64_t value)
     }
     else if (!strcmp(key, "threads")) { if (value < 64) return SLX_EINVAL; al->max_threads = (int)value; }
     else if (!strcmp(key, "zarena_bytes")) { if (value < 1024) return SLX_EINVAL; al->zcap = (unsigned long long)value; }
+    else if (!strcmp(key, "z_start") || !strcmp(key, "cig_start")) {   // test hooks: the caps of a chunk's first attempt (worker_run); setting either forgets what the hook learnt
+        if (value < 0 || value > (1ll << 32)) return SLX_EINVAL;
+        (key[0] == 'z' ? al->z_start : al->cig_start) = (unsigned long long)value;
+        al->z_hook = al->cig_hook = 0;
+    }
     else { slx_set_error("slx_aligner_set: unknown key %s", key); return SLX_EINVAL; }
     return SLX_OK;
 }
@@ -592,6 +597,16 @@ extern "C" int64_t slx_aligner_counter(const slx_aligner *al, const char *key)
             if (al->is_group) for (const slx_aligner *sub : al->subs) v += sub->n_retries; else v = al->n_retries;
             return v;
         }
+        if (!strcmp(key, "ovf_sites")) {        // OVS_* bits (dev_types.h) of the chunks that overflowed since the aligner was created: which checks raised OVF_ZARENA / OVF_CIGAR
+            long long v = 0;
+            if (al->is_group) for (const slx_aligner *sub : al->subs) v |= (long long)sub->ovf_sites; else v = (long long)al->ovf_sites;
+            return v;
+        }
+        if (!strcmp(key, "guard_dirty")) {      // test hooks "z_start" / "cig_start": bytes found changed behind the traceback arena and the CIGAR pool since the aligner was created
+            long long v = 0;
+            if (al->is_group) for (const slx_aligner *sub : al->subs) v += sub->guard_dirty; else v = al->guard_dirty;
+            return v;
+        }
         if (!strcmp(key, "regs_deferred") || !strcmp(key, "hits_wave_reads")) {          // reads k_regs handed to the wave kernel / reads k_hits_wave sorted, since the aligner was created
             long long v = 0;
             const int which = key[0] == 'h';
@@ -645,6 +660,45 @@ __global__ void k_shift_offsets(int64_t *dst, const int64_t *src, int64_t n, int
     if (i < n) dst[i] = src[i] + add;
 }
 
+// Test hooks "z_start" / "cig_start": the two pools get SLX_GUARD_BYTES more than the cap the kernels are told, filled with a byte pattern before every
+// attempt and compared after it -- a check that lets a job write past the cap changes bytes the process owns instead of faulting.
+#define SLX_GUARD_BYTES (1u << 20)
+#define SLX_GUARD_FILL 0xa5
+__global__ void k_guard_count(const uint8_t *z_tail, const uint8_t *cig_tail, unsigned long long *dirty)
+{
+    const size_t at = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 8;
+    if (at >= SLX_GUARD_BYTES) return;
+    unsigned int d = 0;
+    for (int k = 0; k < 8; ++k) d += (z_tail[at + k] != SLX_GUARD_FILL) + (cig_tail[at + k] != SLX_GUARD_FILL);
+    if (d) atomicAdd(dirty, (unsigned long long)d);
+}
+
+static int guard_arm(Worker *wk, const ChunkCaps &caps)
+{
+    int rc;
+    if ((rc = wk->zarena.ensure((size_t)caps.zcap + SLX_GUARD_BYTES)) != SLX_OK) return rc;
+    if ((rc = wk->cigpool.ensure((size_t)caps.cigcap * 4 + SLX_GUARD_BYTES)) != SLX_OK) return rc;
+    if ((rc = wk->guard_cnt.ensure(8)) != SLX_OK) return rc;
+    HIPCHK(hipMemsetAsync(wk->zarena.as<uint8_t>() + caps.zcap, SLX_GUARD_FILL, SLX_GUARD_BYTES, wk->stream));
+    HIPCHK(hipMemsetAsync(wk->cigpool.as<uint8_t>() + caps.cigcap * 4, SLX_GUARD_FILL, SLX_GUARD_BYTES, wk->stream));
+    return SLX_OK;
+}
+
+// after an attempt (its last kernel has ended): the site bits that raise no flag, and under the hook the changed bytes of the two tails
+static int attempt_report(Worker *wk, const ChunkCaps &caps, bool hook, uint32_t *quiet, unsigned long long *dirty)
+{
+    *quiet = 0; *dirty = 0;
+    if (hook) {
+        HIPCHK(hipMemsetAsync(wk->guard_cnt.p, 0, 8, wk->stream));
+        hipLaunchKernelGGL(k_guard_count, dim3(SLX_GUARD_BYTES / 8 / 256), dim3(256), 0, wk->stream, (const uint8_t *)wk->zarena.as<uint8_t>() + caps.zcap,
+                           (const uint8_t *)wk->cigpool.as<uint8_t>() + caps.cigcap * 4, wk->guard_cnt.as<unsigned long long>());
+        HIPCHK(hipMemcpyAsync(dirty, wk->guard_cnt.p, 8, hipMemcpyDeviceToHost, wk->stream));
+    }
+    HIPCHK(hipMemcpyAsync(quiet, wk->counters.as<uint32_t>() + 5, 4, hipMemcpyDeviceToHost, wk->stream));          // (the word behind ck.flags: run_chunk)
+    HIPCHK(slx_wait_stream(wk->stream));
+    return SLX_OK;
+}
+
 // one worker pushes reads [r_lo, r_hi) through the pipeline (in chunks), leaving its SoA result in wk->o_*
 template <typename I>
 static int worker_run(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint8_t *d_bases, const uint64_t *d_offs, int64_t r_lo, int64_t r_hi,
@@ -689,6 +743,7 @@ static int worker_run(slx_aligner *al, Worker *wk, const slx_opt *opt, const uin
         }
         uint64_t pair[2] = {stat[2], stat[3]};
         ChunkCaps caps;
+        bool hook = false;          // test hooks "z_start" / "cig_start"
         {
             std::lock_guard<std::mutex> g(al->mu);
             caps.cap_intv = al->cap_intv;
@@ -698,6 +753,7 @@ static int worker_run(slx_aligner *al, Worker *wk, const slx_opt *opt, const uin
                 caps.zcap = std::max(caps.zcap, std::min<unsigned long long>((unsigned long long)n * (unsigned long long)max_len * 208ull, 4ull << 30));
             }
             caps.cigcap = std::max<unsigned long long>(al->cig_floor, (unsigned long long)n * al->cig_per_read + 4096);
+            hook = al->z_start != 0 || al->cig_start != 0;
         }
         // on top of the per-read budgets: the stretches the waves of k_cig_dp take for themselves and the CIGAR words they reserve ahead
         // ... and the blocks of k_cig_lanes<true>: every wave that takes jobs keeps ONE lane-interleaved block sized for the largest job the routing can send it
@@ -708,9 +764,17 @@ static int worker_run(slx_aligner *al, Worker *wk, const slx_opt *opt, const uin
                                            (al->cig_lane_il ? lane_blocks * ((unsigned long long)LANE_IL_WORDS(max_len) * 256ull + 255ull) : 0ull);
         const unsigned long long cig_waves = (unsigned long long)std::min(n, al->n_cu * 32) * CIG_WAVE_WORDS;
         caps.zcap += z_waves; caps.cigcap += cig_waves;
+        if (hook) {   // the first attempt runs with exactly the caps asked for -- no per-read term, no long-read floor, none of the terms above -- or with what an overflow
+                      // under the hook taught; a knob left at 0 keeps its pool's budget.  What the hook learns stays apart from the budgets (z_hook, cig_hook)
+            std::lock_guard<std::mutex> g(al->mu);
+            if (al->z_start) caps.zcap = al->z_start;
+            if (al->cig_start) caps.cigcap = al->cig_start;
+            caps.zcap = std::max(caps.zcap, al->z_hook); caps.cigcap = std::max(caps.cigcap, al->cig_hook);
+        }
         for (int attempt = 0;; ++attempt) {
             uint32_t fl = 0;
             int64_t hb = hit_base, cb = cig_base;
+            if (hook && (rc = guard_arm(wk, caps)) != SLX_OK) return rc;
             // hit offsets of this worker are relative to its own first read / first hit
             if (max_len > SLX_NARROW_MAX_LEN)           // the same pipeline with 64-bit packed query positions (slx_align_wide.hip)
                 rc = sizeof(I) == 8 ? slx_run_chunk_wide_u64(al, wk, opt, d_bases, d_offs, pair, r0, r_lo, n, max_len, rng_state, first_ordinal, hardclip, keepSecFrac, maxSecondary,
@@ -721,6 +785,14 @@ static int worker_run(slx_aligner *al, Worker *wk, const slx_opt *opt, const uin
             rc = run_chunk<I>(al, wk, opt, d_bases, d_offs, pair, r0, r_lo, n, max_len, rng_state, first_ordinal, hardclip, keepSecFrac, maxSecondary,
                               caps, &hb, &cb, &fl);
             if (rc != SLX_OK) return rc;
+            if (hook || fl) {
+                uint32_t quiet = 0;
+                unsigned long long dirty = 0;
+                if ((rc = attempt_report(wk, caps, hook, &quiet, &dirty)) != SLX_OK) return rc;
+                std::lock_guard<std::mutex> g(al->mu);
+                al->ovf_sites |= (fl & OVS_MASK) | quiet;
+                al->guard_dirty += (long long)dirty;
+            }
             if (!fl) {
                 hit_base = hb; cig_base = cb;
                 ++wk->n_chunks;
@@ -729,7 +801,8 @@ static int worker_run(slx_aligner *al, Worker *wk, const slx_opt *opt, const uin
                 else al->cap_intv = std::max(al->cap_intv, caps.cap_intv);
                 if (attempt > 0) {   // only what an overflow taught -- per read from a large chunk, as a floor from a small one (a batch
                                      // of a few long reads says nothing about the bytes per read of the next 50 M-read batch)
-                    if (n >= 65536) {
+                    if (hook) { al->z_hook = std::max(al->z_hook, caps.zcap); al->cig_hook = std::max(al->cig_hook, caps.cigcap); }
+                    else if (n >= 65536) {
                         al->z_per_read = std::max<unsigned long long>(al->z_per_read, (caps.zcap - z_waves + n - 1) / (unsigned long long)n);
                         al->cig_per_read = std::max<unsigned long long>(al->cig_per_read, (caps.cigcap - cig_waves + n - 1) / (unsigned long long)n);
                     } else {

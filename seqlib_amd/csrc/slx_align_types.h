@@ -82,6 +82,7 @@ struct Worker {
     DevBuf n_chain, n_reg, n_hit, na, frac_rep, zarena, cigpool, counters, lists, hit_cnt, cig_cnt, hit_off_c, cig_off_c;
     DevBuf order_key_in, order_key_out, order_in, order_out, queues, sort_tmp, jobs, fast_list, dp_list, part_flag, part_pos, cand, cand_base,
         cand_cnt, cand_off, dbg_cyc, order_tmp, first_tab, first_cnt, first_off, fb_list, first_jobs, len_stat, s_score, long_list, long_scratch, huge_rows;
+    DevBuf guard_cnt;                                                              // test hook "z_start" / "cig_start": changed bytes behind the two pools (slx_align.hip, worker_run)
     DevBuf chain_left;                                                             // chaining: the light reads k_chain_lds leaves to k_chain (their read numbers)
     DevBuf order_bin, bin_cnt;                                                     // finalize: the multi-region reads binned by region count
     DevBuf defer_list, hits_big;                                                   // finalize: reads k_regs defers to the wave kernel, reads k_hits leaves to k_hits_wave
@@ -123,7 +124,7 @@ struct Worker {
                &c_pos, &c_head, &c_tail, &c_n, &c_rid, &c_w, &c_first, &c_kept, &ia, &ib, &ic, &srt, &regs, &hits, &n_chain, &n_reg, &n_hit,
                &na, &frac_rep, &zarena, &cigpool, &counters, &lists, &hit_cnt, &cig_cnt, &hit_off_c, &cig_off_c, &order_key_in,
                &order_key_out, &order_in, &order_out, &queues, &sort_tmp, &jobs, &fast_list, &dp_list, &part_flag, &part_pos, &cand, &cand_base,
-               &cand_cnt, &cand_off, &dbg_cyc, &order_tmp, &first_tab, &first_cnt, &first_off, &fb_list, &first_jobs, &len_stat, &s_score, &long_list, &long_scratch, &huge_rows, &p2mask, &p2list, &p2items, &p2long, &lane_jobs, &first_dp, &first_sorted, &first_bins, &cig_lane_list, &defer_list, &hits_big, &order_bin, &bin_cnt, &chain_left, &snap_ia, &snap_regs, &snap_nreg,
+               &cand_cnt, &cand_off, &dbg_cyc, &order_tmp, &first_tab, &first_cnt, &first_off, &fb_list, &first_jobs, &len_stat, &s_score, &long_list, &long_scratch, &huge_rows, &p2mask, &p2list, &p2items, &p2long, &lane_jobs, &first_dp, &first_sorted, &first_bins, &cig_lane_list, &defer_list, &hits_big, &order_bin, &bin_cnt, &chain_left, &guard_cnt, &snap_ia, &snap_regs, &snap_nreg,
                &memo_idx, &memo_jobs, &memo_tab, &round_list, &todo_a, &todo_b, &spec_cnt, &seed3_buf, &job_key_in, &job_key_out, &job_val_in, &job_val_out, &job_sort_tmp, &pseg_jobs, &pseg_idx, &pseg_cnt, &gseg_jobs, &gseg_units, &gseg_wrec, &gseg_wout, &gseg_scratch, &gseg_cnt, &xseg_jobs, &xseg_state, &xseg_units, &xseg_out, &xseg_wrec, &xseg_wout, &xseg_scratch, &xseg_cnt,
                &o_hit_off, &o_rid, &o_pos, &o_flag, &o_mapq, &o_score, &o_nm, &o_na, &o_ncig, &o_cig_off, &o_cigar, &o_xa, &o_sub};
         for (auto &e : ev) e = nullptr;
@@ -238,6 +239,11 @@ struct slx_aligner {
     unsigned long long cig_per_read = 8;    // cigar-pool words per read
     unsigned long long cig_floor = 0;       // ... and its floor (learnt from small batches that overflowed)
     int n_retries = 0;
+    // test hook: the caps the first attempt of every chunk runs with, in place of the budgets above (0 = off; slx_aligner_set "z_start" / "cig_start")
+    unsigned long long z_start = 0, cig_start = 0;        // arena bytes / CIGAR-pool words
+    unsigned long long z_hook = 0, cig_hook = 0;          // ... what an overflow under the hook taught (kept apart from the budgets; setting either knob forgets both)
+    long long guard_dirty = 0;                            // ... bytes found changed behind the two pools, since the aligner was created
+    uint32_t ovf_sites = 0;                               // OVS_* bits of every failed attempt since the aligner was created
     std::mutex mu;                // guards the capacity hints above when workers update them
     std::mutex call_mu;           // one batch at a time per aligner: the C++ mirror's alignSequence is const and may be called from many threads
     std::vector<Worker *> workers;

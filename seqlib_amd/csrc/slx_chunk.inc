@@ -632,7 +632,7 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
     ENS(zarena, caps.zcap); ENS(cigpool, caps.cigcap * 4);
     ENS(hit_cnt, ((size_t)n + 1) * 8); ENS(cig_cnt, ((size_t)n + 1) * 8); ENS(hit_off_c, ((size_t)n + 1) * 8); ENS(cig_off_c, ((size_t)n + 1) * 8);
     ENS(counters, 64); ENS(p2mask, (size_t)n * 8); ENS(p2list, (size_t)n * 4); ENS(p2items, (size_t)n * 4); ENS(p2long, (size_t)n * 4);
-    // counters: [0] zused, [1] cigused, [2] flags(u32)
+    // counters: [0] zused, [1] cigused, [2] flags(u32), then one u32 of site bits that raise no flag (OVS_Z_DP_WAVE, dev_types.h)
     HIPCHK(hipMemsetAsync(wk->counters.p, 0, 64, st));
     ENS(queues, 256);
     HIPCHK(hipMemsetAsync(wk->queues.p, 0, 256, st));
