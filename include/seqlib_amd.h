@@ -239,7 +239,8 @@ int  slx_aligner_probe_launches(const slx_aligner *al);
  * "workers" = the aligner's worker count (per device); "hw_queues" = GPU_MAX_HW_QUEUES as the process had it when the aligner was created (4 = unset: the library
  * reads it, never sets it); "regs_deferred" = reads the lane region kernel handed to the wave kernel since the aligner was created;
  * "retries" = chunks run again after an overflow of their work areas since the aligner was created (a steady workload shows 0 after its first call);
- * "chain_lds_reads" / "chain_lds_bail" = reads of the last batch whose chaining finished in LDS / gave the LDS pass up (a 10th chain) and ran again on the HBM columns */
+ * "chain_lds_reads" / "chain_lds_bail" = reads of the last batch whose chaining finished in LDS / gave the LDS pass up (a 10th chain) and ran again on the HBM columns;
+ * "first_lane_jobs" = top-seed extensions of the last batch that k_first_lanes ran (the dynamic program, one lane per job), as the kernel counted them */
 int64_t slx_aligner_counter(const slx_aligner *al, const char *key);
 
 /* Test hook (per-stage differential tests): intermediate results of one read of the LAST batch, copied out of the device work

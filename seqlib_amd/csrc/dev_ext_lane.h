@@ -5,13 +5,14 @@
 // kernel is a serial walk of 10-40 ms on one wave (the extension stage's tail) and on the wave-per-seed job kernel (k_extend_cand)
 // ~10 000 wave instructions per extension.  The extensions of different seeds do not depend on each other, and for these reads there
 // are hundreds of them with the same query: here a wave takes 64 seeds and every lane runs ksw_extend2's scalar loops on its own -- the
-// H/E row of a lane lives in LDS, column-major across the lanes (cell j * 64 + lane: no bank conflicts; layouts below) -- ~36 instructions
+// H/E row of a lane lives in LDS, column-major across the lanes (cell j * 64 + lane: no bank conflicts; layouts and the row loop: dev_lane_rows.h) -- ~36 instructions
 // per cell for 64 extensions at once instead of ~170 per row for one.
 // k_extend_reg then replays mem_chain2aln's decisions and takes the regions from the table (cand), as it does after k_extend_cand.
 // /root/reference/src/BWAAligner.cpp:104 -> mem_align1 -> mem_chain2aln -> ksw_extend2.
 #pragma once
 #include "dev_seed4.h"
 #include "dev_ext_reg.h"
+#include "dev_lane_rows.h"
 
 struct alignas(8) LaneJob {    // one seed extension (k_cand_lane_prep -> k_ext_lanes)
     int64_t s_rbeg, rmax0, rmax1;
@@ -24,122 +25,17 @@ struct alignas(8) LaneJob {    // one seed extension (k_cand_lane_prep -> k_ext_
 
 #define LANE_SCORE_LIMIT 16000  // (read length) x max(mat) has to stay below this for the lane kernel to be used (host check)
 
-// Where a lane keeps its H/E row.  WIDE: one 32-bit word per column -- 14-bit H, 14-bit E, the column's query code above them.  NARROW: when
-// no score can reach 256 (150 bp reads with bwa's default scores: read length x max(mat) < 256) a column is 8-bit H + 8-bit E in a 16-bit
-// word and the query codes sit apart, eight 4-bit codes per word: half the LDS per wave, twice the waves per CU -- and the kernel's time
-// is inversely proportional to its waves per CU (measured by padding the rows: 4 / 3 / 2 waves per CU -> 30.8 / 40.4 / 60.3 ms).
-struct LaneWide {
-    uint32_t *eh;                                   // this lane's word of column 0; stride WAVE words
-    static __host__ __device__ size_t bytes(int cols) { return (size_t)cols * WAVE * 4; }
-    __device__ __forceinline__ void init(uint32_t *base, int, int lane) { eh = base + lane; }
-    __device__ __forceinline__ void put_all(int j, int h, int e, int q) { eh[j * WAVE] = (uint32_t)h | (uint32_t)e << 14 | (uint32_t)q << 28; }
-    __device__ __forceinline__ uint32_t get(int j) const { return eh[j * WAVE]; }
-    __device__ __forceinline__ int q_of(uint32_t v, int) const { return (int)(v >> 28); }
-    static __device__ __forceinline__ int h_of(uint32_t v) { return (int)(v & 0x3fffu); }
-    static __device__ __forceinline__ int e_of(uint32_t v) { return (int)((v >> 14) & 0x3fffu); }
-    __device__ __forceinline__ void put(int j, int h, int e, uint32_t old) { eh[j * WAVE] = (uint32_t)h | (uint32_t)e << 14 | (old & 0xf0000000u); }
-    static __device__ __forceinline__ bool zero(uint32_t v) { return (v & 0x0fffffffu) == 0; }
-};
-struct LaneNarrow {
-    uint16_t *eh;                                   // 16-bit cells, stride WAVE
-    uint32_t *qa;                                   // eight 4-bit query codes per word, stride WAVE words
-    static __host__ __device__ size_t bytes(int cols) { return (size_t)cols * WAVE * 2 + (size_t)((cols + 7) / 8) * WAVE * 4; }
-    __device__ __forceinline__ void init(uint32_t *base, int cols, int lane) { eh = (uint16_t *)base + lane; qa = base + (size_t)cols * WAVE / 2 + lane; }
-    __device__ __forceinline__ void put_all(int j, int h, int e, int q)
-    {
-        eh[j * WAVE] = (uint16_t)(h | e << 8);
-        uint32_t w = (j & 7) ? qa[(j >> 3) * WAVE] : 0u;        // (columns are written in ascending order: a word starts at its column 0)
-        w |= (uint32_t)q << ((j & 7) * 4);
-        qa[(j >> 3) * WAVE] = w;
-    }
-    __device__ __forceinline__ uint32_t get(int j) const { return eh[j * WAVE]; }
-    __device__ __forceinline__ int q_of(uint32_t, int j) const { return (int)((qa[(j >> 3) * WAVE] >> ((j & 7) * 4)) & 7u); }
-    static __device__ __forceinline__ int h_of(uint32_t v) { return (int)(v & 0xffu); }
-    static __device__ __forceinline__ int e_of(uint32_t v) { return (int)(v >> 8); }
-    __device__ __forceinline__ void put(int j, int h, int e, uint32_t) { eh[j * WAVE] = (uint16_t)(h | e << 8); }
-    static __device__ __forceinline__ bool zero(uint32_t v) { return v == 0; }
+// (the rows' two layouts, LaneWide and LaneNarrow, and the row loop: dev_lane_rows.h)
+
+struct LaneBases {              // lane_rows_extend's bases: the read's codes, the reference through a 32-base window (one 8-byte read per 32 rows)
+    const DevRef &R;
+    const uint8_t *query;
+    RWin rw;
+    __device__ __forceinline__ int q(int j) const { return (int)query[j]; }
+    __device__ __forceinline__ int t(int64_t p) { return text_at(R, p, rw); }
 };
 
-// ksw_extend2, scalar, one extension per lane; L = the lane's row (not initialised by the caller)
-template <typename L, typename QF, typename TF>
-__device__ ExtResult lane_ksw_extend2(int qlen, QF qf, int tlen, TF tf, const slx_opt &o, const MatRows &mr, int w, int end_bonus, int h0, L &row)
-{
-    const int o_del = o.o_del, e_del = o.e_del, o_ins = o.o_ins, e_ins = o.e_ins, zdrop = o.zdrop;
-    const int oe_del = o_del + e_del, oe_ins = o_ins + e_ins;
-    // row -1: eh[0].h = h0, then the insertion ramp while it stays positive; the query code of column j rides along
-    for (int j = 0; j <= qlen; ++j) {
-        const int v = h0 - oe_ins - (j - 1) * e_ins;
-        const int h = j == 0 ? h0 : (v > 0 ? v : 0);
-        row.put_all(j, h, 0, j < qlen ? qf(j) : 0);
-    }
-    int max = 0;
-    for (int i = 0; i < 25; ++i) max = max > o.mat[i] ? max : o.mat[i];
-    int max_ins = (int)((double)(qlen * max + end_bonus - o_ins) / e_ins + 1.);
-    max_ins = max_ins > 1 ? max_ins : 1;
-    w = w < max_ins ? w : max_ins;
-    int max_del = (int)((double)(qlen * max + end_bonus - o_del) / e_del + 1.);
-    max_del = max_del > 1 ? max_del : 1;
-    w = w < max_del ? w : max_del;
-    const int tail_top = ext_tail_bound0(o, qlen, h0, max);
-    max = h0;
-    int max_i = -1, max_j = -1, max_ie = -1, gscore = -1, max_off = 0, beg = 0, end = qlen;
-    for (int i = 0; i < tlen; ++i) {
-        if (i >= qlen && ext_tail_done(tail_top - (i - qlen) * e_del, max, gscore)) break;      // dev_ext_wave.h: rows that cannot matter
-        const int t = tf(i);
-        const uint32_t rowp = t == 0 ? mr.packed[0] : t == 1 ? mr.packed[1] : t == 2 ? mr.packed[2] : t == 3 ? mr.packed[3] : mr.packed[4];
-        const int row4 = t == 0 ? mr.q4[0] : t == 1 ? mr.q4[1] : t == 2 ? mr.q4[2] : t == 3 ? mr.q4[3] : mr.q4[4];
-        int f = 0, m = 0, mj = -1;
-        if (beg < i - w) beg = i - w;
-        if (end > i + w + 1) end = i + w + 1;
-        if (end > qlen) end = qlen;
-        int h1 = 0;
-        if (beg == 0) { h1 = h0 - (o_del + e_del * (i + 1)); if (h1 < 0) h1 = 0; }
-        uint32_t cur = beg < end ? row.get(beg) : 0u;
-        for (int j = beg; j < end; ++j) {
-            const uint32_t nxt = row.get(j + 1);                    // (column j + 1 <= qlen exists; read ahead of this cell's arithmetic)
-            int M = L::h_of(cur), e = L::e_of(cur);
-            const uint32_t q = (uint32_t)row.q_of(cur, j);
-            const int s = q < 4 ? __builtin_amdgcn_sbfe((int)rowp, q << 3, 8u) : row4;
-            M = M ? M + s : 0;
-            int h = M > e ? M : e;
-            h = h > f ? h : f;
-            const int hl = h1;                                      // H(i, j-1): what eh[j].h holds for the next row
-            h1 = h;
-            mj = m > h ? mj : j;
-            m = m > h ? m : h;
-            int t2 = M - oe_del; t2 = t2 > 0 ? t2 : 0;
-            e -= e_del; e = e > t2 ? e : t2;
-            row.put(j, hl, e, cur);
-            t2 = M - oe_ins; t2 = t2 > 0 ? t2 : 0;
-            f -= e_ins; f = f > t2 ? f : t2;
-            cur = nxt;
-        }
-        row.put(end, h1, 0, beg < end ? cur : row.get(end));        // eh[end].h = h1; eh[end].e = 0 (the column keeps its query code)
-        if ((end > beg ? end : beg) == qlen) {                       // (the scalar loop's j after its last trip)
-            max_ie = gscore > h1 ? max_ie : i;
-            gscore = gscore > h1 ? gscore : h1;
-        }
-        if (m == 0) break;
-        if (m > max) {
-            max = m; max_i = i; max_j = mj;
-            const int off = mj - i < 0 ? i - mj : mj - i;
-            max_off = max_off > off ? max_off : off;
-        } else if (zdrop > 0) {
-            if (i - max_i > mj - max_j) { if (max - m - ((i - max_i) - (mj - max_j)) * e_del > zdrop) break; }
-            else { if (max - m - ((mj - max_j) - (i - max_i)) * e_ins > zdrop) break; }
-        }
-        int j;
-        for (j = beg; j < end && L::zero(row.get(j)); ++j) {}
-        beg = j;
-        for (j = end; j >= beg && L::zero(row.get(j)); --j) {}
-        end = j + 2 < qlen ? j + 2 : qlen;
-    }
-    ExtResult r;
-    r.score = max; r.qle = max_j + 1; r.tle = max_i + 1; r.gtle = max_ie + 1; r.gscore = gscore; r.max_off = max_off;
-    return r;
-}
-
-// dev_extend_core, one seed per lane (the same statements, the scalar extension above in place of the wave-wide one)
+// dev_extend_core, one seed per lane (the same statements; both sides and both band trials run in lane_rows_extend's one row loop)
 template <typename L>
 __device__ DReg lane_extend_core(const DevRef &R, const slx_opt &opt, const MatRows &mr, const uint8_t *query, int l_query, int s_qbeg, int s_len,
                                  int64_t s_rbeg, int64_t rmax0, int64_t rmax1, int rid, float frac_rep, L &eh)
@@ -147,38 +43,30 @@ __device__ DReg lane_extend_core(const DevRef &R, const slx_opt &opt, const MatR
     DReg a;
     a.rb = a.re = 0; a.qb = a.qe = 0; a.sub = a.csub = a.sub_n = 0; a.seedcov = 0; a.secondary = 0;
     a.n_comp = 0; a.hash = 0;
-    int aw0 = opt.w, aw1 = opt.w, i;
-    a.w = opt.w; a.score = a.truesc = -1; a.rid = rid;
-    RWin rw; rw.bits = 0; rw.chunk = -1;             // the reference through a 32-base window: one 8-byte read per 32 rows
-    if (s_qbeg) {
-        const int64_t tmp = s_rbeg - rmax0;
-        ExtResult er; er.score = -1; er.qle = er.tle = er.gtle = er.gscore = er.max_off = 0;
-        for (i = 0; i < 2; ++i) {
-            const int prev = a.score;
-            aw0 = opt.w << i;
-            er = lane_ksw_extend2(s_qbeg, [&](int j) { return (int)query[s_qbeg - 1 - j]; }, (int)tmp,
-                                  [&](int t) { return text_at(R, s_rbeg - 1 - t, rw); }, opt, mr, aw0, opt.pen_clip5, s_len * opt.a, eh);
+    int aw0 = opt.w, aw1 = opt.w;
+    a.w = opt.w; a.rid = rid;
+    a.score = a.truesc = s_len * opt.a; a.qb = 0; a.rb = s_rbeg;          // (what stands where there is nothing to the left of the seed)
+    const int qe = s_qbeg + s_len;
+    const int64_t re0 = s_rbeg + s_len;
+    a.qe = l_query; a.re = re0;                                           // (... and to its right)
+    LaneSide sd[2];
+    sd[0].qlen = s_qbeg; sd[0].tlen = (int)(s_rbeg - rmax0); sd[0].q0 = s_qbeg - 1; sd[0].t0 = s_rbeg - 1; sd[0].end_bonus = opt.pen_clip5;
+    sd[1].qlen = l_query - qe; sd[1].tlen = (int)(rmax1 - re0); sd[1].q0 = qe; sd[1].t0 = re0; sd[1].end_bonus = opt.pen_clip3;
+    LaneBases bases{R, query, {0, -1}};
+    lane_rows_extend(sd, s_len * opt.a, opt, mr, eh, bases, [&](int side, const LaneRes &er) {
+        if (side == 0) {
+            aw0 = er.aw;
             a.score = er.score;
-            if (a.score == prev || er.max_off < (aw0 >> 1) + (aw0 >> 2)) break;
-        }
-        if (er.gscore <= 0 || er.gscore <= a.score - opt.pen_clip5) { a.qb = s_qbeg - er.qle; a.rb = s_rbeg - er.tle; a.truesc = a.score; }
-        else { a.qb = 0; a.rb = s_rbeg - er.gtle; a.truesc = er.gscore; }
-    } else { a.score = a.truesc = s_len * opt.a; a.qb = 0; a.rb = s_rbeg; }
-    if (s_qbeg + s_len != l_query) {
-        const int sc0 = a.score, qe = s_qbeg + s_len;
-        const int64_t re0 = s_rbeg + s_len;
-        ExtResult er; er.score = -1; er.qle = er.tle = er.gtle = er.gscore = er.max_off = 0;
-        for (i = 0; i < 2; ++i) {
-            const int prev = a.score;
-            aw1 = opt.w << i;
-            er = lane_ksw_extend2(l_query - qe, [&](int j) { return (int)query[qe + j]; }, (int)(rmax1 - re0),
-                                  [&](int t) { return text_at(R, re0 + t, rw); }, opt, mr, aw1, opt.pen_clip3, sc0, eh);
+            if (er.gscore <= 0 || er.gscore <= a.score - opt.pen_clip5) { a.qb = s_qbeg - er.qle; a.rb = s_rbeg - er.tle; a.truesc = a.score; }
+            else { a.qb = 0; a.rb = s_rbeg - er.gtle; a.truesc = er.gscore; }
+        } else {
+            aw1 = er.aw;
+            const int sc0 = a.score;
             a.score = er.score;
-            if (a.score == prev || er.max_off < (aw1 >> 1) + (aw1 >> 2)) break;
+            if (er.gscore <= 0 || er.gscore <= a.score - opt.pen_clip3) { a.qe = qe + er.qle; a.re = re0 + er.tle; a.truesc += a.score - sc0; }
+            else { a.qe = l_query; a.re = re0 + er.gtle; a.truesc += er.gscore - sc0; }
         }
-        if (er.gscore <= 0 || er.gscore <= a.score - opt.pen_clip3) { a.qe = qe + er.qle; a.re = re0 + er.tle; a.truesc += a.score - sc0; }
-        else { a.qe = l_query; a.re = re0 + er.gtle; a.truesc += er.gscore - sc0; }
-    } else { a.qe = l_query; a.re = s_rbeg + s_len; }
+    });
     a.w = aw0 > aw1 ? aw0 : aw1;
     a.seedlen0 = s_len;
     a.frac_rep = frac_rep;
@@ -342,7 +230,7 @@ __global__ void __launch_bounds__(256) k_first_bin_scatter(const FirstJob *jobs,
 
 template <typename L>
 __global__ void __launch_bounds__(64) k_first_lanes(DevRef R, Chunk ck, DevOpt dopt, unsigned int *queue, const FirstJob *jobs, DReg *first, const unsigned int *list,
-                                                     const unsigned int *n_list, int cols)
+                                                     const unsigned int *n_list, int cols, unsigned int *n_ran)
 {
     const slx_opt &opt = dopt.o;
     const int lane = threadIdx.x;
@@ -361,6 +249,7 @@ __global__ void __launch_bounds__(64) k_first_lanes(DevRef R, Chunk ck, DevOpt d
             const DReg a = lane_extend_core<L>(R, opt, mr, ck.codes + j.q_off, j.l_query, j.s_qbeg, j.s_len, j.s_rbeg, j.rmax0, j.rmax1, j.rid, j.frac_rep, row);
             first[job] = a;                              // seedcov is filled in by k_ext_replay
         }
+        if (lane == 0) atomicAdd(n_ran, n_jobs - base < (unsigned int)WAVE ? n_jobs - base : (unsigned int)WAVE);      // jobs this wave has run ("first_lane_jobs")
     }
 }
 

@@ -14,6 +14,7 @@
 // zero mask; ties resolve as the scalar loop does (last arg-max in a row, first row for the maximum).
 #pragma once
 #include "dev_ext.h"
+#include "dev_lane_rows.h"
 
 #define WAVE 64
 #define NEG_BIG (-0x3fffffff)
@@ -65,13 +66,7 @@ __device__ __forceinline__ MatRows make_matrows(const int8_t *mat)
 // tlen ends the loop -- leaves all six reported values as they are, and the loop can stop.  With h0 = 90 and a 57-column extension
 // through two mismatches that is row 61 instead of row ~110 (the first column alone stays alive for h0 - o_del rows).
 // Needs non-negative gap penalties (else: never).  The scalar CPU restatement the parity tests compare with has no such exit.
-__device__ __forceinline__ int ext_tail_bound0(const slx_opt &o, int qlen, int h0, int amax)
-{   // B_qlen (the value at row i = qlen); INT_MAX when the bound does not hold
-    if (o.o_del < 0 || o.e_del < 0 || o.o_ins < 0 || o.e_ins < 0) return 0x7fffffff;
-    const long long b = (long long)h0 + (long long)qlen * (amax > 0 ? amax : 0) - o.o_del - o.e_del;
-    return b > 0x3fffffff ? 0x7fffffff : (int)b;
-}
-__device__ __forceinline__ bool ext_tail_done(int b, int max, int gscore) { return b <= max && (b > 0 ? b : 0) < gscore; }
+// (ext_tail_bound0 = B_qlen, INT_MAX when the bound does not hold, and ext_tail_done: dev_lane_rows.h, which the host compiles too)
 
 // ---------------------------------------------------------------------------------------------- long extensions: the band in registers
 // A contig's extension runs for tens of thousands of rows inside a band of 2 w + 2 columns that slides one column per row.  Here the

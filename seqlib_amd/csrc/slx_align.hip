@@ -592,6 +592,12 @@ extern "C" int64_t slx_aligner_counter(const slx_aligner *al, const char *key)
             if (al->is_group) for (const slx_aligner *sub : al->subs) take(sub); else take(al);
             return v;
         }
+        if (!strcmp(key, "first_lane_jobs")) {          // last batch: top-seed extensions k_first_lanes ran (the DP jobs, one lane each)
+            long long v = 0;
+            auto take = [&](const slx_aligner *a) { for (const Worker *wk : a->workers) v += (long long)wk->first_stat; };
+            if (al->is_group) for (const slx_aligner *sub : al->subs) take(sub); else take(al);
+            return v;
+        }
         if (!strcmp(key, "retries")) {          // chunks run again after an overflow of their work areas (interval lists, traceback arena, CIGAR pool) since the aligner was created
             long long v = 0;
             if (al->is_group) for (const slx_aligner *sub : al->subs) v += sub->n_retries; else v = al->n_retries;
@@ -720,6 +726,7 @@ static int worker_run(slx_aligner *al, Worker *wk, const slx_opt *opt, const uin
     wk->n_chunks = 0;
     for (long long &c : wk->cnt) c = 0;
     wk->chain_stat[0] = wk->chain_stat[1] = 0;
+    wk->first_stat = 0;
     int rc;
     const int64_t n_part = r_hi - r_lo;
     if ((rc = wk->o_hit_off.ensure(((size_t)n_part + 1) * 8)) != SLX_OK) return rc;

@@ -55,7 +55,7 @@ struct DevBuf {
 // The host sizes every stage by a few counters of the one before.  Each used to come back with a hipMemcpyAsync of its own into a pageable local -- five after
 // seeding, three before the compaction: ~20 us apiece, a third of a one-read call.  k_mail gathers them with ONE launch and writes them straight into pinned
 // host memory the worker keeps (the stream's synchronisation, which the host needs anyway, makes them visible): no copy at all.
-#define SLX_MAIL_PARTS 8            // (the largest user, the end of run_chunk, fills six)
+#define SLX_MAIL_PARTS 8            // (the largest user, the end of run_chunk, fills seven)
 struct MailSpec { const unsigned int *src[SLX_MAIL_PARTS]; int words[SLX_MAIL_PARTS]; int n; };
 static __global__ void k_mail(MailSpec s, unsigned int *dst)
 {
@@ -97,6 +97,8 @@ struct Worker {
     DevBuf pseg_jobs, pseg_idx, pseg_cnt;                                          // ... and mem_patch_reg's alignments computed ahead of the region kernel
     unsigned long long fin_stat[2] = {0, 0};                                       // reads deferred by k_regs / left to k_hits_wave since the aligner was created
     unsigned long long chain_stat[2] = {0, 0};                                     // reads k_chain_lds started over on the HBM columns / reads it finished in LDS, of the last batch
+    unsigned long long first_stat = 0;                                             // k_first_lanes: DP jobs it counted as run, of the last batch
+    bool first_lanes_ran = false;                                                  // ... the chunk in flight took that path
     unsigned int pseg_stat = 0;                                                    // ... how many
     unsigned int gseg_stat[3] = {0, 0, 0};                                         // ... segments taken as speculated / run again / jobs cut
     unsigned int xseg_stat[4] = {0, 0, 0, 0};                                      // ... segments taken as speculated / computed again / second band tries / sides cut, summed over this worker's launches

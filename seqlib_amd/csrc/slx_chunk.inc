@@ -636,6 +636,7 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
     HIPCHK(hipMemsetAsync(wk->counters.p, 0, 64, st));
     ENS(queues, 256);
     HIPCHK(hipMemsetAsync(wk->queues.p, 0, 256, st));
+    wk->first_lanes_ran = false;
     HIPCHK(hipMemsetAsync(wk->seed_cnt.as<unsigned long long>() + n, 0, 8, st));      // (k_seed_epi writes the count of every read; the scan takes n + 1 entries)
 
     Chunk ck;
@@ -982,6 +983,7 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
                 if (first_lanes) {
                     ENS(first_sorted, (size_t)top_cap * 4); ENS(first_bins, 1024);
                     HIPCHK(hipMemsetAsync(wk->first_bins.p, 0, 512, st));
+                    wk->first_lanes_ran = true;
                 }
                 hipLaunchKernelGGL(k_first_prep, dim3(std::max(1, std::min(n / 128 + 1, al->n_cu * 12))), dim3(128), 0, st, al->ref, ck, dopt, n, wk->first_off.as<unsigned int>(),
                                    top_cap, wk->first_jobs.as<FirstJob>());
@@ -998,9 +1000,9 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
                         hipLaunchKernelGGL(k_first_bin_scan, dim3(1), dim3(1), 0, st, bins);
                         hipLaunchKernelGGL(k_first_bin_scatter, dim3(al->n_cu * 4), dim3(256), 0, st, fj, (const unsigned int *)wk->first_dp.as<unsigned int>(), (const unsigned int *)(q + 40), max_len, bins, sorted);
                         if (fl_narrow) hipLaunchKernelGGL(k_first_lanes<LaneNarrow>, dim3(al->n_cu * 8), dim3(64), LaneNarrow::bytes(fl_cols), st, al->ref, ck, dopt, q + 22, fj, wk->first_tab.as<DReg>(),
-                                                          (const unsigned int *)sorted, (const unsigned int *)(q + 40), fl_cols);
+                                                          (const unsigned int *)sorted, (const unsigned int *)(q + 40), fl_cols, q + 54);
                         else hipLaunchKernelGGL(k_first_lanes<LaneWide>, dim3(al->n_cu * 4), dim3(64), LaneWide::bytes(fl_cols), st, al->ref, ck, dopt, q + 22, fj, wk->first_tab.as<DReg>(),
-                                                (const unsigned int *)sorted, (const unsigned int *)(q + 40), fl_cols);
+                                                (const unsigned int *)sorted, (const unsigned int *)(q + 40), fl_cols, q + 54);
                     } else
                     hipLaunchKernelGGL(k_ext_first<MAXQ>, dim3(gf), dim3(64), 0, st, al->ref, ck, dopt, n, wk->first_off.as<unsigned int>(), top_cap, q + 22,
                                        wk->first_jobs.as<FirstJob>(), wk->first_tab.as<DReg>(), al->first_diag ? wk->first_dp.as<unsigned int>() : (const unsigned int *)nullptr, q + 40);
@@ -1049,6 +1051,7 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
         ms.src[4] = wk->queues.as<unsigned int>() + 48; ms.words[4] = 1;          // reads k_hits left to k_hits_wave
         ms.src[5] = wk->queues.as<unsigned int>() + 50; ms.words[5] = 2;          // reads k_chain_lds started over on the HBM columns, reads it finished in LDS
         ms.n = 6;
+        if (wk->first_lanes_ran) { ms.src[6] = wk->queues.as<unsigned int>() + 54; ms.words[6] = 1; ms.n = 7; }          // jobs k_first_lanes counted as run
         hipLaunchKernelGGL(k_mail, dim3(1), dim3(64), 0, st, ms, wk->h_mail);
     }
     HIPCHK(slx_wait_stream(st));
@@ -1057,6 +1060,7 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
     wk->fin_stat[0] += wk->h_mail[5]; wk->fin_stat[1] += wk->h_mail[6];
     if (fl) { *flags_out = fl; return SLX_OK; }
     wk->chain_stat[0] += wk->h_mail[7]; wk->chain_stat[1] += wk->h_mail[8];
+    if (wk->first_lanes_ran) wk->first_stat += wk->h_mail[9];
     // grow the outputs and compact
     const size_t H = (size_t)*hit_base + Hc, C = (size_t)*cig_base + Cc;
 #define GROW(buf, bytes, keep) if ((rc = wk->buf.grow((size_t)(bytes), (size_t)(keep), st)) != SLX_OK) return rc
