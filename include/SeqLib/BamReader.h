@@ -10,7 +10,8 @@
 // overlaps (src/BamReader.cpp:64-137: one iterator per region): only the BGZF members the index names are inflated, and the records are tested against the
 // region and compacted on the GPU.  The interval handed down is [pos1, pos2), exactly what the reference hands to sam_itr_queryi.
 // New next to the reference: GetNextRecord (the README's spelling, README.md:150-181), NextBatch (many records at once through the slab path of
-// BamRecord.h), SetBatchBytes, HasIndex.
+// BamRecord.h), SetBatchBytes, HasIndex, and SetReadFilter / ClearReadFilter: a Filter::ReadFilterCollection evaluated on the GPU, so that Next, NextBatch and
+// BWAAligner::alignSequences(BamReader&) see the kept records only -- for the whole file and for regions.
 // Refused loudly: SetRegion / SetRegions with anything but a GenomicRegion / a GRC, CRAM and SAM-text input, "-" (stdin), a second Open.
 #pragma once
 #include <cstdint>
@@ -23,7 +24,9 @@
 #include "SeqLib/BamHeader.h"
 #include "SeqLib/BamRecord.h"
 #include "SeqLib/GenomicRegionCollection.h"
+#include "SeqLib/ReadFilter.h"
 #include "seqlib_amd_bam.h"
+#include "seqlib_amd_filter.h"
 
 namespace SeqLib {
 
@@ -64,6 +67,7 @@ public:
     {
         if (rd_) slx_bam_close(rd_);
         rd_ = nullptr;
+        flt_.reset();
         hdr_ = BamHeader();
         clear_batch();
     }
@@ -99,6 +103,22 @@ public:
         return false;
     }
     bool SetCramReference(const std::string &) { std::cerr << "BamReader::SetCramReference - CRAM input is not available in the MI355X drop-in" << std::endl; return false; }
+
+    // From the next batch on the reader serves only the records the collection keeps: every batch is evaluated and compacted in HBM (include/seqlib_amd_filter.h).
+    // The reader holds the compiled collection; rules added to fc afterwards take effect with the next SetReadFilter.  false when the reader is not open.
+    bool SetReadFilter(const Filter::ReadFilterCollection &fc)
+    {
+        if (!rd_) return false;
+        std::shared_ptr<slx_filter> h = fc.Handle();
+        if (slx_filter_attach(h.get(), rd_) != SLX_OK) { std::cerr << "BamReader::SetReadFilter - " << slx_last_error() << std::endl; return false; }
+        flt_ = h;
+        return true;
+    }
+    void ClearReadFilter()
+    {
+        if (rd_) slx_filter_attach(nullptr, rd_);
+        flt_.reset();
+    }
 
     std::optional<BamRecord> Next()
     {
@@ -217,6 +237,7 @@ private:
 
     std::string path_;
     slx_bam *rd_ = nullptr;
+    std::shared_ptr<slx_filter> flt_;          // the attached read filter, alive as long as the reader uses it
     BamHeader hdr_;
     slx_bam_batch batch_ = {};
     size_t cur_ = 0;

@@ -3,6 +3,9 @@
 // semantics as /root/reference/SeqLib/BamRecord.h:49-192,202-675 and src/BamRecord.cpp:33-106,
 // 255-274,646-664,861-917,960-970,1039-1054; the rest of that 70-method class (mate/pair fields,
 // interval algebra, pile-up helpers) is BAM utility API outside this path.
+// The accessors the read filter's rules call (FullInsertSize, PairOrientation, Interchromosomal, PairMappedFlag, NumClip, NumHardClip, MaxInsertionBases,
+// MaxDeletionBases, CountNBases, ParseReadGroup; SeqLib/BamRecord.h:264, 298, 408-415, src/BamRecord.cpp:580-589, 983-996, 1012-1028, 1139-1158, 1185-1213) go over
+// slx_filter_features (include/seqlib_amd_filter.h): the one body the GPU filter evaluates, so each rule is written down once.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -20,6 +23,7 @@
 #include <string_view>
 #include <vector>
 #include "SeqLib/hts_compat.h"
+#include "seqlib_amd_filter.h"
 
 namespace SeqLib {
 
@@ -99,6 +103,23 @@ struct SlabWriter {
         return cur;
     }
 };
+}  // namespace detail
+
+namespace detail {
+// the record as it stands in a BAM stream: block_size, the 32 fixed bytes, the variable part
+inline std::vector<uint8_t> packed_record(const bam1_t *b)
+{
+    std::vector<uint8_t> o(36 + (size_t)b->l_data);
+    auto put32 = [&](size_t at, uint32_t v) { std::memcpy(&o[at], &v, 4); };
+    const bam1_core_t &c = b->core;
+    put32(0, 32u + (uint32_t)b->l_data); put32(4, (uint32_t)c.tid); put32(8, (uint32_t)c.pos);
+    o[12] = (uint8_t)c.l_qname; o[13] = (uint8_t)c.qual;
+    const uint16_t bin = (uint16_t)c.bin, nc = (uint16_t)c.n_cigar, fl = (uint16_t)c.flag;
+    std::memcpy(&o[14], &bin, 2); std::memcpy(&o[16], &nc, 2); std::memcpy(&o[18], &fl, 2);
+    put32(20, (uint32_t)c.l_qseq); put32(24, (uint32_t)c.mtid); put32(28, (uint32_t)c.mpos); put32(32, (uint32_t)c.isize);
+    if (b->l_data) std::memcpy(&o[36], b->data, (size_t)b->l_data);
+    return o;
+}
 }  // namespace detail
 
 struct Bam1Deleter {            // /root/reference/SeqLib/BamWalker.h:19-24
@@ -273,6 +294,17 @@ public:
         out = z;
         return true;
     }
+    // ---- what the read filter's rules read (one body with the GPU filter: slx_filter_features)
+    bool PairMappedFlag() const { return b ? features().pair_mapped != 0 : false; }
+    bool Interchromosomal() const { return b ? features().interchromosomal != 0 : false; }
+    int32_t FullInsertSize() const { return features().full_insert_size; }
+    int PairOrientation() const { return features().pair_orientation; }          // FRORIENTATION 0, FFORIENTATION 1, RFORIENTATION 2, RRORIENTATION 3, UDORIENTATION 4
+    int32_t NumClip() const { return b ? features().num_clip : 0; }
+    int32_t NumHardClip() const { return b ? features().num_hard_clip : 0; }
+    uint32_t MaxInsertionBases() const { return (uint32_t)features().max_ins; }
+    uint32_t MaxDeletionBases() const { return (uint32_t)features().max_del; }
+    int32_t CountNBases() const { return features().n_bases_n; }
+    std::string ParseReadGroup() const { return std::string(features().read_group); }
     void AddIntTag(std::string_view tag, int32_t val)
     {
         if (!b) return;
@@ -289,6 +321,15 @@ public:
     bam1_t *raw() const { return b.get(); }
 
 private:
+    // the record through the filter's feature body
+    slx_filter_feat features() const
+    {
+        if (!b) throw std::invalid_argument("BamRecord - empty record");
+        const std::vector<uint8_t> o = detail::packed_record(b.get());
+        slx_filter_feat f;
+        if (slx_filter_features(o.data(), (int64_t)o.size(), &f) != SLX_OK) throw std::runtime_error(std::string("BamRecord - ") + slx_last_error());
+        return f;
+    }
     std::shared_ptr<bam1_t> b;
 };
 

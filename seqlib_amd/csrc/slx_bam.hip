@@ -333,6 +333,16 @@ __global__ __launch_bounds__(256) void k_bam_gather(const uint8_t *s, const uint
     for (uint64_t i = lane; i < len; i += 64) o[i] = src[i];
 }
 
+// a read filter attached to the reader (slx_filter.hip): its keep bytes become the keep / length words the two exclusive sums take; and_mode: on top of the region test
+__global__ void k_bam_keep_bytes(const uint8_t *fk, const uint64_t *rec, uint64_t n_rec, int and_mode, unsigned long long *keep, unsigned long long *klen)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r > n_rec) return;
+    if (r == n_rec) { keep[r] = 0; klen[r] = 0; return; }
+    const bool k = fk[r] != 0 && (!and_mode || keep[r] != 0);
+    keep[r] = k; klen[r] = k ? rec[r + 1] - rec[r] : 0;
+}
+
 // ------------------------------------------------------------------ host: the member chain
 struct BamFile {
     int fd = -1;
@@ -469,7 +479,9 @@ struct slx_bam {
     size_t piece_i = 0;
     int64_t piece_cur = -1;                                // next member of pieces[piece_i]; -1: not begun
     bool region_mode = false;
-    std::vector<BamDBuf *> dbufs() { return {&d_comp, &d_desc, &d_err, &d_out, &d_guess, &d_used, &d_exit_a, &d_exit_b, &d_count, &d_base, &d_state, &d_rec, &d_keep, &d_blen, &d_kidx, &d_boff, &d_tmp, &d_bases, &d_offs, &d_map, &d_cs, &d_cr}; }
+    slx_filter *flt = nullptr;                             // a read filter attached by slx_filter_attach; nullptr: nothing new is launched
+    BamDBuf d_fkeep;                                       // its keep bytes
+    std::vector<BamDBuf *> dbufs() { return {&d_fkeep, &d_comp, &d_desc, &d_err, &d_out, &d_guess, &d_used, &d_exit_a, &d_exit_b, &d_count, &d_base, &d_state, &d_rec, &d_keep, &d_blen, &d_kidx, &d_boff, &d_tmp, &d_bases, &d_offs, &d_map, &d_cs, &d_cr}; }
     std::vector<BamHBuf *> hbufs() { return {&h_comp, &h_desc, &h_err, &h_out, &h_rec, &h_state, &h_map}; }
 };
 
@@ -886,6 +898,12 @@ static int bam_next_regions(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
             const uint64_t *rec = rd->d_rec.as<uint64_t>();
             k_bam_region_keep<<<(unsigned)((n_rec + 1 + 255) / 256), 256, 0, st>>>(s, rec, n_rec, g.tid, g.beg, g.end, rd->d_keep.as<ull>(), rd->d_blen.as<ull>(), ds + 5);
             BAM_HIPCHK(hipGetLastError());
+            if (rd->flt) {                                 // keep = region test AND filter
+                BAM_CHK(rd->d_fkeep.ensure(n_rec + 8));
+                BAM_CHK(slx_filter_eval_device(rd->flt, rd->device, st, s, rec, n_rec, end, rd->d_fkeep.as<uint8_t>(), nullptr));
+                k_bam_keep_bytes<<<(unsigned)((n_rec + 1 + 255) / 256), 256, 0, st>>>(rd->d_fkeep.as<uint8_t>(), rec, n_rec, 1, rd->d_keep.as<ull>(), rd->d_blen.as<ull>());
+                BAM_HIPCHK(hipGetLastError());
+            }
             size_t tb = 0;
             BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, rd->d_keep.as<ull>(), rd->d_kidx.as<ull>(), (int)(n_rec + 1), st));
             BAM_CHK(rd->d_tmp.ensure(tb + 8));
@@ -924,6 +942,64 @@ static int bam_next_regions(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
     return SLX_OK;
 }
 
+// the whole file with a read filter attached: spans as without one, the filter's keep bytes, the two exclusive sums and k_bam_gather into d_cs / d_cr as for a
+// region; a span whose records are all dropped goes on to the next, since n_records == 0 is the end of the file
+static int bam_next_filtered(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
+{
+    typedef unsigned long long ull;
+    hipStream_t st = rd->st;
+    const int64_t nm = (int64_t)rd->f.mem.size();
+    BAM_CHK(rd->h_state.ensure(64));
+    ull *hs = rd->h_state.as<ull>();
+    uint64_t kn = 0, kb = 0, repaired = 0;
+    int64_t members = 0;
+    while (!kn) {
+        const int64_t a = rd->next_member;
+        if (a >= nm && rd->carry.empty()) break;
+        int64_t done = a;
+        uint64_t total = 0, n_rec = 0, end = 0, rep = 0;
+        BAM_CHK(bam_span(rd, max_bytes, a, nm, 0, 0, &done, &total, &n_rec, &end, &rep));
+        if (!n_rec && total) { slx_set_error("BAM: '%s' ends inside a record (%llu bytes after the last whole record)", rd->f.path.c_str(), (unsigned long long)total); return SLX_EIO; }
+        rd->next_member = done; members += done - a; repaired += rep;
+        BAM_CHK(bam_take_carry(rd, end, total));
+        BAM_HIPCHK(slx_wait_stream(st));
+        if (!n_rec) break;
+        const uint8_t *s = rd->d_out.as<uint8_t>();
+        const uint64_t *rec = rd->d_rec.as<uint64_t>();
+        for (BamDBuf *b : {&rd->d_keep, &rd->d_blen, &rd->d_kidx, &rd->d_boff}) BAM_CHK(b->ensure(8 * (n_rec + 1)));
+        BAM_CHK(rd->d_fkeep.ensure(n_rec + 8));
+        BAM_CHK(slx_filter_eval_device(rd->flt, rd->device, st, s, rec, n_rec, end, rd->d_fkeep.as<uint8_t>(), nullptr));
+        k_bam_keep_bytes<<<(unsigned)((n_rec + 1 + 255) / 256), 256, 0, st>>>(rd->d_fkeep.as<uint8_t>(), rec, n_rec, 0, rd->d_keep.as<ull>(), rd->d_blen.as<ull>());
+        BAM_HIPCHK(hipGetLastError());
+        size_t tb = 0;
+        BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, rd->d_keep.as<ull>(), rd->d_kidx.as<ull>(), (int)(n_rec + 1), st));
+        BAM_CHK(rd->d_tmp.ensure(tb + 8));
+        BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(rd->d_tmp.p, tb, rd->d_keep.as<ull>(), rd->d_kidx.as<ull>(), (int)(n_rec + 1), st));
+        BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(rd->d_tmp.p, tb, rd->d_blen.as<ull>(), rd->d_boff.as<ull>(), (int)(n_rec + 1), st));
+        BAM_HIPCHK(hipMemcpyAsync(hs + 5, rd->d_kidx.as<ull>() + n_rec, 8, hipMemcpyDeviceToHost, st));
+        BAM_HIPCHK(hipMemcpyAsync(hs + 6, rd->d_boff.as<ull>() + n_rec, 8, hipMemcpyDeviceToHost, st));
+        BAM_HIPCHK(slx_wait_stream(st));
+        kn = hs[5]; kb = hs[6];
+        if (!kn) continue;
+        BAM_CHK(rd->d_cs.ensure(kb + 8)); BAM_CHK(rd->d_cr.ensure(8 * (kn + 1)));
+        k_bam_gather<<<(unsigned)((n_rec + 3) / 4), 256, 0, st>>>(s, rec, n_rec, rd->d_kidx.as<ull>(), rd->d_boff.as<ull>(), rd->d_cs.as<uint8_t>(), rd->d_cr.as<uint64_t>(), 0, 0);
+        BAM_HIPCHK(hipGetLastError());
+        BAM_CHK(rd->h_out.ensure(kb + 8)); BAM_CHK(rd->h_rec.ensure(8 * (kn + 1)));
+        BAM_HIPCHK(hipMemcpyAsync(rd->h_out.p, rd->d_cs.p, kb, hipMemcpyDeviceToHost, st));
+        BAM_HIPCHK(hipMemcpyAsync(rd->h_rec.p, rd->d_cr.p, 8 * (kn + 1), hipMemcpyDeviceToHost, st));
+        BAM_HIPCHK(slx_wait_stream(st));
+    }
+    rd->c_repaired += (int64_t)repaired; rd->c_records += (int64_t)kn;
+    out->n_records = (int64_t)kn; out->n_bytes = (int64_t)kb;
+    out->stream = rd->h_out.as<uint8_t>(); out->rec_off = rd->h_rec.as<uint64_t>();
+    out->d_stream = rd->d_cs.p; out->d_rec_off = rd->d_cr.p;
+    out->n_members = members; out->n_repaired_chunks = (int64_t)repaired;
+    rd->cur_stream = rd->d_cs.p; rd->cur_rec = rd->d_cr.p; rd->map_stream = nullptr;
+    return SLX_OK;
+}
+
+void slx_reader_set_filter(slx_bam *rd, slx_filter *f) { rd->flt = f; }
+
 extern "C" int slx_bam_next(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
 {
     if (!rd || !out) { slx_set_error("slx_bam_next: null argument"); return SLX_EINVAL; }
@@ -931,6 +1007,7 @@ extern "C" int slx_bam_next(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
     BAM_HIPCHK(hipSetDevice(rd->device));
     rd->us[0] = rd->us[1] = rd->us[2] = rd->us[4] = 0;
     if (rd->region_mode) return bam_next_regions(rd, max_bytes, out);
+    if (rd->flt) return bam_next_filtered(rd, max_bytes, out);
     const int64_t nm = (int64_t)rd->f.mem.size();
     const int64_t a = rd->next_member;
     if (a >= nm && rd->carry.empty()) return SLX_OK;

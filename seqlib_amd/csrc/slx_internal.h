@@ -71,3 +71,10 @@ struct slx_bam;
 int slx_aligner_device_of(const slx_aligner *al);          // the device of a single-device aligner; -1 for a group handle
 // the reads slx_bam_reads_device last unpacked for the batch whose d_stream is batch_d_stream: bases, offsets, record of read (all in HBM) and their number; false when there are none
 bool slx_reader_device_reads(const slx_bam *rd, const void *batch_d_stream, const void **d_bases, const void **d_offs, const int64_t **d_rec_of_read, int64_t *n_reads, int *device);
+
+// what the read filter (slx_filter.hip) and the reader (slx_bam.hip) need of each other
+struct slx_filter;
+void slx_reader_set_filter(slx_bam *rd, slx_filter *f);          // nullptr detaches
+// keep bytes of the n_rec records of s[0, n_bytes) (offsets rec, n_rec + 1 of them) into d_keep, all in the HBM of `device`, on `stream` (a hipStream_t), which has
+// drained when the call returns; *n_kept where not null.  SLX_EIO: a record's fields pass its block_size
+int slx_filter_eval_device(slx_filter *f, int device, void *stream, const uint8_t *s, const uint64_t *rec, uint64_t n_rec, uint64_t n_bytes, uint8_t *d_keep, uint64_t *n_kept);
