@@ -135,6 +135,8 @@ void slx_aligner_free(slx_aligner *al);
  *   "cig_lanes" 0|1 (1)       CIGAR jobs with a narrow band (<= 33 columns, query <= 158 bases) run one lane per job (k_cig_lanes); k_cig_dp keeps the others
  *   "first_diag" 0|1 (1)      the top-seed extensions that the diagonal answers run one lane per job (k_first_diag); k_ext_first keeps the dynamic program
  *   "chain_lds" 0|1 (1)       chaining of the light reads with a read's lists in LDS, written to its seed slots once at the end (k_chain_lds); 0: every list in HBM (k_chain)
+ *   "walk_stage" 0|1 (1)      the per-read extension walk (k_extend_reg, reads up to 704 bp) opens its chains from headers made 64 at a time, one chain per lane
+ *                             (window, contig clip, top seed: dev_chain_hdr.h), and walks a one-seed chain from its header alone; 0: every chain by the whole wave
  *   "first_lanes" 0|1 (1)     the other top-seed extensions of the light reads (the dynamic program) one lane per job, binned by work (k_first_lanes); 0: one wave per job (k_ext_first)
  *   "lane_narrow" 0|1 (1)     k_ext_lanes keeps 8-bit H / E cells when no score can reach 256
  *   "p2_coop" 0|1 (1)         seeding pass 2: re-seeding calls inside repeats one wave per call (k_seed2_coop); needs p2_items
@@ -240,7 +242,8 @@ int  slx_aligner_probe_launches(const slx_aligner *al);
  * reads it, never sets it); "regs_deferred" = reads the lane region kernel handed to the wave kernel since the aligner was created;
  * "retries" = chunks run again after an overflow of their work areas since the aligner was created (a steady workload shows 0 after its first call);
  * "chain_lds_reads" / "chain_lds_bail" = reads of the last batch whose chaining finished in LDS / gave the LDS pass up (a 10th chain) and ran again on the HBM columns;
- * "first_lane_jobs" = top-seed extensions of the last batch that k_first_lanes ran (the dynamic program, one lane per job), as the kernel counted them */
+ * "first_lane_jobs" = top-seed extensions of the last batch that k_first_lanes ran (the dynamic program, one lane per job), as the kernel counted them;
+ * "walk_staged_chains" = chains of the last batch that k_extend_reg opened from a lane-made header ("walk_stage"; 0 with the knob off) */
 int64_t slx_aligner_counter(const slx_aligner *al, const char *key);
 
 /* Test hook (per-stage differential tests): intermediate results of one read of the LAST batch, copied out of the device work

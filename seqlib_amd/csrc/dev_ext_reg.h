@@ -14,6 +14,7 @@
 // /root/reference/src/BWAAligner.cpp:104.
 #pragma once
 #include "dev_ext_wave.h"
+#include "dev_chain_hdr.h"
 
 template <int CTRL, int ROW_MASK, int BANK_MASK>
 __device__ __forceinline__ int dpp_get(int identity, int v)
@@ -388,12 +389,25 @@ template <int MAXQ> __device__ __forceinline__ int *dev_long_sort_hist()
 #ifndef EXT_MIN_WAVES
 #define EXT_MIN_WAVES 4
 #endif
+#ifndef WALK_RG_REGIONS
+#define WALK_RG_REGIONS 128   // regions whose covered-test keys the staged walk keeps in LDS (150 bp form; 0 = all in HBM)
+#endif
+struct WalkSeeds {            // a read's seeds by slot, for chain_hdr_make
+    const ReadWS &w;
+    __device__ __forceinline__ int qbeg(int s) const { return w.s_qbeg(s); }
+    __device__ __forceinline__ int len(int s) const { return w.s_len(s); }
+    __device__ __forceinline__ int64_t rbeg(int s) const { return w.s_rbeg[s]; }
+    __device__ __forceinline__ int score(int s) const { return w.s_score ? w.s_score[s] : w.s_len(s); }      // mem_seed_t::score (= length unless the seed filter ran)
+};
 template <int MAXQ>
 __global__ void __launch_bounds__(64, EXT_MIN_WAVES) k_extend_reg(DevRef R, Chunk ck, DevOpt dopt, const int *order, unsigned int *queue, const unsigned int *n_slots, int hi_prio,
                                                                    const int *first = nullptr, const unsigned int *n_first = nullptr,
                                                                    const unsigned int *top_off = nullptr, unsigned int top_cap = 0, const DReg *top_tab = nullptr,
-                                                                   ExtSpec sp = ExtSpec())
+                                                                   ExtSpec sp = ExtSpec(), int walk_stage = 0, unsigned int *n_staged = nullptr)
 {
+    // walk_stage (short reads only): the headers of WALK_HB chains at a time are made one per lane (dev_chain_hdr.h) and left in LDS, so the
+    // dependent loads that open every chain are in flight for 64 chains at once; a one-seed chain is then walked from its header alone.
+    // n_staged counts the chains served from such a header.  0 = every chain opened by the whole wave, as before.
     // top_tab (optional): the region of the top (longest) seed of every kept chain, extended ahead of time one wave per chain by
     // k_ext_first -- top_tab[top_off[r] + chain index] for the reads whose slots lie below top_cap.  What the extension of a seed
     // yields depends on its chain only, so the walk below takes the stored region where it would extend that seed.  For a read from
@@ -410,6 +424,23 @@ __global__ void __launch_bounds__(64, EXT_MIN_WAVES) k_extend_reg(DevRef R, Chun
     // several waves share a CU: a 2 kb contig needs 24 KB, not the 96 KB of an 8 kb one), else in HBM (ck.huge_rows; the row is only ever
     // touched inside the band, a few hundred columns at a time)
     __shared__ int sh_eh_h[MAXQ > 704 ? 1 : MAXQ + 2], sh_eh_e[MAXQ > 704 ? 1 : MAXQ + 2], sh_gap_lut[MAXQ > 704 ? 1 : MAXQ + 2];
+    // chain headers of the staged walk: 64 chains per batch; the 704-column form, whose rows leave 1.7 KB of a wave's 10 KB share of the CU's
+    // LDS, stages 16; the contig form none
+    constexpr int WALK_HB = MAXQ <= 320 ? WAVE : (MAXQ <= 704 ? 16 : 1);
+    __shared__ int64_t sh_h_rmax0[WALK_HB], sh_h_rmax1[WALK_HB], sh_h_toprb[WALK_HB];
+    __shared__ qp_t sh_h_topql[WALK_HB];
+    __shared__ int sh_h_n[WALK_HB], sh_h_first[WALK_HB], sh_h_rid[WALK_HB], sh_h_tops[WALK_HB];
+    // ... and the covered test's keys of the read's first regions (the SoA mirror of w.regs; beyond these the keys are in the hit slots in HBM):
+    // 128 regions for reads up to 160 bp, 64 up to 320 bp, none for the 704-column form
+    constexpr int WALK_RG = MAXQ <= 160 ? WALK_RG_REGIONS : (MAXQ <= 320 ? WALK_RG_REGIONS / 2 : 0);
+    __shared__ int64_t sh_rg_rb[WALK_RG ? WALK_RG : 1], sh_rg_re[WALK_RG ? WALK_RG : 1];
+    __shared__ qp_t sh_rg_q[WALK_RG ? WALK_RG : 1];
+    __shared__ int sh_rg_w[WALK_RG ? WALK_RG : 1], sh_rg_sl0[WALK_RG ? WALK_RG : 1];
+    static_assert(MAXQ > 704 || 3 * (MAXQ + 2) * sizeof(int) + WALK_HB * (3 * sizeof(int64_t) + sizeof(qp_t) + 4 * sizeof(int)) +
+                                    (WALK_RG ? WALK_RG : 1) * (2 * sizeof(int64_t) + sizeof(qp_t) + 2 * sizeof(int)) <= 10240,
+                  "16 one-wave blocks share a CU's 160 KB of LDS");
+    const bool staged = MAXQ <= 704 && walk_stage != 0;
+    unsigned int staged_cnt = 0;
     extern __shared__ int sh_dyn[];
     int *eh_h = sh_eh_h, *eh_e = sh_eh_e, *gap_lut = sh_gap_lut;
     int lut_n = MAXQ + 2;
@@ -473,43 +504,69 @@ __global__ void __launch_bounds__(64, EXT_MIN_WAVES) k_extend_reg(DevRef R, Chun
 #endif
         int64_t *const sd_rb = (int64_t *)(hs + 32 * cap);
         int *const sd_s = w.ib;
+        // the keys of region ri: the staged walk keeps those of the first WALK_RG regions in LDS (and only there)
+        auto rg_keys = [&](int ri, int64_t &prb, int64_t &pre_, qp_t &pq, int &pw, int &psl0) {
+            if (WALK_RG > 0 && staged && ri < WALK_RG) { prb = sh_rg_rb[ri]; pre_ = sh_rg_re[ri]; pq = sh_rg_q[ri]; pw = sh_rg_w[ri]; psl0 = sh_rg_sl0[ri]; }
+            else { prb = rg_rb[ri]; pre_ = rg_re[ri]; pq = rg_q[ri]; pw = rg_w[ri]; psl0 = rg_sl0[ri]; }
+        };
         for (int ci = 0; ci < n_chn && !give_up; ++ci) {
-            const int c = __builtin_amdgcn_readfirstlane(w.ia[ci]);
-            const int n = __builtin_amdgcn_readfirstlane(w.c_n[c]);
-            const int *cs = w.c_w + __builtin_amdgcn_readfirstlane(w.c_first[c]);   // the chain's seeds, flattened by the chaining kernel
-            if (n == 0) continue;
+            int c = 0, n, rid_c = 0;
+            const int *cs;                                          // the chain's seeds, flattened by the chaining kernel
             int64_t rmax0 = l_pac << 1, rmax1 = 0;
-            for (int i = lane; i < n; i += WAVE) {                 // lanes take seeds, then a wave min/max
-                const int s = cs[i];
-                const int qb = w.s_qbeg(s), sl = w.s_len(s);
-                const int64_t b = w.s_rbeg[s] - (qb + max_gap_of(qb));
-                const int64_t e = w.s_rbeg[s] + sl + ((l_query - qb - sl) + max_gap_of(l_query - qb - sl));
-                rmax0 = rmax0 < b ? rmax0 : b;
-                rmax1 = rmax1 > e ? rmax1 : e;
+            bool hdr = false;                                      // this chain's window and top seed come from a lane-made header
+            qp_t top_ql = 0; int64_t top_rb = 0; int top_s = 0;
+            if (staged) {
+                const int bi = ci & (WALK_HB - 1);
+                if (bi == 0) {                                     // the headers of chains ci .. ci + WALK_HB - 1, lane L for chain ci + L
+                    __syncthreads();
+                    if (lane < WALK_HB && ci + lane < n_chn) {
+                        const int cc = w.ia[ci + lane];
+                        const int nn = w.c_n[cc], ff = w.c_first[cc];
+                        ChainHdr h;
+                        const bool made = chain_hdr_make(h, w.c_w + ff, nn, WalkSeeds{w}, max_gap_of, l_query, l_pac, R.n_seqs, R.ann_off, R.ann_len);
+                        sh_h_n[lane] = nn; sh_h_first[lane] = ff; sh_h_rid[lane] = w.c_rid[cc]; sh_h_tops[lane] = made ? h.top_s : -1;
+                        if (made) { sh_h_rmax0[lane] = h.rmax0; sh_h_rmax1[lane] = h.rmax1; sh_h_toprb[lane] = h.top_rbeg; sh_h_topql[lane] = QP_PACK(h.top_qbeg, h.top_len); }
+                    }
+                    __syncthreads();
+                }
+                n = __builtin_amdgcn_readfirstlane(sh_h_n[bi]);
+                cs = w.c_w + __builtin_amdgcn_readfirstlane(sh_h_first[bi]);
+                rid_c = __builtin_amdgcn_readfirstlane(sh_h_rid[bi]);
+                top_s = __builtin_amdgcn_readfirstlane(sh_h_tops[bi]);
+                hdr = top_s >= 0;
+                if (hdr) {
+                    rmax0 = (int64_t)rfl_u64((uint64_t)sh_h_rmax0[bi]); rmax1 = (int64_t)rfl_u64((uint64_t)sh_h_rmax1[bi]);
+                    top_rb = (int64_t)rfl_u64((uint64_t)sh_h_toprb[bi]); top_ql = qp_uniform(sh_h_topql[bi]);
+                    ++staged_cnt;
+                }
+            } else {
+                c = __builtin_amdgcn_readfirstlane(w.ia[ci]);
+                n = __builtin_amdgcn_readfirstlane(w.c_n[c]);
+                cs = w.c_w + __builtin_amdgcn_readfirstlane(w.c_first[c]);
             }
-            for (int d = 32; d >= 1; d >>= 1) {
-                const int64_t o0 = __shfl_xor(rmax0, d, WAVE), o1 = __shfl_xor(rmax1, d, WAVE);
-                rmax0 = rmax0 < o0 ? rmax0 : o0;
-                rmax1 = rmax1 > o1 ? rmax1 : o1;
-            }
-            rmax0 = rmax0 > 0 ? rmax0 : 0;
-            rmax1 = rmax1 < l_pac << 1 ? rmax1 : l_pac << 1;
-            if (rmax0 < l_pac && l_pac < rmax1) {
-                if (w.s_rbeg[cs[0]] < l_pac) rmax1 = l_pac; else rmax0 = l_pac;
-            }
-            {
-                int is_rev;
-                const int rid = dev_pos2rid(R, dev_depos(R, w.s_rbeg[cs[0]], &is_rev));
-                int64_t far_beg = R.ann_off[rid], far_end = far_beg + R.ann_len[rid];
-                if (is_rev) { const int64_t t = far_beg; far_beg = (l_pac << 1) - far_end; far_end = (l_pac << 1) - t; }
-                rmax0 = rmax0 > far_beg ? rmax0 : far_beg;
-                rmax1 = rmax1 < far_end ? rmax1 : far_end;
+            if (n == 0) continue;
+            const bool one = hdr && n == 1;                        // a one-seed chain: no sort, no sorted-seed scratch, seedcov by chain_hdr_seedcov1
+            if (!hdr) {                                            // the window by the whole wave: lanes take seeds, then a wave min / max
+                for (int i = lane; i < n; i += WAVE) {
+                    const int s = cs[i];
+                    const int qb = w.s_qbeg(s), sl = w.s_len(s);
+                    const int64_t b = w.s_rbeg[s] - (qb + max_gap_of(qb));
+                    const int64_t e = w.s_rbeg[s] + sl + ((l_query - qb - sl) + max_gap_of(l_query - qb - sl));
+                    rmax0 = rmax0 < b ? rmax0 : b;
+                    rmax1 = rmax1 > e ? rmax1 : e;
+                }
+                for (int d = 32; d >= 1; d >>= 1) {
+                    const int64_t o0 = __shfl_xor(rmax0, d, WAVE), o1 = __shfl_xor(rmax1, d, WAVE);
+                    rmax0 = rmax0 < o0 ? rmax0 : o0;
+                    rmax1 = rmax1 > o1 ? rmax1 : o1;
+                }
+                (void)chain_hdr_clip(rmax0, rmax1, w.s_rbeg[cs[0]], l_pac, R.n_seqs, R.ann_off, R.ann_len);          // clamps, l_pac rule, contig clip
             }
             // ---- the chain's seeds in the order mem_chain2aln takes them (ascending (length, list index), walked from the top):
             // ranks by an all-pairs count on registers (keys are distinct), records scattered to a sorted SoA scratch
             DBG_T0();
             qp_t my_ql = 0; int64_t my_rb = 0; int my_rank = -1;   // n <= 64: this lane's seed and its rank, for the batch test below
-            if (n <= WAVE) {                                       // the common case: keys never leave the registers
+            if (!one && n <= WAVE) {                               // the common case: keys never leave the registers (one seed: it is the header's top seed)
                 const bool mine = lane < n;
                 const int sid = mine ? cs[lane] : 0;
                 const qp_t ql = mine ? w.s_ql[sid] : (qp_t)0;
@@ -523,7 +580,7 @@ __global__ void __launch_bounds__(64, EXT_MIN_WAVES) k_extend_reg(DevRef R, Chun
                     rank += kj < key ? 1 : 0;
                 }
                 if (mine) { sd_ql[rank] = ql; sd_rb[rank] = rb; sd_s[rank] = sid; my_ql = ql; my_rb = rb; my_rank = rank; }
-            } else if (dev_long_sort<MAXQ>(n)) {
+            } else if (!one && dev_long_sort<MAXQ>(n)) {
                 // contigs: a chain of thousands of seeds.  The all-pairs count below is quadratic (a third of the walk's time for a 7 000-seed
                 // chain); the keys are (score, list index) and the scores of all but a few seeds are small integers, so: a counting sort by
                 // score -- histogram in LDS, exclusive scan, placement in index order (stable: the position among the equal scores of a block of
@@ -594,7 +651,7 @@ __global__ void __launch_bounds__(64, EXT_MIN_WAVES) k_extend_reg(DevRef R, Chun
                         sd_ql[rank] = w.s_ql[sid]; sd_rb[rank] = w.s_rbeg[sid]; sd_s[rank] = sid;
                     }
                 }
-            } else {
+            } else if (!one) {
                 for (int i = lane; i < n; i += WAVE) w.srt[i] = (uint64_t)(uint32_t)(w.s_score ? w.s_score[cs[i]] : w.s_len(cs[i])) << 32 | (uint64_t)i;
                 __threadfence_block();                                 // other lanes read these keys below
                 for (int i0 = 0; i0 < n; i0 += WAVE) {
@@ -617,7 +674,7 @@ __global__ void __launch_bounds__(64, EXT_MIN_WAVES) k_extend_reg(DevRef R, Chun
                     if (mine) { sd_ql[rank] = ql; sd_rb[rank] = rb; sd_s[rank] = sid; }
                 }
             }
-            __threadfence_block();
+            if (!one) __threadfence_block();
             DBG_T1(t_sort);
             bool top_kept = false;                                 // was the chain's first (longest) seed extended?
             [[maybe_unused]] int n_ext = 0;                        // contigs: sorted positions of the seeds of this chain taken so far, in w.ic[]
@@ -635,9 +692,8 @@ __global__ void __launch_bounds__(64, EXT_MIN_WAVES) k_extend_reg(DevRef R, Chun
                         const int q0 = QP_HI(my_ql), l0 = QP_LO(my_ql);
                         bool cov = false;
                         for (int ri = 0; ri < n_av; ++ri) {
-                            const int64_t prb = rg_rb[ri], pre_ = rg_re[ri];
-                            const qp_t pq = rg_q[ri];
-                            const int pw = rg_w[ri], psl0 = rg_sl0[ri];
+                            int64_t prb, pre_; qp_t pq; int pw, psl0;
+                            rg_keys(ri, prb, pre_, pq, pw, psl0);
                             const int pqb = QP_HI(pq), pqe = QP_LO(pq);
                             if (!(my_rb < prb || my_rb + l0 > pre_ || q0 < pqb || q0 + l0 > pqe) && !((double)(l0 - psl0) > .1 * l_query)) {
                                 int qd = q0 - pqb; int64_t rd = my_rb - prb;
@@ -662,10 +718,9 @@ __global__ void __launch_bounds__(64, EXT_MIN_WAVES) k_extend_reg(DevRef R, Chun
                     }
                     if (__ballot(fail) == 0) { DBG_T1(t_test); break; }
                 }
-                const qp_t s_ql = qp_uniform(sd_ql[k]);
-                const int s = __builtin_amdgcn_readfirstlane(sd_s[k]);
+                qp_t s_ql = top_ql; int s = top_s; int64_t s_rbeg = top_rb;
+                if (!one) { s_ql = qp_uniform(sd_ql[k]); s = __builtin_amdgcn_readfirstlane(sd_s[k]); s_rbeg = (int64_t)rfl_u64((uint64_t)sd_rb[k]); }
                 const int s_qbeg = QP_HI(s_ql), s_len = QP_LO(s_ql);
-                const int64_t s_rbeg = (int64_t)rfl_u64((uint64_t)sd_rb[k]);
                 // "has this seed been covered by an earlier region?": only whether ANY region passes the test matters, so lanes
                 // evaluate 64 regions each, four blocks of key loads in flight at a time
                 bool covered = false;
@@ -683,9 +738,8 @@ __global__ void __launch_bounds__(64, EXT_MIN_WAVES) k_extend_reg(DevRef R, Chun
                         const int ri0 = base + u * WAVE + lane;
                         const bool valid = ri0 < n_av;
                         const int ri = valid ? ri0 : n_av - 1;
-                        const int64_t prb = rg_rb[ri], pre_ = rg_re[ri];
-                        const qp_t pq = rg_q[ri];
-                        const int pw = rg_w[ri], psl0 = rg_sl0[ri];
+                        int64_t prb, pre_; qp_t pq; int pw, psl0;
+                        rg_keys(ri, prb, pre_, pq, pw, psl0);
                         const int pqb = QP_HI(pq), pqe = QP_LO(pq);
                         if (valid && !(s_rbeg < prb || s_rbeg + s_len > pre_ || s_qbeg < pqb || s_qbeg + s_len > pqe) &&
                             !((double)(s_len - psl0) > .1 * l_query)) {
@@ -725,7 +779,7 @@ __global__ void __launch_bounds__(64, EXT_MIN_WAVES) k_extend_reg(DevRef R, Chun
                         }
                         if (__ballot(hit)) other_diag = true;
                     }
-                    if (!other_diag) { sd_ql[k] = QP_KEEP_HI(s_ql); DBG_T1(t_test); continue; }      // every lane stores the same word
+                    if (!other_diag) { if (!one) sd_ql[k] = QP_KEEP_HI(s_ql); DBG_T1(t_test); continue; }      // every lane stores the same word (one seed: nobody reads it)
                 }
                 DBG_T1(t_test);
                 DBG_T0();
@@ -769,24 +823,32 @@ __global__ void __launch_bounds__(64, EXT_MIN_WAVES) k_extend_reg(DevRef R, Chun
                                 a.w = opt.w; a.seedlen0 = s_len; a.score = a.truesc = 0; a.rid = w.c_rid[c];
                                 a.sub = a.csub = a.sub_n = 0; a.seedcov = 0; a.secondary = 0; a.n_comp = 0; a.hash = 0; a.frac_rep = frac_rep;
                             }
-                        } else a = dev_extend_core<NCH>(R, opt, mr, query, l_query, s_qbeg, s_len, s_rbeg, rmax0, rmax1, w.c_rid[c], frac_rep, eh_h, eh_e, lane);
+                        } else a = dev_extend_core<NCH>(R, opt, mr, query, l_query, s_qbeg, s_len, s_rbeg, rmax0, rmax1, staged ? rid_c : w.c_rid[c], frac_rep, eh_h, eh_e, lane);
                     }
-                    else a = dev_extend_core<NCH>(R, opt, mr, query, l_query, s_qbeg, s_len, s_rbeg, rmax0, rmax1, w.c_rid[c], frac_rep, eh_h, eh_e, lane);
-                    int cov = 0;
-                    for (int i = lane; i < n; i += WAVE) {
-                        const qp_t tq = w.s_ql[cs[i]];
-                        const int t_qbeg = QP_HI(tq), t_len = QP_LO(tq);
-                        const int64_t t_rbeg = w.s_rbeg[cs[i]];
-                        if (t_qbeg >= a.qb && t_qbeg + t_len <= a.qe && t_rbeg >= a.rb && t_rbeg + t_len <= a.re) cov += t_len;
+                    else a = dev_extend_core<NCH>(R, opt, mr, query, l_query, s_qbeg, s_len, s_rbeg, rmax0, rmax1, staged ? rid_c : w.c_rid[c], frac_rep, eh_h, eh_e, lane);
+                    if (one) a.seedcov = chain_hdr_seedcov1(s_qbeg, s_len, s_rbeg, a.qb, a.qe, a.rb, a.re);
+                    else {
+                        int cov = 0;
+                        for (int i = lane; i < n; i += WAVE) {
+                            const qp_t tq = w.s_ql[cs[i]];
+                            const int t_qbeg = QP_HI(tq), t_len = QP_LO(tq);
+                            const int64_t t_rbeg = w.s_rbeg[cs[i]];
+                            if (t_qbeg >= a.qb && t_qbeg + t_len <= a.qe && t_rbeg >= a.rb && t_rbeg + t_len <= a.re) cov += t_len;
+                        }
+                        for (int d = 32; d >= 1; d >>= 1) cov += __shfl_xor(cov, d, WAVE);
+                        a.seedcov = cov;
                     }
-                    for (int d = 32; d >= 1; d >>= 1) cov += __shfl_xor(cov, d, WAVE);
-                    a.seedcov = cov;
                 }
                 if (k == n - 1) top_kept = true;
                 if constexpr (MAXQ > 704) w.ic[n_ext++] = k;
                 // every lane stores the same bytes (region + its keys for the covered test), so every lane may read them back
                 w.regs[n_av] = a;
+                if (WALK_RG > 0 && staged && n_av < WALK_RG) {
+                    if (lane == 0) { sh_rg_rb[n_av] = a.rb; sh_rg_re[n_av] = a.re; sh_rg_q[n_av] = QP_PACK(a.qb, a.qe); sh_rg_w[n_av] = a.w; sh_rg_sl0[n_av] = a.seedlen0; }
+                    __syncthreads();                               // the other lanes read them in the next covered test
+                } else {
                 rg_rb[n_av] = a.rb; rg_re[n_av] = a.re; rg_q[n_av] = QP_PACK(a.qb, a.qe); rg_w[n_av] = a.w; rg_sl0[n_av] = a.seedlen0;
+                }
                 ++n_av;
                 DBG_T1(t_dp);
             }
@@ -805,6 +867,7 @@ __global__ void __launch_bounds__(64, EXT_MIN_WAVES) k_extend_reg(DevRef R, Chun
 #undef DBG_T0
 #undef DBG_T1
     }
+    if (n_staged && staged_cnt && lane == 0) atomicAdd(n_staged, staged_cnt);
 }
 
 

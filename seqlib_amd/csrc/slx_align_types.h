@@ -55,7 +55,7 @@ struct DevBuf {
 // The host sizes every stage by a few counters of the one before.  Each used to come back with a hipMemcpyAsync of its own into a pageable local -- five after
 // seeding, three before the compaction: ~20 us apiece, a third of a one-read call.  k_mail gathers them with ONE launch and writes them straight into pinned
 // host memory the worker keeps (the stream's synchronisation, which the host needs anyway, makes them visible): no copy at all.
-#define SLX_MAIL_PARTS 8            // (the largest user, the end of run_chunk, fills seven)
+#define SLX_MAIL_PARTS 8            // (the largest user, the end of run_chunk, fills all eight)
 struct MailSpec { const unsigned int *src[SLX_MAIL_PARTS]; int words[SLX_MAIL_PARTS]; int n; };
 static __global__ void k_mail(MailSpec s, unsigned int *dst)
 {
@@ -99,6 +99,7 @@ struct Worker {
     unsigned long long chain_stat[2] = {0, 0};                                     // reads k_chain_lds started over on the HBM columns / reads it finished in LDS, of the last batch
     unsigned long long first_stat = 0;                                             // k_first_lanes: DP jobs it counted as run, of the last batch
     bool first_lanes_ran = false;                                                  // ... the chunk in flight took that path
+    unsigned long long walk_stat = 0;                                              // k_extend_reg: chains it served from a lane-made header, of the last batch
     unsigned int pseg_stat = 0;                                                    // ... how many
     unsigned int gseg_stat[3] = {0, 0, 0};                                         // ... segments taken as speculated / run again / jobs cut
     unsigned int xseg_stat[4] = {0, 0, 0, 0};                                      // ... segments taken as speculated / computed again / second band tries / sides cut, summed over this worker's launches
@@ -227,6 +228,7 @@ struct slx_aligner {
     int p2_coop = 1;              // ... 1 = calls inside repeats (long work lists) one WAVE per call (k_seed2_coop)
     int p2_items_cap = 0;         // test hook: capacity of the item list (0 = one per read of the chunk); reads whose items do not fit are walked whole
     int top_reuse = 1;            // 1 = k_extend_reg takes top-seed regions from that table (heavy reads, and light reads it redoes) instead of extending in place
+    int walk_stage = 1;           // 1 = k_extend_reg (short reads) opens its chains from headers made 64 at a time, one per lane (dev_chain_hdr.h); 0 = chain by chain on the whole wave
     int seed_free_cus = 0;        // see "seed_free_cus" in slx_aligner_set
     int stream_prio = 0;
     int n_workers = 3;            // concurrent parts of a large batch

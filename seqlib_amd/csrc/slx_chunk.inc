@@ -304,7 +304,7 @@ static void launch_tail(slx_aligner *al, Worker *wk, const Chunk &ck, const DevO
     const int g = std::max(1, std::min(n, ck.huge_rows ? HUGE_BLOCKS : al->n_cu * 32));
     const unsigned ext_smem = (MAXQ > 704 && !ck.huge_rows) ? (unsigned)(3 * ck.long_stride * 4) : 0u;
     if (ext_heavy) hipLaunchKernelGGL(k_extend_reg<MAXQ>, dim3(g), dim3(64), ext_smem, st, al->ref, ck, dopt, ext_light, q + 1, ext_slots ? ext_slots : n_slots, 0,
-                                      ext_heavy, n_heavy, top_off, top_cap, top_tab);
+                                      ext_heavy, n_heavy, top_off, top_cap, top_tab, ExtSpec(), al->walk_stage, q + 55);
     else {
         bool in_rounds = false;
         if constexpr (MAXQ > 704) {
@@ -360,7 +360,7 @@ static void launch_tail(slx_aligner *al, Worker *wk, const Chunk &ck, const DevO
         }
         if (!in_rounds)
             hipLaunchKernelGGL(k_extend_reg<MAXQ>, dim3(g), dim3(64), ext_smem, st, al->ref, ck, dopt, (const int *)nullptr, q + 1, n_slots, 0, (const int *)nullptr,
-                               (const unsigned int *)nullptr, top_off, top_cap, top_tab);
+                               (const unsigned int *)nullptr, top_off, top_cap, top_tab, ExtSpec(), al->walk_stage, q + 55);
     }
 #ifdef EXT_STATS
     ext_stats_print(st, "extend_reg", n, nullptr);
@@ -1042,25 +1042,39 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
         HIPCHK(hipcub::DeviceScan::ExclusiveSum(wk->scan_tmp.p, tb2, wk->cig_cnt.as<unsigned long long>(), wk->cig_off_c.as<unsigned long long>(), n + 1, st));
     }
     unsigned long long Hc = 0, Cc = 0;
+    // the counters the host reads after the chunk, in one launch: every part gets its place in h_mail where it is added, so no reader counts words by hand
+    int m_hits, m_cig, m_flags, m_defer, m_big, m_chain, m_walk, m_first = -1;
     {
         MailSpec ms{};
-        ms.src[0] = (const unsigned int *)(wk->hit_off_c.as<unsigned long long>() + n); ms.words[0] = 2;
-        ms.src[1] = (const unsigned int *)(wk->cig_off_c.as<unsigned long long>() + n); ms.words[1] = 2;
-        ms.src[2] = (const unsigned int *)ck.flags; ms.words[2] = 1;
-        ms.src[3] = wk->queues.as<unsigned int>() + 46; ms.words[3] = 1;          // reads k_regs deferred to the wave kernel
-        ms.src[4] = wk->queues.as<unsigned int>() + 48; ms.words[4] = 1;          // reads k_hits left to k_hits_wave
-        ms.src[5] = wk->queues.as<unsigned int>() + 50; ms.words[5] = 2;          // reads k_chain_lds started over on the HBM columns, reads it finished in LDS
-        ms.n = 6;
-        if (wk->first_lanes_ran) { ms.src[6] = wk->queues.as<unsigned int>() + 54; ms.words[6] = 1; ms.n = 7; }          // jobs k_first_lanes counted as run
+        int at = 0;
+        auto part = [&](const unsigned int *src, int words) {
+            if (ms.n >= SLX_MAIL_PARTS || at + words > 64) return -1;          // (h_mail holds 64 words)
+            ms.src[ms.n] = src; ms.words[ms.n] = words; ++ms.n;
+            at += words;
+            return at - words;
+        };
+        m_hits = part((const unsigned int *)(wk->hit_off_c.as<unsigned long long>() + n), 2);
+        m_cig = part((const unsigned int *)(wk->cig_off_c.as<unsigned long long>() + n), 2);
+        m_flags = part((const unsigned int *)ck.flags, 1);
+        m_defer = part(wk->queues.as<unsigned int>() + 46, 1);          // reads k_regs deferred to the wave kernel
+        m_big = part(wk->queues.as<unsigned int>() + 48, 1);            // reads k_hits left to k_hits_wave
+        m_chain = part(wk->queues.as<unsigned int>() + 50, 2);          // reads k_chain_lds started over on the HBM columns, reads it finished in LDS
+        m_walk = part(wk->queues.as<unsigned int>() + 55, 1);           // chains k_extend_reg opened from a lane-made header
+        if (wk->first_lanes_ran) m_first = part(wk->queues.as<unsigned int>() + 54, 1);          // jobs k_first_lanes counted as run
+        if (m_hits < 0 || m_cig < 0 || m_flags < 0 || m_defer < 0 || m_big < 0 || m_chain < 0 || m_walk < 0 || (wk->first_lanes_ran && m_first < 0)) {
+            slx_set_error("run_chunk: more counters than k_mail has parts (SLX_MAIL_PARTS)");
+            return SLX_EINTERNAL;
+        }
         hipLaunchKernelGGL(k_mail, dim3(1), dim3(64), 0, st, ms, wk->h_mail);
     }
     HIPCHK(slx_wait_stream(st));
-    memcpy(&Hc, wk->h_mail, 8); memcpy(&Cc, wk->h_mail + 2, 8);
-    const uint32_t fl = wk->h_mail[4];
-    wk->fin_stat[0] += wk->h_mail[5]; wk->fin_stat[1] += wk->h_mail[6];
+    memcpy(&Hc, wk->h_mail + m_hits, 8); memcpy(&Cc, wk->h_mail + m_cig, 8);
+    const uint32_t fl = wk->h_mail[m_flags];
+    wk->fin_stat[0] += wk->h_mail[m_defer]; wk->fin_stat[1] += wk->h_mail[m_big];
     if (fl) { *flags_out = fl; return SLX_OK; }
-    wk->chain_stat[0] += wk->h_mail[7]; wk->chain_stat[1] += wk->h_mail[8];
-    if (wk->first_lanes_ran) wk->first_stat += wk->h_mail[9];
+    wk->chain_stat[0] += wk->h_mail[m_chain]; wk->chain_stat[1] += wk->h_mail[m_chain + 1];
+    wk->walk_stat += wk->h_mail[m_walk];
+    if (m_first >= 0) wk->first_stat += wk->h_mail[m_first];
     // grow the outputs and compact
     const size_t H = (size_t)*hit_base + Hc, C = (size_t)*cig_base + Cc;
 #define GROW(buf, bytes, keep) if ((rc = wk->buf.grow((size_t)(bytes), (size_t)(keep), st)) != SLX_OK) return rc
