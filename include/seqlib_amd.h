@@ -137,6 +137,10 @@ void slx_aligner_free(slx_aligner *al);
  *   "chain_lds" 0|1 (1)       chaining of the light reads with a read's lists in LDS, written to its seed slots once at the end (k_chain_lds); 0: every list in HBM (k_chain)
  *   "walk_stage" 0|1 (1)      the per-read extension walk (k_extend_reg, reads up to 704 bp) opens its chains from headers made 64 at a time, one chain per lane
  *                             (window, contig clip, top seed: dev_chain_hdr.h), and walks a one-seed chain from its header alone; 0: every chain by the whole wave
+ *   "ext_row_exit" 0|1 (1)    the short-read extension loops (k_extend_reg, k_extend_cand, k_ext_first; k_ext_lanes, k_first_lanes) end a dynamic program after a row whose
+ *                             maximum, with every remaining query column a match, can no longer change the score, the band trials' max_off or which end of the
+ *                             alignment (local, or to the query's end) the region takes; only where the band never clips the row (band + 1 >= query length).
+ *                             Same records; 0: the loops run to z-drop, an all-zero row or the tail bound
  *   "first_lanes" 0|1 (1)     the other top-seed extensions of the light reads (the dynamic program) one lane per job, binned by work (k_first_lanes); 0: one wave per job (k_ext_first)
  *   "lane_narrow" 0|1 (1)     k_ext_lanes keeps 8-bit H / E cells when no score can reach 256
  *   "p2_coop" 0|1 (1)         seeding pass 2: re-seeding calls inside repeats one wave per call (k_seed2_coop); needs p2_items
@@ -243,7 +247,8 @@ int  slx_aligner_probe_launches(const slx_aligner *al);
  * "retries" = chunks run again after an overflow of their work areas since the aligner was created (a steady workload shows 0 after its first call);
  * "chain_lds_reads" / "chain_lds_bail" = reads of the last batch whose chaining finished in LDS / gave the LDS pass up (a 10th chain) and ran again on the HBM columns;
  * "first_lane_jobs" = top-seed extensions of the last batch that k_first_lanes ran (the dynamic program, one lane per job), as the kernel counted them;
- * "walk_staged_chains" = chains of the last batch that k_extend_reg opened from a lane-made header ("walk_stage"; 0 with the knob off) */
+ * "walk_staged_chains" = chains of the last batch that k_extend_reg opened from a lane-made header ("walk_stage"; 0 with the knob off);
+ * "ext_row_exits" = dynamic programs of the last batch's short-read extension kernels (band trials, in the lane kernels) that the row exit ended ("ext_row_exit"; 0 with the knob off) */
 int64_t slx_aligner_counter(const slx_aligner *al, const char *key);
 
 /* Test hook (per-stage differential tests): intermediate results of one read of the LAST batch, copied out of the device work

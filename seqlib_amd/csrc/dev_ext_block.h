@@ -312,7 +312,8 @@ __device__ ExtResult block_extend_side(int qlen, QF qf, int tlen, TF tf, const s
     if (fits && XB_THREADS < 256 && 2 * w + 2 <= 4 * XB_THREADS) return block_ksw_extend2_band<4>(qlen, qf, tlen, tf, o, mr, w, h0, amax, S);
     __syncthreads();
     if (threadIdx.x < WAVE) {
-        const ExtResult r = reg_ksw_extend2_auto<0>(qlen, qf, tlen, tf, o, mr, w_in, end_bonus, h0, eh_h, eh_e, (int)threadIdx.x);
+        unsigned int no_exit = 0;                                      // (the block kernels run without the row exit)
+        const ExtResult r = reg_ksw_extend2_auto<0>(qlen, qf, tlen, tf, o, mr, w_in, end_bonus, h0, eh_h, eh_e, (int)threadIdx.x, EXT_ROW_EXIT_OFF, no_exit);
         if (threadIdx.x == 0) S.res = r;
     }
     __syncthreads();

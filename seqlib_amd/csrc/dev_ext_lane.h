@@ -35,10 +35,19 @@ struct LaneBases {              // lane_rows_extend's bases: the read's codes, t
     __device__ __forceinline__ int t(int64_t p) { return text_at(R, p, rw); }
 };
 
+// the lanes' counts of trials the row exit ended, summed over the wave: one atomic per wave ("ext_row_exits")
+__device__ __forceinline__ void lane_exits_add(unsigned int *dst, unsigned int mine, int lane)
+{
+    const unsigned int sum = (unsigned int)__builtin_amdgcn_readlane(dpp_incl_add_scan((int)mine), WAVE - 1);
+    if (dst && sum && lane == 0) atomicAdd(dst, sum);
+}
+
 // dev_extend_core, one seed per lane (the same statements; both sides and both band trials run in lane_rows_extend's one row loop)
+// row_exit: non-zero = the RELAXED row exit, which is enough here for the reason given at dev_extend_core: `done` below reads gscore / gtle only in
+// the branch the rule keeps.  n_exit: this lane's band trials the exit ended.
 template <typename L>
 __device__ DReg lane_extend_core(const DevRef &R, const slx_opt &opt, const MatRows &mr, const uint8_t *query, int l_query, int s_qbeg, int s_len,
-                                 int64_t s_rbeg, int64_t rmax0, int64_t rmax1, int rid, float frac_rep, L &eh)
+                                 int64_t s_rbeg, int64_t rmax0, int64_t rmax1, int rid, float frac_rep, L &eh, int row_exit, unsigned int &n_exit)
 {
     DReg a;
     a.rb = a.re = 0; a.qb = a.qe = 0; a.sub = a.csub = a.sub_n = 0; a.seedcov = 0; a.secondary = 0;
@@ -66,7 +75,7 @@ __device__ DReg lane_extend_core(const DevRef &R, const slx_opt &opt, const MatR
             if (er.gscore <= 0 || er.gscore <= a.score - opt.pen_clip3) { a.qe = qe + er.qle; a.re = re0 + er.tle; a.truesc += a.score - sc0; }
             else { a.qe = l_query; a.re = re0 + er.gtle; a.truesc += er.gscore - sc0; }
         }
-    });
+    }, row_exit ? EXT_ROW_EXIT_RELAXED : EXT_ROW_EXIT_OFF, &n_exit);
     a.w = aw0 > aw1 ? aw0 : aw1;
     a.seedlen0 = s_len;
     a.frac_rep = frac_rep;
@@ -156,6 +165,7 @@ __global__ void __launch_bounds__(64) k_ext_lanes(DevRef R, Chunk ck, DevOpt dop
     row.init(lane_lds, cols, lane);
     const unsigned int nh = (unsigned int)__builtin_amdgcn_readfirstlane((int)*n_heavy);
     const unsigned int n_jobs = nh ? (unsigned int)__builtin_amdgcn_readfirstlane((int)job_off[nh]) : 0u;
+    unsigned int exit_cnt = 0;                       // this lane's band trials the row exit ended
     for (;;) {
         const unsigned int base = wave_take(queue, (unsigned int)WAVE);
         if (base >= n_jobs) break;
@@ -163,7 +173,7 @@ __global__ void __launch_bounds__(64) k_ext_lanes(DevRef R, Chunk ck, DevOpt dop
         if (job < n_jobs) {
             const LaneJob j = jobs[job];
             const uint8_t *query = ck.codes + j.q_off;
-            DReg a = lane_extend_core<L>(R, opt, mr, query, j.l_query, j.s_qbeg, j.s_len, j.s_rbeg, j.rmax0, j.rmax1, j.rid, j.frac_rep, row);
+            DReg a = lane_extend_core<L>(R, opt, mr, query, j.l_query, j.s_qbeg, j.s_len, j.s_rbeg, j.rmax0, j.rmax1, j.rid, j.frac_rep, row, ck.ext_row_exit, exit_cnt);
             // seedcov: the chain's seeds that lie inside the region
             const ReadWS w = make_ws(ck, j.r);
             const int n = w.c_n[j.c];
@@ -179,6 +189,7 @@ __global__ void __launch_bounds__(64) k_ext_lanes(DevRef R, Chunk ck, DevOpt dop
             cand[j.out] = a;
         }
     }
+    lane_exits_add(ck.ext_exits, exit_cnt, lane);
 }
 
 // ---------------------------------------------------------------------------------------------- light reads: the top-seed extensions that need the dynamic program, one lane per job
@@ -239,6 +250,7 @@ __global__ void __launch_bounds__(64) k_first_lanes(DevRef R, Chunk ck, DevOpt d
     L row;
     row.init(lane_lds, cols, lane);
     const unsigned int n_jobs = (unsigned int)__builtin_amdgcn_readfirstlane((int)*n_list);
+    unsigned int exit_cnt = 0;                       // this lane's band trials the row exit ended
     for (;;) {
         const unsigned int base = wave_take(queue, (unsigned int)WAVE);
         if (base >= n_jobs) break;
@@ -246,11 +258,12 @@ __global__ void __launch_bounds__(64) k_first_lanes(DevRef R, Chunk ck, DevOpt d
         if (t < n_jobs) {
             const unsigned int job = list[t];
             const FirstJob j = jobs[job];
-            const DReg a = lane_extend_core<L>(R, opt, mr, ck.codes + j.q_off, j.l_query, j.s_qbeg, j.s_len, j.s_rbeg, j.rmax0, j.rmax1, j.rid, j.frac_rep, row);
+            const DReg a = lane_extend_core<L>(R, opt, mr, ck.codes + j.q_off, j.l_query, j.s_qbeg, j.s_len, j.s_rbeg, j.rmax0, j.rmax1, j.rid, j.frac_rep, row, ck.ext_row_exit, exit_cnt);
             first[job] = a;                              // seedcov is filled in by k_ext_replay
         }
         if (lane == 0) atomicAdd(n_ran, n_jobs - base < (unsigned int)WAVE ? n_jobs - base : (unsigned int)WAVE);      // jobs this wave has run ("first_lane_jobs")
     }
+    lane_exits_add(ck.ext_exits, exit_cnt, lane);
 }
 
 // ---------------------------------------------------------------------------------------------- light reads: the diagonal, one lane per job

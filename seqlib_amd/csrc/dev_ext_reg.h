@@ -94,8 +94,11 @@ __device__ __forceinline__ MatCols make_matcols(const int8_t *mat)
 // quantities are non-negative, so both wave scans are six unsigned-max DPP steps; the row maximum travels as (h << 10 | column),
 // whose maximum is the scalar loop's LAST arg-max.  F at the first column of the band comes out <= 0 instead of 0, which
 // cannot change h because E >= 0.  Cells outside [beg, end] keep their stale registers exactly like eh[] does.
+// row_exit (EXT_ROW_EXIT_*, dev_lane_rows.h): end the loop after a row that rules out any change ("the row exit", dev_ext_wave.h); n_exit counts the
+// calls it ended.  Everything the test reads is scalar: a few SALU instructions per row.
 template <int CPL, typename QF, typename TF>
-__device__ ExtResult reg_ksw_extend2(int qlen_, QF qf, int tlen_, TF tf, const slx_opt &o, const MatRows &mr, int w_, int end_bonus_, int h0_, int lane)
+__device__ ExtResult reg_ksw_extend2(int qlen_, QF qf, int tlen_, TF tf, const slx_opt &o, const MatRows &mr, int w_, int end_bonus_, int h0_, int lane,
+                                     int row_exit, unsigned int &n_exit)
 {
     // every lane passes the same job: pin the job parameters to scalar registers so that the band / maximum / z-drop
     // bookkeeping below is scalar code instead of 64 identical vector lanes
@@ -129,6 +132,9 @@ __device__ ExtResult reg_ksw_extend2(int qlen_, QF qf, int tlen_, TF tf, const s
     w = w < max_del ? w : max_del;
     w = __builtin_amdgcn_readfirstlane(w);                       // the f64 divisions above run on the vector unit
     const int tail_top = ext_tail_bound0(o, qlen, h0, max);
+    const int apos = max > 0 ? max : 0;
+    const bool exit_ok = __builtin_amdgcn_readfirstlane(row_exit) != EXT_ROW_EXIT_OFF && ext_row_exit_ok(o, qlen, w, h0);
+    const int exit_bonus = __builtin_amdgcn_readfirstlane(row_exit) == EXT_ROW_EXIT_RELAXED ? end_bonus : -1;
     max = h0;
     int max_i = -1, max_j = -1, max_ie = -1, gscore = -1, max_off = 0, beg = 0, end = qlen;
     // target bases are fetched 64 rows at a time (lane t holds row i0+t) one block ahead, then read with v_readlane
@@ -247,6 +253,9 @@ __device__ ExtResult reg_ksw_extend2(int qlen_, QF qf, int tlen_, TF tf, const s
         const int jl = last_nz >= nbeg ? last_nz : nbeg - 1;
         beg = nbeg;
         end = jl + 2 < qlen ? jl + 2 : qlen;
+        // ---- the row exit: no later row can change what is reported.  (beg == 0 now means the band began at column 0 in this row too: h1_init is
+        // column -1 as the next row reads it)
+        if (exit_ok && ext_row_done(ext_row_bound(m, beg == 0 ? h1_init : 0, apos, qlen, beg, tlen, i), max, gscore, exit_bonus)) { ++n_exit; break; }
     }
     ExtResult r;
     r.score = max; r.qle = max_j + 1; r.tle = max_i + 1; r.gtle = max_ie + 1; r.gscore = gscore; r.max_off = max_off;
@@ -312,7 +321,7 @@ __device__ __forceinline__ bool diag_extend(int qlen_, QF qf, int tlen_, TF tf, 
 // of their widest extensions in LDS instead (wave_ksw_extend2): more than three columns per lane would spill.
 template <int NCH, typename QF, typename TF>
 __device__ __forceinline__ ExtResult reg_ksw_extend2_auto(int qlen, QF qf, int tlen, TF tf, const slx_opt &o, const MatRows &mr, int w, int end_bonus,
-                                                          int h0, int *eh_h, int *eh_e, int lane)
+                                                          int h0, int *eh_h, int *eh_e, int lane, int row_exit, unsigned int &n_exit)
 {
     {
         ExtResult d;
@@ -322,18 +331,23 @@ __device__ __forceinline__ ExtResult reg_ksw_extend2_auto(int qlen, QF qf, int t
 #endif
         if (dg) return d;
     }
-    if (qlen + 1 <= WAVE) return reg_ksw_extend2<1>(qlen, qf, tlen, tf, o, mr, w, end_bonus, h0, lane);
-    if (qlen + 1 <= 2 * WAVE) return reg_ksw_extend2<2>(qlen, qf, tlen, tf, o, mr, w, end_bonus, h0, lane);
-    if (qlen + 1 <= 3 * WAVE) return reg_ksw_extend2<3>(qlen, qf, tlen, tf, o, mr, w, end_bonus, h0, lane);
+    if (qlen + 1 <= WAVE) return reg_ksw_extend2<1>(qlen, qf, tlen, tf, o, mr, w, end_bonus, h0, lane, row_exit, n_exit);
+    if (qlen + 1 <= 2 * WAVE) return reg_ksw_extend2<2>(qlen, qf, tlen, tf, o, mr, w, end_bonus, h0, lane, row_exit, n_exit);
+    if (qlen + 1 <= 3 * WAVE) return reg_ksw_extend2<3>(qlen, qf, tlen, tf, o, mr, w, end_bonus, h0, lane, row_exit, n_exit);
     return wave_ksw_extend2<NCH>(qlen, qf, tlen, tf, o, mr, w, end_bonus, h0, eh_h, eh_e, lane);
 }
 
 // Left + right extension of one seed (the body of mem_chain2aln's seed loop once a seed is known to need extending): the region
 // without its seedcov.  Shared by the per-read kernel and the ahead-of-time kernel for heavy reads.
+// row_exit: 0, or non-zero for the RELAXED row exit.  That rule keeps score, qle, tle and max_off -- what the band trials below read -- and the branch
+// of `er.gscore <= 0 || er.gscore <= a.score - pen_clip` taken below with the fields that branch reads; gscore / gtle may differ from ksw_extend2's
+// only where the first branch is taken, which reads neither.  n_exit: calls of the dynamic program the exit ended.
 template <int NCH>
 __device__ DReg dev_extend_core(const DevRef &R, const slx_opt &opt, const MatRows &mr, const uint8_t *query, int l_query, int s_qbeg, int s_len,
-                                int64_t s_rbeg, int64_t rmax0, int64_t rmax1, int rid, float frac_rep, int *eh_h, int *eh_e, int lane)
+                                int64_t s_rbeg, int64_t rmax0, int64_t rmax1, int rid, float frac_rep, int *eh_h, int *eh_e, int lane, int row_exit,
+                                unsigned int &n_exit)
 {
+    const int rx = row_exit ? EXT_ROW_EXIT_RELAXED : EXT_ROW_EXIT_OFF;
     DReg a;
     a.rb = a.re = 0; a.qb = a.qe = 0; a.sub = a.csub = a.sub_n = 0; a.seedcov = 0; a.secondary = 0;
     a.n_comp = 0; a.hash = 0;
@@ -346,7 +360,7 @@ __device__ DReg dev_extend_core(const DevRef &R, const slx_opt &opt, const MatRo
             const int prev = a.score;
             aw0 = opt.w << i;
             er = reg_ksw_extend2_auto<NCH>(s_qbeg, [&](int j) { return (int)query[s_qbeg - 1 - j]; }, (int)tmp,
-                                      [&](int t) { return ref_base(R, s_rbeg - 1 - t); }, opt, mr, aw0, opt.pen_clip5, s_len * opt.a, eh_h, eh_e, lane);
+                                      [&](int t) { return ref_base(R, s_rbeg - 1 - t); }, opt, mr, aw0, opt.pen_clip5, s_len * opt.a, eh_h, eh_e, lane, rx, n_exit);
             a.score = er.score;
             if (a.score == prev || er.max_off < (aw0 >> 1) + (aw0 >> 2)) break;
         }
@@ -361,7 +375,7 @@ __device__ DReg dev_extend_core(const DevRef &R, const slx_opt &opt, const MatRo
             const int prev = a.score;
             aw1 = opt.w << i;
             er = reg_ksw_extend2_auto<NCH>(l_query - qe, [&](int j) { return (int)query[qe + j]; }, (int)(rmax1 - re0),
-                                      [&](int t) { return ref_base(R, re0 + t); }, opt, mr, aw1, opt.pen_clip3, sc0, eh_h, eh_e, lane);
+                                      [&](int t) { return ref_base(R, re0 + t); }, opt, mr, aw1, opt.pen_clip3, sc0, eh_h, eh_e, lane, rx, n_exit);
             a.score = er.score;
             if (a.score == prev || er.max_off < (aw1 >> 1) + (aw1 >> 2)) break;
         }
@@ -440,7 +454,7 @@ __global__ void __launch_bounds__(64, EXT_MIN_WAVES) k_extend_reg(DevRef R, Chun
                                     (WALK_RG ? WALK_RG : 1) * (2 * sizeof(int64_t) + sizeof(qp_t) + 2 * sizeof(int)) <= 10240,
                   "16 one-wave blocks share a CU's 160 KB of LDS");
     const bool staged = MAXQ <= 704 && walk_stage != 0;
-    unsigned int staged_cnt = 0;
+    unsigned int staged_cnt = 0, exit_cnt = 0;                   // exit_cnt: in-place DPs the row exit ended (ck.ext_row_exit, "ext_row_exits")
     extern __shared__ int sh_dyn[];
     int *eh_h = sh_eh_h, *eh_e = sh_eh_e, *gap_lut = sh_gap_lut;
     int lut_n = MAXQ + 2;
@@ -823,9 +837,9 @@ __global__ void __launch_bounds__(64, EXT_MIN_WAVES) k_extend_reg(DevRef R, Chun
                                 a.w = opt.w; a.seedlen0 = s_len; a.score = a.truesc = 0; a.rid = w.c_rid[c];
                                 a.sub = a.csub = a.sub_n = 0; a.seedcov = 0; a.secondary = 0; a.n_comp = 0; a.hash = 0; a.frac_rep = frac_rep;
                             }
-                        } else a = dev_extend_core<NCH>(R, opt, mr, query, l_query, s_qbeg, s_len, s_rbeg, rmax0, rmax1, staged ? rid_c : w.c_rid[c], frac_rep, eh_h, eh_e, lane);
+                        } else a = dev_extend_core<NCH>(R, opt, mr, query, l_query, s_qbeg, s_len, s_rbeg, rmax0, rmax1, staged ? rid_c : w.c_rid[c], frac_rep, eh_h, eh_e, lane, ck.ext_row_exit, exit_cnt);
                     }
-                    else a = dev_extend_core<NCH>(R, opt, mr, query, l_query, s_qbeg, s_len, s_rbeg, rmax0, rmax1, staged ? rid_c : w.c_rid[c], frac_rep, eh_h, eh_e, lane);
+                    else a = dev_extend_core<NCH>(R, opt, mr, query, l_query, s_qbeg, s_len, s_rbeg, rmax0, rmax1, staged ? rid_c : w.c_rid[c], frac_rep, eh_h, eh_e, lane, ck.ext_row_exit, exit_cnt);
                     if (one) a.seedcov = chain_hdr_seedcov1(s_qbeg, s_len, s_rbeg, a.qb, a.qe, a.rb, a.re);
                     else {
                         int cov = 0;
@@ -868,6 +882,7 @@ __global__ void __launch_bounds__(64, EXT_MIN_WAVES) k_extend_reg(DevRef R, Chun
 #undef DBG_T1
     }
     if (n_staged && staged_cnt && lane == 0) atomicAdd(n_staged, staged_cnt);
+    if (ck.ext_exits && exit_cnt && lane == 0) atomicAdd(ck.ext_exits, exit_cnt);
 }
 
 
@@ -917,10 +932,12 @@ __global__ void k_cand_base(const int *heavy, const unsigned int *n_heavy, const
 }
 
 // one (read, chain, part) job; out of line so that the queue loop of the kernel stays a plain fetch / test / call (see dev_cig_dp_job)
+// (returns the DPs the row exit ended)
 template <int MAXQ>
-__device__ __noinline__ void dev_cand_job(const DevRef &R, const Chunk &ck, const slx_opt &opt, const MatRows &mr, const int *gap_lut, int *eh_h, int *eh_e,
-                                          int r, int jl, DReg *out, int lane)
+__device__ __noinline__ unsigned int dev_cand_job(const DevRef &R, const Chunk &ck, const slx_opt &opt, const MatRows &mr, const int *gap_lut, int *eh_h, int *eh_e,
+                                                  int r, int jl, DReg *out, int lane)
 {
+    unsigned int n_exit = 0;
     constexpr int NCH = MAXQ > 704 ? 0 : (MAXQ + 2 + WAVE - 1) / WAVE;   // 0: long reads, see wave_ksw_extend2
     auto max_gap_of = [&](int q) { return gap_lut[q < 0 ? 0 : (q > MAXQ + 1 ? MAXQ + 1 : q)]; };
     const int64_t l_pac = R.l_pac;
@@ -946,11 +963,11 @@ __device__ __noinline__ void dev_cand_job(const DevRef &R, const Chunk &ck, cons
             } else rem -= lane_read(pin, WAVE - 1);
         }
     }
-    if (ci < 0) return;
+    if (ci < 0) return 0;
     const int c = w.ia[ci];
     const int n = w.c_n[c];
     const int *cs = w.c_w + w.c_first[c];
-    if (n == 0) return;
+    if (n == 0) return 0;
     int64_t rmax0 = l_pac << 1, rmax1 = 0;
     for (int i = lane; i < n; i += WAVE) {
         const int s = cs[i];
@@ -984,7 +1001,7 @@ __device__ __noinline__ void dev_cand_job(const DevRef &R, const Chunk &ck, cons
     const int j_end = (part + 1) * CAND_PART < n ? (part + 1) * CAND_PART : n;
     for (int j = part * CAND_PART; j < j_end; ++j) {
         const int s = cs[j];
-        DReg a = dev_extend_core<NCH>(R, opt, mr, query, l_query, w.s_qbeg(s), w.s_len(s), w.s_rbeg[s], rmax0, rmax1, rid_c, frac_rep, eh_h, eh_e, lane);
+        DReg a = dev_extend_core<NCH>(R, opt, mr, query, l_query, w.s_qbeg(s), w.s_len(s), w.s_rbeg[s], rmax0, rmax1, rid_c, frac_rep, eh_h, eh_e, lane, ck.ext_row_exit, n_exit);
         int cov = 0;
         for (int i = lane; i < n; i += WAVE) {
             const int t = cs[i];
@@ -996,6 +1013,7 @@ __device__ __noinline__ void dev_cand_job(const DevRef &R, const Chunk &ck, cons
         a.seedcov = cov;
         if (lane == 0) out[s] = a;
     }
+    return n_exit;
 }
 
 template <int MAXQ>
@@ -1011,6 +1029,7 @@ __global__ void __launch_bounds__(64, EXT_JOB_WAVES) k_extend_cand(DevRef R, Chu
     __syncthreads();
     const unsigned int nh = (unsigned int)__builtin_amdgcn_readfirstlane((int)*n_heavy);
     const unsigned int n_jobs = nh ? (unsigned int)__builtin_amdgcn_readfirstlane((int)job_off[nh]) : 0u;
+    unsigned int exit_cnt = 0;
     for (;;) {
         const unsigned int job = wave_take(queue, 1u);
         if (job >= n_jobs) break;
@@ -1018,8 +1037,9 @@ __global__ void __launch_bounds__(64, EXT_JOB_WAVES) k_extend_cand(DevRef R, Chu
         while (hi - lo > 1) { const unsigned int mid = (lo + hi) >> 1; if (job_off[mid] <= job) lo = mid; else hi = mid; }
         const int r = heavy[lo];
         const int base = __builtin_amdgcn_readfirstlane(ck.cand_base[r]);
-        if (base >= 0) dev_cand_job<MAXQ>(R, ck, opt, mr, gap_lut, eh_h, eh_e, r, (int)(job - job_off[lo]), cand + base, lane);   // else extended in place
+        if (base >= 0) exit_cnt += dev_cand_job<MAXQ>(R, ck, opt, mr, gap_lut, eh_h, eh_e, r, (int)(job - job_off[lo]), cand + base, lane);   // else extended in place
     }
+    if (ck.ext_exits && exit_cnt && lane == 0) atomicAdd(ck.ext_exits, exit_cnt);
 }
 
 
@@ -1102,17 +1122,19 @@ __global__ void __launch_bounds__(128) k_first_prep(DevRef R, Chunk ck, DevOpt d
 
 // one top-seed extension; out of line so that the queue loop of the kernel stays a plain fetch / test / call
 template <int MAXQ>
-__device__ __noinline__ void dev_first_job(const DevRef &R, const Chunk &ck, const slx_opt &opt, const MatRows &mr, int *eh_h, int *eh_e, const FirstJob *jp,
-                                           DReg *out, int lane)
+__device__ __noinline__ unsigned int dev_first_job(const DevRef &R, const Chunk &ck, const slx_opt &opt, const MatRows &mr, int *eh_h, int *eh_e, const FirstJob *jp,
+                                                   DReg *out, int lane)
 {
+    unsigned int n_exit = 0;
     constexpr int NCH = MAXQ > 704 ? 0 : (MAXQ + 2 + WAVE - 1) / WAVE;   // 0: long reads, see wave_ksw_extend2
     const FirstJob j = *jp;                          // every lane reads the same 64 bytes
     const int64_t s_rbeg = (int64_t)rfl_u64((uint64_t)j.s_rbeg), rmax0 = (int64_t)rfl_u64((uint64_t)j.rmax0), rmax1 = (int64_t)rfl_u64((uint64_t)j.rmax1);
     const uint8_t *query = ck.codes + rfl_u64(j.q_off);
     const int l_query = __builtin_amdgcn_readfirstlane(j.l_query), s_qbeg = __builtin_amdgcn_readfirstlane(j.s_qbeg);
     const int s_len = __builtin_amdgcn_readfirstlane(j.s_len), rid = __builtin_amdgcn_readfirstlane(j.rid);
-    const DReg a = dev_extend_core<NCH>(R, opt, mr, query, l_query, s_qbeg, s_len, s_rbeg, rmax0, rmax1, rid, j.frac_rep, eh_h, eh_e, lane);
+    const DReg a = dev_extend_core<NCH>(R, opt, mr, query, l_query, s_qbeg, s_len, s_rbeg, rmax0, rmax1, rid, j.frac_rep, eh_h, eh_e, lane, ck.ext_row_exit, n_exit);
     if (lane == 0) *out = a;                         // seedcov is filled in by k_ext_replay
+    return n_exit;                                   // DPs the row exit ended
 }
 
 #define FIRST_BATCH 8        // jobs per queue fetch of k_ext_first (one fetch-add on a shared address costs ~10 ns device-wide)
@@ -1133,6 +1155,7 @@ __global__ void __launch_bounds__(64, EXT_JOB_WAVES) k_ext_first(DevRef R, Chunk
     unsigned int n_jobs = (unsigned int)__builtin_amdgcn_readfirstlane((int)first_off[n]);
     if (n_jobs > cap) n_jobs = cap;                  // (reads whose slots pass the table end are not prepared either)
     if (dp_list) n_jobs = (unsigned int)__builtin_amdgcn_readfirstlane((int)*n_dp);       // only the jobs k_first_diag left (dev_ext_lane.h)
+    unsigned int exit_cnt = 0;
     for (;;) {
         constexpr unsigned int BATCH = MAXQ > 704 ? 1u : (unsigned int)FIRST_BATCH;          // (a contig's extension is milliseconds: one per fetch)
         const unsigned int base = wave_take(queue, BATCH);
@@ -1140,9 +1163,10 @@ __global__ void __launch_bounds__(64, EXT_JOB_WAVES) k_ext_first(DevRef R, Chunk
         const unsigned int end = base + BATCH < n_jobs ? base + BATCH : n_jobs;
         for (unsigned int k = base; k < end; ++k) {
             const unsigned int job = dp_list ? (unsigned int)__builtin_amdgcn_readfirstlane((int)dp_list[k]) : k;
-            dev_first_job<MAXQ>(R, ck, opt, mr, eh_h, eh_e, jobs + job, first + job, lane);
+            exit_cnt += dev_first_job<MAXQ>(R, ck, opt, mr, eh_h, eh_e, jobs + job, first + job, lane);
         }
     }
+    if (ck.ext_exits && exit_cnt && lane == 0) atomicAdd(ck.ext_exits, exit_cnt);
 }
 
 template <int MAXQ>

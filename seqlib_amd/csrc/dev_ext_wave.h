@@ -67,6 +67,33 @@ __device__ __forceinline__ MatRows make_matrows(const int8_t *mat)
 // through two mismatches that is row 61 instead of row ~110 (the first column alone stays alive for h0 - o_del rows).
 // Needs non-negative gap penalties (else: never).  The scalar CPU restatement the parity tests compare with has no such exit.
 // (ext_tail_bound0 = B_qlen, INT_MAX when the bound does not hold, and ext_tail_done: dev_lane_rows.h, which the host compiles too)
+//
+// The row exit: rows that cannot matter, after ANY row (ext_row_bound / ext_row_done, dev_lane_rows.h; reg_ksw_extend2 and lane_rows_extend use it).
+// The tail bound above only knows h0 and the shape of the matrix, so it catches the extension that matched to the query's end; an extension into
+// a flank that does not match runs on until an all-zero row or z-drop.  After row i let m be the row's maximum, beg' the next row's first column
+// (the band update done) and hb what row i left in column -1: its h1 start, max(0, h0 - o_del - e_del * (i + 1)), if beg' = 0, else 0.  Then
+//     U = max(m, hb) + max(amax, 0) * min(qlen - beg', tlen - 1 - i)
+// bounds every H of every later row.  What enters row i + 1 is: an h of row i (<= m); an E', and E' <= max(E, M) <= the h of its column <= m;
+// column -1 (hb: row i + 1 reads it as the diagonal of its column 0 -- rows further down read a smaller one and have fewer rows left); or a cell
+// beyond the band, and those are zero: the band's end only ever moves back over cells whose h and e are both zero, and a zero H is dead
+// (M = H ? H + s : 0).  From there a path gains at most amax per diagonal step and nothing from a gap (penalties >= 0), and it has at most
+// qlen - beg' diagonal steps left, at most one per remaining row.
+// (hb is the ramp of row i, not of row i + 1: with h0 - o_del - e_del * (i + 2) the bound is one e_del short on the path "i + 1 rows deleted,
+// then the query matches from its first base", and tests/test_ext_row_exit_host.py's c_ramp cases then take the wrong branch below.)
+// Preconditions: gap penalties >= 0, as above, and zero cells beyond the band.  That holds when the band never clips `end` -- w + 1 >= qlen with w
+// the trial's effective band: then i + w + 1 >= qlen >= end in every row.  A clipped `end` (= i + w + 1) leaves what row -1 put into the columns
+// beyond it, and those re-enter the band later.  The clip bound grows with i, so a column beyond it was beyond it in every earlier row and has
+// never been written: it is a column j >= i + w + 2 >= w + 2 holding row -1's insertion ramp max(0, h0 - oe_ins - (j - 1) * e_ins), which is
+// <= max(0, h0 - oe_ins - (w + 1) * e_ins).  So the second form: h0 <= oe_ins + (w + 1) * e_ins, and those cells are zero as well (bwa's
+// defaults: h0 <= 108 with the effective band min(100, qlen) of a 150 bp read's extension -- every seed shorter than 109 bases; the long
+// junk flanks of the reads that lie half inside a repeat, the walk's longest DPs, are of this kind).  Neither holds: ext_row_exit_ok says no
+// and the loop runs as before (tests/test_ext_row_exit_host.py, c_clip: h0 on both sides of that edge with queries longer than the band).
+// Two rules, after the bookkeeping of row i (max, gscore as row i left them):
+//   strict   U <= max && max(U, 0) < gscore         -- ext_tail_done's form: no later row changes any of the six results;
+//   relaxed  U <= max - end_bonus (end_bonus = the caller's pen_clip >= 0), or the strict rule.  max, max_i, max_j and max_off are final (U <= max),
+//            and every later h1 is <= max - pen_clip.  A gscore that was above max - pen_clip cannot change (an update needs h1 >= gscore); one that
+//            was not stays at or below it, so `gscore <= 0 || gscore <= score - pen_clip` holds with and without the later rows, and that branch of
+//            dev_extend_core / lane_extend_core reads qle and tle only.  gscore / gtle may differ from ksw_extend2's there and nowhere else.
 
 // ---------------------------------------------------------------------------------------------- long extensions: the band in registers
 // A contig's extension runs for tens of thousands of rows inside a band of 2 w + 2 columns that slides one column per row.  Here the

@@ -31,6 +31,28 @@ LROW_FN int ext_tail_bound0(const O &o, int qlen, int h0, int amax)
 }
 LROW_FN bool ext_tail_done(int b, int max, int gscore) { return b <= max && (b > 0 ? b : 0) < gscore; }
 
+// Rows that cannot matter, after ANY row (derivation and preconditions: dev_ext_wave.h, "the row exit").  EXT_ROW_EXIT_*: what has to stay as it is.
+#define EXT_ROW_EXIT_OFF 0          // no exit: the loop runs to z-drop, an all-zero row, the tail bound or tlen
+#define EXT_ROW_EXIT_STRICT 1       // all six results of ksw_extend2
+#define EXT_ROW_EXIT_RELAXED 2      // score, qle, tle, max_off, and which branch of `gscore <= 0 || gscore <= score - pen_clip` the caller takes, with the fields that branch reads
+template <typename O>
+LROW_FN bool ext_row_exit_ok(const O &o, int qlen, int w, int h0)
+{   // w = the trial's effective band (after the max_ins / max_del limits).  Either the band never clips `end`, or what a clipped `end` leaves
+    // beyond it -- row -1's insertion ramp in the columns from w + 2 on -- is zero there
+    if (o.o_del < 0 || o.e_del < 0 || o.o_ins < 0 || o.e_ins < 0) return false;
+    return w + 1 >= qlen || (long long)h0 - o.o_ins - o.e_ins - (long long)(w + 1) * o.e_ins <= 0;
+}
+// U after row i: m = the row's maximum, hb = what the row left in column -1 for the next one (its h1 start if the band begins at column 0, else 0),
+// beg = the next row's first column, apos = max(amax, 0)
+LROW_FN int ext_row_bound(int m, int hb, int apos, int qlen, int beg, int tlen, int i)
+{
+    const int a = qlen - beg, b = tlen - 1 - i;
+    const int k = a < b ? a : b;
+    return (m > hb ? m : hb) + apos * (k > 0 ? k : 0);
+}
+// end_bonus: the caller's pen_clip for the relaxed rule; < 0 = the strict rule only
+LROW_FN bool ext_row_done(int U, int max, int gscore, int end_bonus) { return (end_bonus >= 0 && U <= max - end_bonus) || ext_tail_done(U, max, gscore); }
+
 // Where a lane keeps its H/E row.  WIDE: one 32-bit word per column -- 14-bit H, 14-bit E, the column's query code above them.  NARROW: when
 // no score can reach 256 (150 bp reads with bwa's default scores: read length x max(mat) < 256) a column is 8-bit H + 8-bit E in a 16-bit
 // word and the query codes sit apart, eight 4-bit codes per word: half the LDS per wave, twice the waves per CU -- and the kernel's time
@@ -74,8 +96,10 @@ struct LaneRes { int score, qle, tle, gtle, gscore, max_off, aw; };      // ksw_
 // Extends side 0 (where s[0].qlen > 0) from score h0, then side 1 (where s[1].qlen > 0) from the score side 0 ended with, each with the band
 // opt.w and -- by mem_chain2aln's rule -- once more with twice the band.  done(side, res) is called once per side that ran, in that order.
 // O = slx_opt, MR = MatRows (dev_ext_wave.h), L = the lane's row (not initialised by the caller), F = the bases.
+// row_exit (EXT_ROW_EXIT_*): end a trial after a row that rules out any change; *n_exit (optional) counts the trials it ended.
 template <typename L, typename F, typename O, typename MR, typename D>
-LROW_FN void lane_rows_extend(const LaneSide s[2], int h0, const O &o, const MR &mr, L &row, F &fetch, D done)
+LROW_FN void lane_rows_extend(const LaneSide s[2], int h0, const O &o, const MR &mr, L &row, F &fetch, D done, int row_exit = EXT_ROW_EXIT_STRICT,
+                              unsigned int *n_exit = nullptr)
 {
     const int o_del = o.o_del, e_del = o.e_del, o_ins = o.o_ins, e_ins = o.e_ins, zdrop = o.zdrop;
     const int oe_del = o_del + e_del, oe_ins = o_ins + e_ins;
@@ -83,7 +107,9 @@ LROW_FN void lane_rows_extend(const LaneSide s[2], int h0, const O &o, const MR 
     for (int i = 0; i < 25; ++i) amax = amax > o.mat[i] ? amax : o.mat[i];
     int side = s[0].qlen > 0 ? 0 : (s[1].qlen > 0 ? 1 : 2), trial = 0, prev = -1;
     bool fresh = true;
-    int qlen = 0, tlen = 0, q0 = 0, dir = 0, w = 0, aw = 0, tail_top = 0;
+    int qlen = 0, tlen = 0, q0 = 0, dir = 0, w = 0, aw = 0, tail_top = 0, exit_bonus = -1;
+    bool exit_ok = false;
+    const int apos = amax > 0 ? amax : 0;
     int64_t t0 = 0;
     int max = 0, max_i = -1, max_j = -1, max_ie = -1, gscore = -1, max_off = 0, beg = 0, end = 0, i = 0;
     while (side < 2) {
@@ -107,6 +133,8 @@ LROW_FN void lane_rows_extend(const LaneSide s[2], int h0, const O &o, const MR 
             max_del = max_del > 1 ? max_del : 1;
             w = w < max_del ? w : max_del;
             tail_top = ext_tail_bound0(o, qlen, h0, amax);
+            exit_ok = row_exit != EXT_ROW_EXIT_OFF && ext_row_exit_ok(o, qlen, w, h0);
+            exit_bonus = row_exit == EXT_ROW_EXIT_RELAXED ? end_bonus : -1;
             max = h0;
             max_i = -1; max_j = -1; max_ie = -1; gscore = -1; max_off = 0; beg = 0; end = qlen; i = 0;
         }
@@ -121,6 +149,7 @@ LROW_FN void lane_rows_extend(const LaneSide s[2], int h0, const O &o, const MR 
             if (end > qlen) end = qlen;
             int h1 = 0;
             if (beg == 0) { h1 = h0 - (o_del + e_del * (i + 1)); if (h1 < 0) h1 = 0; }
+            const int hb = h1;                                          // column -1 as the next row reads it
             uint32_t cur = beg < end ? row.get(beg) : 0u;
             for (int j = beg; j < end; ++j) {
                 const uint32_t nxt = row.get(j + 1);                    // (column j + 1 <= qlen exists; read ahead of this cell's arithmetic)
@@ -165,6 +194,10 @@ LROW_FN void lane_rows_extend(const LaneSide s[2], int h0, const O &o, const MR 
                 beg = j;
                 for (j = end; j >= beg && L::zero(row.get(j)); --j) {}
                 end = j + 2 < qlen ? j + 2 : qlen;
+                if (exit_ok && ext_row_done(ext_row_bound(m, beg == 0 ? hb : 0, apos, qlen, beg, tlen, i), max, gscore, exit_bonus)) {
+                    stop = true;                                        // no later row can change what is reported (dev_ext_wave.h)
+                    if (n_exit) ++*n_exit;
+                }
                 ++i;
             }
         }

@@ -136,6 +136,8 @@ struct Chunk {
     const int32_t *cand_base;
     unsigned long long *dbg_cyc;   // SLX_DEBUG_CYC: cycles a kernel spent on each read, 4 arrays of n_reads (null otherwise)
     int dbg_stage;                 // 1 = the extension kernel fills them, 2 = the region kernel
+    int ext_row_exit;              // "ext_row_exit": 1 = the short-read extension loops end after a row that rules out any change (dev_ext_wave.h, "the row exit")
+    unsigned int *ext_exits;       // ... DPs / band trials it ended ("ext_row_exits"; may be null)
     // per-read results
     int32_t *n_chain;         // kept chains
     int32_t *n_reg;

@@ -509,6 +509,7 @@ extern "C" int slx_aligner_set(slx_aligner *al, const char *key, int64_t value)
     else if (!strcmp(key, "top_heavy")) al->top_heavy = value != 0;
     else if (!strcmp(key, "top_reuse")) al->top_reuse = value != 0;
     else if (!strcmp(key, "walk_stage")) al->walk_stage = value != 0;
+    else if (!strcmp(key, "ext_row_exit")) al->ext_row_exit = value != 0;
     else if (!strcmp(key, "p2_items")) al->p2_items = value != 0;
     else if (!strcmp(key, "p2_coop")) al->p2_coop = value != 0;
     else if (!strcmp(key, "p2_items_cap")) al->p2_items_cap = (int)value;
@@ -602,6 +603,12 @@ extern "C" int64_t slx_aligner_counter(const slx_aligner *al, const char *key)
         if (!strcmp(key, "walk_staged_chains")) {          // last batch: chains k_extend_reg opened from a lane-made header (walk_stage)
             long long v = 0;
             auto take = [&](const slx_aligner *a) { for (const Worker *wk : a->workers) v += (long long)wk->walk_stat; };
+            if (al->is_group) for (const slx_aligner *sub : al->subs) take(sub); else take(al);
+            return v;
+        }
+        if (!strcmp(key, "ext_row_exits")) {          // last batch: DPs of the short-read extension kernels ended by the row exit (ext_row_exit)
+            long long v = 0;
+            auto take = [&](const slx_aligner *a) { for (const Worker *wk : a->workers) v += (long long)wk->exit_stat; };
             if (al->is_group) for (const slx_aligner *sub : al->subs) take(sub); else take(al);
             return v;
         }
@@ -735,6 +742,7 @@ static int worker_run(slx_aligner *al, Worker *wk, const slx_opt *opt, const uin
     wk->chain_stat[0] = wk->chain_stat[1] = 0;
     wk->first_stat = 0;
     wk->walk_stat = 0;
+    wk->exit_stat = 0;
     int rc;
     const int64_t n_part = r_hi - r_lo;
     if ((rc = wk->o_hit_off.ensure(((size_t)n_part + 1) * 8)) != SLX_OK) return rc;

@@ -100,6 +100,7 @@ struct Worker {
     unsigned long long first_stat = 0;                                             // k_first_lanes: DP jobs it counted as run, of the last batch
     bool first_lanes_ran = false;                                                  // ... the chunk in flight took that path
     unsigned long long walk_stat = 0;                                              // k_extend_reg: chains it served from a lane-made header, of the last batch
+    unsigned long long exit_stat = 0;                                              // extension kernels: DPs (lane kernels: band trials) the row exit ended, of the last batch
     unsigned int pseg_stat = 0;                                                    // ... how many
     unsigned int gseg_stat[3] = {0, 0, 0};                                         // ... segments taken as speculated / run again / jobs cut
     unsigned int xseg_stat[4] = {0, 0, 0, 0};                                      // ... segments taken as speculated / computed again / second band tries / sides cut, summed over this worker's launches
@@ -229,6 +230,8 @@ struct slx_aligner {
     int p2_items_cap = 0;         // test hook: capacity of the item list (0 = one per read of the chunk); reads whose items do not fit are walked whole
     int top_reuse = 1;            // 1 = k_extend_reg takes top-seed regions from that table (heavy reads, and light reads it redoes) instead of extending in place
     int walk_stage = 1;           // 1 = k_extend_reg (short reads) opens its chains from headers made 64 at a time, one per lane (dev_chain_hdr.h); 0 = chain by chain on the whole wave
+    int ext_row_exit = 1;         // 1 = the short-read extension loops (reg_ksw_extend2, lane_rows_extend) end after a row that rules out any change of what their caller
+                                  // reads (dev_ext_wave.h, "the row exit"); 0 = they run to z-drop, an all-zero row or the tail bound
     int seed_free_cus = 0;        // see "seed_free_cus" in slx_aligner_set
     int stream_prio = 0;
     int n_workers = 3;            // concurrent parts of a large batch

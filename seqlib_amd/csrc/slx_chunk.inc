@@ -662,6 +662,7 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
     ck.hardclip = hardclip; ck.keepSecFrac = ksf; ck.maxSecondary = maxsec;
     ck.sam_mode = (opt->flag & SLX_F_REG2SAM) ? 1 : 0;
     ck.seed_cnt = wk->seed_cnt.as<unsigned long long>();
+    ck.ext_row_exit = al->ext_row_exit; ck.ext_exits = wk->queues.as<unsigned int>() + 56;          // [56] DPs the row exit ended (the extension kernels add to it)
     const bool production = al->chain_mode == 1 && n >= al->split_min && !has_long;
     const bool use_cand = al->cand_mode == 1 && production;
     if (use_cand) {
@@ -1059,7 +1060,7 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
         m_defer = part(wk->queues.as<unsigned int>() + 46, 1);          // reads k_regs deferred to the wave kernel
         m_big = part(wk->queues.as<unsigned int>() + 48, 1);            // reads k_hits left to k_hits_wave
         m_chain = part(wk->queues.as<unsigned int>() + 50, 2);          // reads k_chain_lds started over on the HBM columns, reads it finished in LDS
-        m_walk = part(wk->queues.as<unsigned int>() + 55, 1);           // chains k_extend_reg opened from a lane-made header
+        m_walk = part(wk->queues.as<unsigned int>() + 55, 2);           // chains k_extend_reg opened from a lane-made header, DPs the row exit ended
         if (wk->first_lanes_ran) m_first = part(wk->queues.as<unsigned int>() + 54, 1);          // jobs k_first_lanes counted as run
         if (m_hits < 0 || m_cig < 0 || m_flags < 0 || m_defer < 0 || m_big < 0 || m_chain < 0 || m_walk < 0 || (wk->first_lanes_ran && m_first < 0)) {
             slx_set_error("run_chunk: more counters than k_mail has parts (SLX_MAIL_PARTS)");
@@ -1074,6 +1075,7 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
     if (fl) { *flags_out = fl; return SLX_OK; }
     wk->chain_stat[0] += wk->h_mail[m_chain]; wk->chain_stat[1] += wk->h_mail[m_chain + 1];
     wk->walk_stat += wk->h_mail[m_walk];
+    wk->exit_stat += wk->h_mail[m_walk + 1];
     if (m_first >= 0) wk->first_stat += wk->h_mail[m_first];
     // grow the outputs and compact
     const size_t H = (size_t)*hit_base + Hc, C = (size_t)*cig_base + Cc;
