@@ -376,6 +376,9 @@ __device__ __forceinline__ int kmer_codes(QB &qb, int p, int K, uint32_t &fw, ui
 // x[1] is read by nothing but the next rank-based forward step.  So from there the walk needs one suffix-array read (the occurrence's
 // position, dense SA) and the 2-bit reference -- 32 bases per 8-byte read -- instead of a rank per base.  A lane switches after two
 // consecutive steps at one occurrence (chance matches next to a mismatch die at once: not worth the two reads).
+// Exact only where the pac IS the indexed text.  An in-memory build over N holes fills them twice, once for the pac and once for the BWT text
+// (slx_index.cpp), and a direct step inside a hole then follows bases the index does not hold: the host hands such an index over without the
+// dense SA (slx_chunk.inc, slx_aligner::text_is_pac), which switches off every direct step here, bwd_direct and the repeat filter.
 #ifndef SEED4_DIRECT_AFTER
 #define SEED4_DIRECT_AFTER 2
 #endif

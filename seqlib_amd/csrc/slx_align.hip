@@ -107,6 +107,28 @@ __global__ void k_sa_walk(DevFM<I> fm, I *dense, uint64_t n_sa)
     }
 }
 
+// Is the pac the forward half of the text the FM-index is over?  The BWT symbol of rank i is the text's base before suffix sa[i]: one pass over the dense SA
+// compares it with the pac's base there.  They differ where an in-memory build of the reference's kind filled an N -- it draws for the pac and again for the
+// BWT text -- and index files do not say how they were made.  differ: set to 1 by any lane that finds a difference (all write the same value).
+template <typename I>
+__global__ void k_text_is_pac(DevFM<I> fm, DevRef R, const I *dense, unsigned int *differ)
+{
+    const uint64_t n1 = (uint64_t)fm.seq_len + 1, stride = (uint64_t)gridDim.x * blockDim.x;
+    RWin w; w.bits = 0; w.chunk = -1;
+    bool bad = false;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n1; i += stride) {
+        if (i == (uint64_t)fm.primary) continue;          // suffix 0: the symbol before it is the sentinel, which the BWT does not hold
+        const uint64_t x = i - (i > (uint64_t)fm.primary ? 1 : 0);
+        const uint32_t *blk = fm.bwt + ((size_t)(x >> 7) << 4) + 8;
+        const int jj = (int)(x & 127);
+        const int c = (blk[jj >> 4] >> ((~jj & 15) << 1)) & 3;
+        const int64_t p = (int64_t)dense[i] - 1;
+        if (p < 0 || p >= (R.l_pac << 1)) { bad = true; continue; }          // (not a suffix array: certainly not this pac's)
+        if (text_at(R, p, w) != c) bad = true;
+    }
+    if (bad) *differ = 1u;
+}
+
 // ---------------------------------------------------------------- create / free
 template <typename I>
 static int build_lut(slx_aligner *al)
@@ -182,12 +204,35 @@ static int upload_fm(slx_aligner *al)
     return SLX_OK;
 }
 
+// al->text_is_pac: what the index knows of itself (built in memory), or one pass over a loaded index (k_text_is_pac); needs al->ref and the dense SA
+template <typename I>
+static int find_text_is_pac(slx_aligner *al)
+{
+    const slx_index *idx = al->host_idx;
+    al->text_is_pac = idx->text_is_pac != 0;
+    if (idx->text_is_pac >= 0 || !al->have_dense) return SLX_OK;
+    unsigned int *d_differ = nullptr, differ = 0;
+    HIPCHK(hipMalloc((void **)&d_differ, sizeof differ));
+    hipError_t e = hipMemsetAsync(d_differ, 0, sizeof differ, al->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_text_is_pac<I>, dim3(al->n_cu * 16), dim3(256), 0, al->stream, fm_of<I>(al), al->ref, al->d_sa_dense.as<I>(), d_differ);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&differ, d_differ, sizeof differ, hipMemcpyDeviceToHost, al->stream);
+    if (e == hipSuccess) e = slx_wait_stream(al->stream);
+    (void)hipFree(d_differ);
+    HIPCHK(e);
+    al->text_is_pac = differ == 0;
+    return SLX_OK;
+}
+
 // the repeat filter of pass 2 of the seeding kernels: one bit per hashed rep_k-mer that occurs at least twice (8-16 bits per text symbol:
 // 128 MB of HBM for a 129 M-symbol index, 8 GB for GRCh38's 6.2 G -- per aligner; knob "rep_k" = 0 turns it off)
 template <typename I>
 static int build_rep_filter(slx_aligner *al)
 {
     al->rep_mask = 0;
+    if (!al->text_is_pac) return SLX_OK;          // the filter is made of the pac's k-mers: where the pac is not the indexed text it would rule out what the index finds
     if (al->rep_k <= 0 || al->rep_k > 31 || !al->have_dense || al->host_idx->seq_len < 1024) return SLX_OK;
     uint64_t bits = 1ull << 20;
     while (bits < al->host_idx->seq_len * 8ull) bits <<= 1;
@@ -313,6 +358,7 @@ static int aligner_init(slx_aligner *al, const slx_index *idx, const int *device
             al->ref.ann_alt = al->d_ann_alt.as<uint8_t>();
         }
     }
+    if ((rc = al->wide ? find_text_is_pac<uint64_t>(al) : find_text_is_pac<uint32_t>(al)) != SLX_OK) return rc;
     if ((rc = al->wide ? build_rep_filter<uint64_t>(al) : build_rep_filter<uint32_t>(al)) != SLX_OK) return rc;
     // log() table from the host's libm
     const int LUT_N = SLX_LOG_LUT_N;
@@ -572,6 +618,7 @@ extern "C" int64_t slx_aligner_counter(const slx_aligner *al, const char *key)
 {   // what the last batch held (diagnostics and tests: "did that kernel see any work?"); -1 for an unknown key
     if (!al || !key) return -1;
     if (!strcmp(key, "workers")) return al->is_group ? al->subs[0]->n_workers : al->n_workers;     // (per device)
+    if (!strcmp(key, "text_is_pac")) return (al->is_group ? al->subs[0] : al)->text_is_pac ? 1 : 0;          // 0: the index was built over N holes; direct text steps and the repeat filter are off
     if (!strcmp(key, "hw_queues")) return al->hw_queues;          // GPU_MAX_HW_QUEUES as the process had it when the aligner was created (4 = the runtime's default)
     if (!strcmp(key, "long_rounds") || !strcmp(key, "long_jobs")) {       // extension rounds / seed jobs of the last long-read chunk (largest over the workers)
         long long v = 0;

@@ -153,6 +153,9 @@ struct slx_aligner {
     DevRef ref;
     bool dense_sa = true;
     bool have_dense = false;
+    bool text_is_pac = true;      // the pac is the forward half of the text the FM-index is over (slx_index::text_is_pac, or k_text_is_pac's answer for a loaded index).  False
+                                  // for an in-memory build over N holes: nothing may then step through the pac instead of the index -- no direct steps (the chunk runs
+                                  // without the dense SA they hang on), no bwd_direct, no repeat filter.  Counter "text_is_pac"
     const slx_index *host_idx = nullptr;
     // knobs
     int64_t chunk_reads = 1 << 24;  // one chunk per worker for a 10 M-read batch: the heavy-tail reads are then paid for once

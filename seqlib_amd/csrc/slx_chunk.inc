@@ -678,7 +678,9 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
     }
     DevOpt dopt; dopt.o = *opt;
     DevFM<I> fm = fm_of<I>(al);
-    fm.sa_dense = (al->dense_sa && al->have_dense) ? al->d_sa_dense.as<I>() : nullptr;
+    // (the seeding kernels take "dense SA present" as leave to step through the pac instead of the index: not where the pac is not the indexed text -- that
+    // index runs as with dense_sa = 0)
+    fm.sa_dense = (al->dense_sa && al->have_dense && al->text_is_pac) ? al->d_sa_dense.as<I>() : nullptr;
     fm.rep = al->rep_mask ? al->d_rep.as<uint32_t>() : nullptr; fm.rep_mask = al->rep_mask; fm.rep_k = al->rep_k;
     // (a text position plus the flag bit must fit the index type: every u64 index, u32 indexes below 2^31 symbols)
     fm.bwd_direct = (al->bwd_direct && fm.sa_dense && (sizeof(I) == 8 || (uint64_t)fm.seq_len < (1ULL << 31))) ? 1 : 0;

@@ -4,6 +4,7 @@
 // SURVEY.md Appendix B, which was byte-checked against the reference's tests/data/tiny.fa.*.
 // The suffix sort / BWT / Occ construction itself runs on the GPU (slx_index_gpu.hip).
 #include "slx_internal.h"
+#include "index_build_width.h"
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -135,17 +136,18 @@ extern "C" int slx_index_build(const char *const *names, const char *const *seqs
         total += L[i];
     }
     // (the reference's in-memory builder stops at 2^31 - 1 BWT symbols -- is_bwt takes an int; larger indexes reach it as files
-    // made by `bwa index`.  Here texts of 2^32 - 1 symbols and more take the 64-bit suffix sorter, slx_index_gpu64.hip.)
-    const bool wide = (uint64_t)total * 2 + 1 >= (1ULL << 32) || getenv("SLX_BUILD64") != nullptr;
+    // made by `bwa index`.  Here texts whose 2 * total + 1 suffixes no longer count in an int take the 64-bit suffix sorter,
+    // slx_index_gpu64.hip: index_build_width.h.)
+    const bool wide = !slx_build32_fits((uint64_t)total) || getenv("SLX_BUILD64") != nullptr;
     slx_index *idx = new slx_index();
     idx->l_pac = total;
     // forward pac (first pass over the sequences; every N draws lrand48()&3)
     idx->pac.assign((size_t)(total / 4 + 2), 0);
-    int64_t l = 0;
+    int64_t l = 0, n_drawn = 0;
     for (int i = 0; i < n; ++i)
         for (int64_t k = 0; k < L[i]; ++k, ++l) {
             int c = NT4[(uint8_t)seqs[i][k]];
-            if (c >= 4) c = (int)(lrand48() & 3);
+            if (c >= 4) { c = (int)(lrand48() & 3); ++n_drawn; }
             idx->pac[(size_t)(l >> 2)] |= (uint8_t)(c << ((~l & 3) << 1));
         }
     // BWT text: second pass (fresh draws at N, as the reference's second seqlib_make_pac call) ++ reverse complement
@@ -161,6 +163,7 @@ extern "C" int slx_index_build(const char *const *names, const char *const *seqs
     int rc = wide ? slx_gpu_build_fm64(idx, text.data(), (uint64_t)total * 2) : slx_gpu_build_fm(idx, text.data(), (uint64_t)total * 2);
     std::vector<uint8_t>().swap(text);
     if (rc != SLX_OK) { delete idx; return rc; }
+    idx->text_is_pac = n_drawn == 0 ? 1 : 0;          // the second pass drew afresh at every N: inside a hole the FM-index and the pac hold different bases
     idx->seed = 11;
     int64_t off = 0;
     for (int i = 0; i < n; ++i) {

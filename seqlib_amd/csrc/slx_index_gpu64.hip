@@ -1,4 +1,4 @@
-// slx_index_gpu64.hip -- FM-index construction on the GPU for texts of 2^32 - 1 symbols and more (a GRCh38-sized
+// slx_index_gpu64.hip -- FM-index construction on the GPU for texts of 2^31 - 1 symbols and more (index_build_width.h; a GRCh38-sized
 // reference is 6.2 G symbols: forward ++ reverse complement).  The reference itself cannot build such an index in
 // memory (its ConstructIndex runs the 32-bit is_bwt, /root/reference/src/BWAIndex.cpp:127-138,305-341) and reaches
 // them through LoadIndex of files made by `bwa index`; the RESULT is specified by those files (suffix order with an
@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <vector>
 #include "slx_internal.h"
+#include "index_build_width.h"
 
 #define HIPCHK(x)                                                                                   \
     do {                                                                                            \
@@ -452,7 +453,9 @@ int slx_gpu_build_fm64(slx_index *idx, const uint8_t *text, uint64_t n)
     idx->sa.resize(n_sa);
     HIPCHK(hipMemcpy(idx->sa.data(), samp.p, n_sa * 8, hipMemcpyDeviceToHost));
     idx->dense_sa32.clear();
-    if (n1 < (1ULL << 32) && !getenv("SLX_BUILD64_NO_DENSE")) {   // small text through the 64-bit builder (test hook): keep the dense SA like the 32-bit one does
+    // a text the 32-bit builder would have taken, sent here by the test hook: keep the dense SA like that one does.  (Texts of 2^31 symbols and more are here
+    // because they have to be: their suffix array stays on the device -- 8 bytes a suffix through the host is tens of gigabytes -- and the aligner rebuilds it.)
+    if (slx_build32_fits(n >> 1) && !getenv("SLX_BUILD64_NO_DENSE")) {
         std::vector<u64> full(n1);
         HIPCHK(hipMemcpy(full.data(), sa, n1 * 8, hipMemcpyDeviceToHost));
         idx->dense_sa32.resize(n1);

@@ -36,6 +36,9 @@ struct slx_index {
     std::vector<uint8_t> pac;           // forward strand, 2 bit/base
     // optional: full suffix array kept from a device build (sentinel-inclusive order, n+1 entries)
     std::vector<uint32_t> dense_sa32;
+    // is the pac the forward half of the text the FM-index is over?  1: built here from sequences without N.  0: built here and N were drawn -- twice, as the
+    // reference does, once for the pac and once for the BWT text.  -1: loaded from files, which do not say: the aligner finds out (slx_align.hip, k_text_is_pac)
+    int text_is_pac = -1;
 };
 
 void slx_set_error(const char *fmt, ...);
@@ -62,7 +65,7 @@ static inline hipError_t slx_wait_stream(hipStream_t st)
 
 // device-side index construction (slx_index_gpu.hip): text T[0..n) over {0..3} -> fills bwt/sa/primary/L2
 int slx_gpu_build_fm(slx_index *idx, const uint8_t *text, uint64_t n);
-// the same for texts of 2^32 - 1 symbols and more (slx_index_gpu64.hip); also taken for small texts when SLX_BUILD64 is set (test hook)
+// the same for texts the 32-bit builder cannot count in an int (index_build_width.h: 2^31 - 1 symbols and more; slx_index_gpu64.hip); also taken for small texts when SLX_BUILD64 is set (test hook)
 int slx_gpu_build_fm64(slx_index *idx, const uint8_t *text, uint64_t n);
 
 // what the record builder (slx_rec.hip) needs of the other handles
