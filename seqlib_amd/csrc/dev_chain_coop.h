@@ -11,6 +11,7 @@
 // Behaviour: bwa mem_chain / test_and_merge / mem_chain_weight / mem_chain_flt.
 #pragma once
 #include "dev_chain.h"
+#include "dev_as.h"
 
 __device__ __forceinline__ int64_t lane_read64(int64_t v, int src)
 {
@@ -20,22 +21,47 @@ __device__ __forceinline__ int64_t lane_read64(int64_t v, int src)
     return (int64_t)(((unsigned long long)hi << 32) | lo);
 }
 
-struct CoopTables {            // LDS tables of one wave
-    int64_t *s_pos;            // chain positions in ascending order (the ordered set)
-    int *s_ord;                // chain handle at each rank; later reused as the weight-sorted list a[]
-    int *s_w, *s_cb, *s_ce, *s_first, *s_kept;
-    signed char *s_kf;
+// The LDS tables of one wave, one struct so that a single LDS-typed base reaches the out-of-line routine and every table is that base + a
+// constant: the accesses are ds_ instructions (dev_as.h has the reason), and no table pointer is ever loaded.
+template <int NCMAX>
+struct CoopTables {
+    int64_t pos[NCMAX + 64];   // chain positions in ascending order (the ordered set)
+    int ord[NCMAX + 64];       // chain handle at each rank; later reused as the weight-sorted list a[]
+    int w[NCMAX], cb[NCMAX], ce[NCMAX], first[NCMAX], kept[NCMAX];
+    signed char kf[NCMAX];
+};
+
+// the columns of ReadWS this routine touches, as global-address-space pointers with scalar bases (one read per wave): a store to them does not
+// stand in front of the next LDS read
+struct CoopWS {
+    glb_ptr<int64_t> s_rbeg; glb_ptr<qp_t> s_ql; glb_ptr<int32_t> s_next, s_score;
+    glb_ptr<int64_t> c_pos; glb_ptr<int32_t> c_head, c_tail, c_n, c_rid, c_w, c_first, ia;
+    __device__ __forceinline__ int s_qbeg(int s) const { return QP_HI(s_ql[s]); }
+    __device__ __forceinline__ int s_len(int s) const { return QP_LO(s_ql[s]); }
 };
 
 // one heavy read on one wave; out of line so that the queue loop of the kernel stays a plain fetch / test / call
 template <typename I, int NCMAX, bool FINAL>
-__device__ __noinline__ void dev_chain_read_coop(const DevFM<I> &fm, const DevRef &R, const Chunk &ck, const slx_opt &opt, int r, const CoopTables &T, int lane,
-                                                 int nc_limit)
+__device__ __noinline__ void dev_chain_read_coop(const DevFM<I> &fm, const DevRef &R, const Chunk &ck, const slx_opt &opt, int r_, lds_ptr<CoopTables<NCMAX>> T, int lane,
+                                                 int nc_limit_)
 {
-    int64_t *s_pos = T.s_pos; int *s_ord = T.s_ord, *s_w = T.s_w, *s_cb = T.s_cb, *s_ce = T.s_ce, *s_first = T.s_first, *s_kept = T.s_kept;
-    signed char *s_kf = T.s_kf;
+    const int r = rfl_i32(r_), nc_limit = rfl_i32(nc_limit_);
+    const lds_ptr<int64_t> s_pos = T->pos;
+    const lds_ptr<int> s_ord = T->ord, s_w = T->w, s_cb = T->cb, s_ce = T->ce, s_first = T->first, s_kept = T->kept;
+    const lds_ptr<signed char> s_kf = T->kf;
+    // what the loops read of opt and R, once per read and in scalar registers (they reach this routine by reference, that is in memory)
+    const int o_w = rfl_i32(opt.w), o_max_chain_gap = rfl_i32(opt.max_chain_gap), o_max_occ = rfl_i32(opt.max_occ);
+    const int o_min_chain_weight = rfl_i32(opt.min_chain_weight), o_min_seed_len = rfl_i32(opt.min_seed_len), o_max_chain_extend = rfl_i32(opt.max_chain_extend);
+    const float o_mask_level = rfl_f32(opt.mask_level), o_drop_ratio = rfl_f32(opt.drop_ratio);
+    const int64_t l_pac = rfl_i64(R.l_pac);
+    const glb_ptr<const uint8_t> ann_alt = as_glb_uniform(R.ann_alt);
+    auto is_alt = [&](int rid) { return ann_alt && rid >= 0 ? (int)ann_alt[rid] : 0; };      // ref_is_alt
     {
-        ReadWS w = make_ws(ck, r);
+        const ReadWS w0 = make_ws(ck, r);
+        CoopWS w;
+        w.s_rbeg = as_glb_uniform(w0.s_rbeg); w.s_ql = as_glb_uniform(w0.s_ql); w.s_next = as_glb_uniform(w0.s_next); w.s_score = as_glb_uniform(w0.s_score);
+        w.c_pos = as_glb_uniform(w0.c_pos); w.c_head = as_glb_uniform(w0.c_head); w.c_tail = as_glb_uniform(w0.c_tail); w.c_n = as_glb_uniform(w0.c_n);
+        w.c_rid = as_glb_uniform(w0.c_rid); w.c_w = as_glb_uniform(w0.c_w); w.c_first = as_glb_uniform(w0.c_first); w.ia = as_glb_uniform(w0.ia);
         // The LDS table bounds the number of CHAINS, which is usually far below the number of seed occurrences (2 000 occurrences in
         // 45 chains is typical of a repeat tract), so a read is only turned away when a chain would not fit any more: n_chain = -2
         // hands it to the launch with the bigger table, and past that one to a single lane on global memory.
@@ -54,15 +80,15 @@ __device__ __noinline__ void dev_chain_read_coop(const DevFM<I> &fm, const DevRe
         // while the set is a sorted array (the position comes from s_pos) and one (c_pos) once it is a tree -- it was two dependent round
         // trips (c_head / c_tail, then the seeds), which under the seeding kernels' memory pressure made this the most stretched kernel of
         // the pipeline.  The global arrays are still written, as the later phases and kernels read them.
-        int *l_tail = s_w, *l_lastql = s_cb, *l_lastoff = s_ce, *l_firstql = s_first, *l_rid = s_kept;
+        const lds_ptr<int> l_tail = s_w, l_lastql = s_cb, l_lastoff = s_ce, l_firstql = s_first, l_rid = s_kept;
         const bool cnt16 = ck.seed_off[r + 1] - ck.seed_off[r] < 65536;      // (the count fits 16 bits; else it is read back from c_n)
         // ---------------- mem_chain: seeds in interval order, occurrences in rank order
         for (int i = 0; i < n_intv; ++i) {
             const int qbeg = QP_HI(iinfo[i]), slen = QP_LO(iinfo[i]) - qbeg;
             const I x0 = ix0[i], x2 = ix2[i];
-            const I step = x2 > (I)opt.max_occ ? x2 / (I)opt.max_occ : (I)1;
+            const I step = x2 > (I)o_max_occ ? x2 / (I)o_max_occ : (I)1;
             I cm = (x2 + step - 1) / step;        // trips of `for (k = count = 0; k < x2 && count < max_occ; k += step, ++count)`
-            if (cm > (I)opt.max_occ) cm = (I)opt.max_occ;
+            if (cm > (I)o_max_occ) cm = (I)o_max_occ;
             const int count_max = (int)cm;
             for (int base = 0; base < count_max; base += 64) {
                 const int t = base + lane;
@@ -100,16 +126,22 @@ __device__ __noinline__ void dev_chain_read_coop(const DevFM<I> &fm, const DevRe
                             const int f_qbeg = (int)(fql >> 16);
 #endif
                             const int l_qbeg = QP_HI(lql), l_len = QP_LO(lql);
-                            const int64_t f_rbeg = tree ? w.c_pos[c] : s_pos[lo];          // a chain's position is its first seed's reference start
+                            int64_t f_rbeg;                                                // a chain's position is its first seed's reference start
+                            if (tree) {
+                                f_rbeg = w.c_pos[c];
+                                // (the load ends inside its branch: left in flight it would put a wait for the vector-memory counter, which on
+                                // this target holds the loop's stores to HBM as well, on the sorted-array path too)
+                                __builtin_amdgcn_s_waitcnt(0x0f70);                        // vmcnt(0); expcnt and lgkmcnt left alone
+                            } else f_rbeg = s_pos[lo];
                             const int64_t l_rbeg = f_rbeg + l_lastoff[c];
                             const int64_t qend = l_qbeg + l_len, rend = l_rbeg + l_len;
                             int res;
                             if (rid != l_rid[c]) res = 0;
                             else if (qbeg >= f_qbeg && qbeg + slen <= qend && rbeg >= f_rbeg && rbeg + slen <= rend) res = 1;
-                            else if ((l_rbeg < R.l_pac || f_rbeg < R.l_pac) && rbeg >= R.l_pac) res = 0;
+                            else if ((l_rbeg < l_pac || f_rbeg < l_pac) && rbeg >= l_pac) res = 0;
                             else {
                                 const int64_t x = qbeg - l_qbeg, y = rbeg - l_rbeg;
-                                if (y >= 0 && x - y <= opt.w && y - x <= opt.w && x - l_len < opt.max_chain_gap && y - l_len < opt.max_chain_gap) {
+                                if (y >= 0 && x - y <= o_w && y - x <= o_w && x - l_len < o_max_chain_gap && y - l_len < o_max_chain_gap) {
                                     const int s = ns++;   // every lane stores the same bytes
                                     w.s_rbeg[s] = rbeg; w.s_ql[s] = QP_PACK(qbeg, slen); w.s_next[s] = -1; if (w.s_score) w.s_score[s] = slen;
                                     w.s_next[last] = s; w.c_tail[c] = s;
@@ -132,7 +164,7 @@ __device__ __noinline__ void dev_chain_read_coop(const DevFM<I> &fm, const DevRe
                         // equal positions in a multi-node kbtree: which chain a search meets first and the traversal order depend on the tree's
                         // shape (dev_kbtree.h).  Until now the sorted array and the tree agreed; the tree's shape is a function of the insertion
                         // order, which is the chains' creation order -- so it is rebuilt by replaying those insertions, and the set goes on as the tree.
-                        kb.mem = (int *)w.regs; kb.n_nodes = 0; kb.root = kb.alloc(0);
+                        kb.mem = (int *)w0.regs; kb.n_nodes = 0; kb.root = kb.alloc(0);
                         for (int h = 0; h < nc; ++h) kb.put(w.c_pos[h], h);
                         tree = true;
                     }
@@ -167,7 +199,7 @@ __device__ __noinline__ void dev_chain_read_coop(const DevFM<I> &fm, const DevRe
                 }
             }
         }
-        if (tree) kb.traverse(s_ord);             // __kb_traverse: the order mem_chain_flt receives the chains in
+        if (tree) kb.traverse((int *)s_ord);            // __kb_traverse: the order mem_chain_flt receives the chains in
         ck.frac_rep[r] = (float)ck.l_rep[r] / len;
         // ---------------- mem_chain_flt
         // weights, one chain per lane (handles are 0..nc-1 in creation order; s_ord gives them in pos order)
@@ -183,7 +215,7 @@ __device__ __noinline__ void dev_chain_read_coop(const DevFM<I> &fm, const DevRe
         for (int base = 0; base < nc; base += 64) {
             const int m = base + lane;
             int c = 0; bool keep = false;
-            if (m < nc) { c = s_ord[m]; keep = s_w[c] >= opt.min_chain_weight; }
+            if (m < nc) { c = s_ord[m]; keep = s_w[c] >= o_min_chain_weight; }
             const unsigned long long bal = __ballot(keep);
             const int rank = __popcll(bal & ((1ull << lane) - 1ull));
             if (keep) s_ord[n_chn + rank] = c;     // n_chn + rank <= m: never overtakes the reads of this block
@@ -191,7 +223,7 @@ __device__ __noinline__ void dev_chain_read_coop(const DevFM<I> &fm, const DevRe
         }
         int n_out = 0;
         if (n_chn > 0) {
-            int *a = s_ord;
+            const lds_ptr<int> a = s_ord;
             ks_introsort_idx(n_chn, a, [&](int x, int y) { return s_w[x] > s_w[y]; });   // uniform: every lane runs the same sort on LDS
             int n_kept = 0;
             s_kf[a[0]] = 3;
@@ -199,7 +231,7 @@ __device__ __noinline__ void dev_chain_read_coop(const DevFM<I> &fm, const DevRe
             for (int i = 1; i < n_chn; ++i) {
                 const int ci = a[i];
                 const int bi = s_cb[ci], ei = s_ce[ci], wi = s_w[ci], li = ei - bi;
-                const bool i_alt = ref_is_alt(R, w.c_rid[ci]) != 0;
+                const bool i_alt = is_alt(w.c_rid[ci]) != 0;
                 int large_ovlp = 0;
                 bool broke = false;
                 for (int kb = 0; kb < n_kept && !broke; kb += 64) {
@@ -210,13 +242,13 @@ __device__ __noinline__ void dev_chain_read_coop(const DevFM<I> &fm, const DevRe
                         cj = a[s_kept[k]];
                         const int bj = s_cb[cj], ej = s_ce[cj];
                         const int b_max = bj > bi ? bj : bi, e_min = ej < ei ? ej : ei;
-                        if (e_min > b_max && (!ref_is_alt(R, w.c_rid[cj]) || i_alt)) {   // (an ALT kept chain does not shadow a primary-assembly one)
+                        if (e_min > b_max && (!is_alt(w.c_rid[cj]) || i_alt)) {   // (an ALT kept chain does not shadow a primary-assembly one)
                             const int lj = ej - bj;
                             const int min_l = li < lj ? li : lj;
-                            if ((float)(e_min - b_max) >= (float)min_l * opt.mask_level && min_l < opt.max_chain_gap) {
+                            if ((float)(e_min - b_max) >= (float)min_l * o_mask_level && min_l < o_max_chain_gap) {
                                 large = true;
                                 const int wj = s_w[cj];
-                                if ((float)wi < (float)wj * opt.drop_ratio && wj - wi >= opt.min_seed_len << 1) drop = true;
+                                if ((float)wi < (float)wj * o_drop_ratio && wj - wi >= o_min_seed_len << 1) drop = true;
                             }
                         }
                     }
@@ -237,7 +269,7 @@ __device__ __noinline__ void dev_chain_read_coop(const DevFM<I> &fm, const DevRe
             for (i = k = 0; i < n_chn; ++i) {        // at most max_chain_extend chains of kind 1/2
                 const int kf = s_kf[a[i]];
                 if (kf == 0 || kf == 3) continue;
-                if (++k >= opt.max_chain_extend) break;
+                if (++k >= o_max_chain_extend) break;
             }
             for (int m = i + lane; m < n_chn; m += 64) if (s_kf[a[m]] < 3) s_kf[a[m]] = 0;
             // kept chains, in weight order, to the read's global list (ordered compaction)
@@ -278,12 +310,8 @@ template <typename I, int NCMAX, bool FINAL>
 __global__ void __launch_bounds__(64) k_chain_coop(DevFM<I> fm, DevRef R, Chunk ck, DevOpt dopt, const int *order, unsigned int *queue,
                                                    const unsigned int *n_slots, int nc_limit)
 {
-    __shared__ int64_t s_pos[NCMAX + 64];
-    __shared__ int s_ord[NCMAX + 64];
-    __shared__ int s_w[NCMAX], s_cb[NCMAX], s_ce[NCMAX], s_first[NCMAX], s_kept[NCMAX];
-    __shared__ signed char s_kf[NCMAX];
-    CoopTables T;
-    T.s_pos = s_pos; T.s_ord = s_ord; T.s_w = s_w; T.s_cb = s_cb; T.s_ce = s_ce; T.s_first = s_first; T.s_kept = s_kept; T.s_kf = s_kf;
+    __shared__ CoopTables<NCMAX> tables;
+    const lds_ptr<CoopTables<NCMAX>> T = as_lds(&tables);
     const int lane = threadIdx.x;
     const int n_todo = __builtin_amdgcn_readfirstlane((int)*n_slots);
     for (;;) {

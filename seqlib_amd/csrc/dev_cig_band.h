@@ -483,8 +483,7 @@ template <int MAXQ, int NB>
 __global__ void __launch_bounds__(GB_THREADS) k_regs_wave_long(DevRef R, Chunk ck, DevOpt dopt, FinLists fl, const int *order, unsigned int *queue, const unsigned int *n_slots,
                                                                PMemo pm)
 {
-    __shared__ int s_idx[NB], s_ka[NB], s_kb[NB], s_qe[NB], s_rid[NB], s_w[NB];
-    __shared__ int64_t s_k64[NB], s_rb[NB];
+    __shared__ SortTables<NB> tables;
     __shared__ RegsBlockShared SB;
     if ((int)blockIdx.x * WAVE >= ck.long_threads) return;          // (this block's stretch of the per-thread rows: threads blockIdx.x * 64 ..)
     if (threadIdx.x >= WAVE) {                                       // helpers
@@ -496,9 +495,7 @@ __global__ void __launch_bounds__(GB_THREADS) k_regs_wave_long(DevRef R, Chunk c
         return;
     }
     const int lane = threadIdx.x;
-    SortStage ss;
-    ss.idx = s_idx; ss.k64 = s_k64; ss.ka = s_ka; ss.kb = s_kb; ss.m_rb = s_rb; ss.m_qe = s_qe; ss.m_rid = s_rid; ss.m_w = s_w;
-    ss.nmax = NB; ss.lane = lane;
+    const SortStage ss = tables.stage(lane);
     int *eh_h = ck.long_scratch + (size_t)blockIdx.x * WAVE * 2 * ck.long_stride, *eh_e = eh_h + ck.long_stride;
     int cur_r = 0;
     WaveScorerLong sc{R, dopt.o, ck, lane, eh_h, eh_e, &SB, pm.jobs ? &pm : nullptr, &cur_r};

@@ -8,6 +8,7 @@
 // from a table the host fills with its own libm so that MAPQ cannot differ by an ulp.
 #pragma once
 #include "dev_ext.h"
+#include "dev_as.h"
 
 #define DEV_MINUS_INF (-0x40000000)
 
@@ -139,23 +140,29 @@ __device__ GenCig dev_gen_cigar2(const DevRef &R, const slx_opt &o, const Chunk 
 // SC = the global-alignment scorer: sc(band, l_query, query segment, rb, re) -> bwa_gen_cigar2's score (no CIGAR).
 // One lane with private rows in the lane-per-read kernels, the wave-parallel DP in the wave-per-read one.
 // the tests of mem_patch_reg that come before its global alignment: the band to align with, or -1 = no patch
-__device__ __forceinline__ int dev_patch_pre(const DevRef &R, const slx_opt &o, int64_t a_rb, int64_t a_re, int a_qb, int a_qe, int a_w,
+// (l_pac = R.l_pac and o_w = opt.w by value: the loops that call this keep them in registers)
+__device__ __forceinline__ int dev_patch_pre(int64_t l_pac, int o_w, int64_t a_rb, int64_t a_re, int a_qb, int a_qe, int a_w,
                                              int64_t b_rb, int64_t b_re, int b_qb, int b_qe, int b_w)
 {
     int w;
     double r;
-    if (a_rb < R.l_pac && b_rb >= R.l_pac) return -1;
+    if (a_rb < l_pac && b_rb >= l_pac) return -1;
     if (a_qb >= b_qb || a_qe >= b_qe || a_re >= b_re) return -1;
     w = (int)((a_re - b_rb) - (a_qe - b_qb));
     w = w > 0 ? w : -w;
     r = (double)(a_re - b_rb) / (double)(b_re - a_rb) - (double)(a_qe - b_qb) / (double)(b_qe - a_qb);
     r = r > 0. ? r : -r;
     if (a_re < b_rb || a_qe < b_qb) {
-        if (w > o.w << 1 || r >= (double)0.05f) return -1;
-    } else if (w > o.w << 2 || r >= (double)(0.05f * 2)) return -1;
+        if (w > o_w << 1 || r >= (double)0.05f) return -1;
+    } else if (w > o_w << 2 || r >= (double)(0.05f * 2)) return -1;
     w += a_w + b_w;
-    w = w < o.w << 2 ? w : o.w << 2;
+    w = w < o_w << 2 ? w : o_w << 2;
     return w;
+}
+__device__ __forceinline__ int dev_patch_pre(const DevRef &R, const slx_opt &o, int64_t a_rb, int64_t a_re, int a_qb, int a_qe, int a_w,
+                                             int64_t b_rb, int64_t b_re, int b_qb, int b_qe, int b_w)
+{
+    return dev_patch_pre(R.l_pac, o.w, a_rb, a_re, a_qb, a_qe, a_w, b_rb, b_re, b_qb, b_qe, b_w);
 }
 
 template <int MAXQ, typename SC>
@@ -316,14 +323,28 @@ __device__ inline void dev_mark_primary_alt(const DevRef &R, const slx_opt &opt,
 // unstable and its tie order shows in the output, so the serial algorithm itself is kept; what changes is where it runs: one
 // lane sorts handles against keys held in LDS instead of chasing 96-byte region records through global memory (a
 // 1 000-region read spent ~100 ms in these sorts).
+// The tables are LDS-typed pointers (dev_as.h): the region code runs out of line, where a plain pointer to them is a flat address.
 struct SortStage {
-    int *idx;         // handles being sorted
-    int64_t *k64;     // key by handle: re / rb / hash
-    int *ka, *kb;     // keys by handle: score, qb
-    int64_t *m_rb;    // mirror of the region fields the de-duplication loop reads (by handle); re / score / qb live in k64 / ka / kb
-    int *m_qe, *m_rid, *m_w;
+    lds_ptr<int> idx;         // handles being sorted
+    lds_ptr<int64_t> k64;     // key by handle: re / rb / hash
+    lds_ptr<int> ka, kb;      // keys by handle: score, qb
+    lds_ptr<int64_t> m_rb;    // mirror of the region fields the de-duplication loop reads (by handle); re / score / qb live in k64 / ka / kb
+    lds_ptr<int> m_qe, m_rid, m_w;
     int nmax;         // capacity (handles)
     int lane;
+};
+// the tables of one wave, for the kernels to declare __shared__
+template <int NB>
+struct SortTables {
+    int64_t k64[NB], rb[NB];
+    int idx[NB], ka[NB], kb[NB], qe[NB], rid[NB], w[NB];
+    __device__ __forceinline__ SortStage stage(int lane)
+    {
+        SortStage ss;
+        ss.idx = as_lds(idx); ss.k64 = as_lds(k64); ss.ka = as_lds(ka); ss.kb = as_lds(kb); ss.m_rb = as_lds(rb); ss.m_qe = as_lds(qe); ss.m_rid = as_lds(rid); ss.m_w = as_lds(w);
+        ss.nmax = NB; ss.lane = lane;
+        return ss;
+    }
 };
 
 // The barriers of dev_fin_regs order the LDS traffic of ONE wave (the staged path runs one read per wave).  The contig-length region kernel
@@ -343,50 +364,69 @@ __device__ int dev_fin_regs(const DevRef &R, const Chunk &ck, const slx_opt &opt
         int n = ck.n_reg[r];
         int *a = w.ia;                            // region handles
         DReg *G = w.regs;
-        const bool staged = ss != nullptr && n <= ss->nmax && n >= 2;
+        // R, ck and opt reach this routine by reference, that is in memory, and its loops are chains of dependent reads: what they need of
+        // opt and R is read here, once per read, into scalar registers (the values are the same in every lane of every kernel) ...
+        const int o_max_chain_gap = rfl_i32(opt.max_chain_gap), o_w = rfl_i32(opt.w);
+        const float o_mask_level_redun = rfl_f32(opt.mask_level_redun), o_mask_level = rfl_f32(opt.mask_level);
+        const int64_t l_pac = rfl_i64(R.l_pac);
+        // ... and so are the table bases (one read per wave wherever there is a stage)
+        SortStage S;
+        S.idx = S.ka = S.kb = S.m_qe = S.m_rid = S.m_w = nullptr; S.k64 = S.m_rb = nullptr; S.nmax = 0; S.lane = 0;
+        if (ss) {
+            S.idx = lds_uniform(ss->idx); S.k64 = lds_uniform(ss->k64); S.ka = lds_uniform(ss->ka); S.kb = lds_uniform(ss->kb);
+            S.m_rb = lds_uniform(ss->m_rb); S.m_qe = lds_uniform(ss->m_qe); S.m_rid = lds_uniform(ss->m_rid); S.m_w = lds_uniform(ss->m_w);
+            S.nmax = rfl_i32(ss->nmax); S.lane = ss->lane;
+            n = rfl_i32(n);
+        }
+        const bool staged = ss != nullptr && n <= S.nmax && n >= 2;
+        // the staged loops go to the read's region records and handle list through global-address-space pointers: a store to them is not
+        // waited for by the next LDS read
+        glb_ptr<DReg> Gg = as_glb(G);
+        glb_ptr<int> ag = as_glb(a);
+        if (staged) { Gg = as_glb_uniform(G); ag = as_glb_uniform(a); }
         const bool dbg = ck.dbg_cyc && ck.dbg_stage == 2;
         unsigned long long t0 = dbg ? __builtin_readcyclecounter() : 0ull, t1 = t0, t2 = t0, t3 = t0;
         // sort a[0..m) with `less` over handles: in LDS by one lane when staged (fill(h) copies handle h's keys), else in place
         auto sort_handles = [&](int m, auto fill, auto less_lds, auto less_glb) {
             if (!staged) { ks_introsort_idx(m, a, less_glb); return; }
             __threadfence_block();                                   // a[] and G[] were last written by other lanes' stores
-            for (int i = ss->lane; i < m; i += 64) { const int h = a[i]; ss->idx[i] = h; fill(h); }
+            for (int i = S.lane; i < m; i += 64) { const int h = ag[i]; S.idx[i] = h; fill(h); }
             fin_sync<MAXQ>();
             // When no two keys are equal every correct sort gives klib's order, so the wave counts ranks (64 elements at a time against
             // all m, keys broadcast from LDS): ~m * m / 64 comparisons per lane instead of one lane's m log m at LDS latency.  With a tie
             // anywhere the tie order of ks_introsort shows in the output: then the serial algorithm itself runs, on one lane as before.
             bool tie = m > 768;                                      // (beyond that the quadratic count costs more than it saves on average)
-            if (!tie) for (int e = ss->lane; e < m; e += 64) {
-                const int he = ss->idx[e];
+            if (!tie) for (int e = S.lane; e < m; e += 64) {
+                const int he = S.idx[e];
                 int rank = 0;
                 for (int j = 0; j < m; ++j) {
-                    const int hj = ss->idx[j];
+                    const int hj = S.idx[j];
                     const bool lt = less_lds(hj, he);
                     rank += lt ? 1 : 0;
                     if (!lt && j != e && !less_lds(he, hj)) tie = true;
                 }
-                ss->m_w[e] = rank;                                   // (m_w / m_rid are free during the three sorts)
+                S.m_w[e] = rank;                                   // (m_w / m_rid are free during the three sorts)
             }
             if (!__any(tie)) {
                 fin_sync<MAXQ>();
-                for (int e = ss->lane; e < m; e += 64) ss->m_rid[ss->m_w[e]] = ss->idx[e];
+                for (int e = S.lane; e < m; e += 64) S.m_rid[S.m_w[e]] = S.idx[e];
                 fin_sync<MAXQ>();
-                for (int e = ss->lane; e < m; e += 64) { const int h = ss->m_rid[e]; ss->idx[e] = h; a[e] = h; }
+                for (int e = S.lane; e < m; e += 64) { const int h = S.m_rid[e]; S.idx[e] = h; ag[e] = h; }
             } else {
                 fin_sync<MAXQ>();
-                if (ss->lane == 0) ks_introsort_idx(m, ss->idx, less_lds);
+                if (S.lane == 0) ks_introsort_idx(m, S.idx, less_lds);
                 fin_sync<MAXQ>();
-                for (int i = ss->lane; i < m; i += 64) a[i] = ss->idx[i];
+                for (int i = S.lane; i < m; i += 64) ag[i] = S.idx[i];
             }
             fin_sync<MAXQ>();
             __threadfence_block();
         };
-        if (staged) { for (int i = ss->lane; i < n; i += 64) a[i] = i; __threadfence_block(); }
+        if (staged) { for (int i = S.lane; i < n; i += 64) ag[i] = i; __threadfence_block(); }
         else for (int i = 0; i < n; ++i) a[i] = i;
         // ---------------- mem_sort_dedup_patch
         if (n > 1) {
-            sort_handles(n, [&](int h) { ss->k64[h] = G[h].re; },
-                         [&](int x, int y) { return ss->k64[x] < ss->k64[y]; },
+            sort_handles(n, [&](int h) { S.k64[h] = Gg[h].re; },
+                         [&](int x, int y) { return S.k64[x] < S.k64[y]; },
                          [&](int x, int y) { return G[x].re < G[y].re; });
             if (dbg) t1 = __builtin_readcyclecounter();
             if (defer && !staged && n <= 64) {          // (64 = REGS_SMALL_N: what the wave kernel's launch for these reads stages in LDS)
@@ -403,7 +443,7 @@ __device__ int dev_fin_regs(const DevRef &R, const Chunk &ck, const slx_opt &opt
                     }
                 }
             }
-            if (staged) { for (int i = ss->lane; i < n; i += 64) G[i].n_comp = 1; __threadfence_block(); }
+            if (staged) { for (int i = S.lane; i < n; i += 64) Gg[i].n_comp = 1; __threadfence_block(); }
             else for (int i = 0; i < n; ++i) G[a[i]].n_comp = 1;
             if (staged) {
                 // The reads that come here have ~1 000 regions from one repeat tract: the window of the scalar j-loop is "every region
@@ -411,26 +451,30 @@ __device__ int dev_fin_regs(const DevRef &R, const Chunk &ck, const slx_opt &opt
                 // each lane classifies its q against the current p; removals of q's (which do not change p) that precede the first
                 // p-changing event in j order are applied together; that event (p removed / a patch attempt, whose alignment runs on
                 // the whole wave) is then handled alone and the scan resumes below it with the new p.
-                const int lane = ss->lane;
-                int64_t *m_re = ss->k64; int *m_sc = ss->ka, *m_qb = ss->kb;
+                const int lane = S.lane;
+                const lds_ptr<int64_t> m_re = S.k64; const lds_ptr<int> m_sc = S.ka, m_qb = S.kb;
                 for (int h = lane; h < n; h += 64) {
-                    const DReg &g = G[h];
-                    ss->m_rb[h] = g.rb; m_re[h] = g.re; m_qb[h] = g.qb; ss->m_qe[h] = g.qe; ss->m_rid[h] = g.rid; m_sc[h] = g.score; ss->m_w[h] = g.w;
+                    const glb_ptr<const DReg> g = Gg + h;
+                    S.m_rb[h] = g->rb; m_re[h] = g->re; m_qb[h] = g->qb; S.m_qe[h] = g->qe; S.m_rid[h] = g->rid; m_sc[h] = g->score; S.m_w[h] = g->w;
                 }
                 fin_sync<MAXQ>();
                 for (int i = 1; i < n; ++i) {
-                    const int ph = ss->idx[i], prevh = ss->idx[i - 1];
-                    if (ss->m_rid[ph] != ss->m_rid[prevh] || ss->m_rb[ph] >= m_re[prevh] + opt.max_chain_gap) continue;
+                    const int ph = S.idx[i], prevh = S.idx[i - 1];
+                    // p's fields live in registers across the scan: they change only at an event (a patch), where they are read again
+                    int64_t p_rb = S.m_rb[ph];
+                    const int p_rid = S.m_rid[ph];
+                    if (p_rid != S.m_rid[prevh] || p_rb >= m_re[prevh] + o_max_chain_gap) continue;
+                    const int64_t p_re = m_re[ph];
+                    const int p_qe = S.m_qe[ph];
+                    int p_qb = m_qb[ph], p_sc = m_sc[ph], p_w = S.m_w[ph];
                     int jtop = i - 1;
                     while (jtop >= 0) {
-                        const int64_t p_rb = ss->m_rb[ph], p_re = m_re[ph];
-                        const int p_qb = m_qb[ph], p_qe = ss->m_qe[ph], p_rid = ss->m_rid[ph], p_sc = m_sc[ph], p_w = ss->m_w[ph];
                         const int j = jtop - lane;
                         const bool valid = j >= 0;
-                        const int qh = ss->idx[valid ? j : 0];
-                        const int64_t q_rb = ss->m_rb[qh], q_re = m_re[qh];
-                        const int q_qb = m_qb[qh], q_qe = ss->m_qe[qh], q_sc = m_sc[qh], q_w = ss->m_w[qh];
-                        const bool cond = valid && p_rid == ss->m_rid[qh] && p_rb < q_re + opt.max_chain_gap;
+                        const int qh = S.idx[valid ? j : 0];
+                        const int64_t q_rb = S.m_rb[qh], q_re = m_re[qh];
+                        const int q_qb = m_qb[qh], q_qe = S.m_qe[qh], q_sc = m_sc[qh], q_w = S.m_w[qh];
+                        const bool cond = valid && p_rid == S.m_rid[qh] && p_rb < q_re + o_max_chain_gap;
                         const unsigned long long stopm = __ballot(!cond);
                         const int first_stop = stopm ? (int)__ffsll((long long)stopm) - 1 : 64;
                         const bool live = lane < first_stop;
@@ -440,12 +484,12 @@ __device__ int dev_fin_regs(const DevRef &R, const Chunk &ck, const slx_opt &opt
                             const int64_t oq = q_qb < p_qb ? q_qe - p_qb : p_qe - q_qb;
                             const int64_t mr = q_re - q_rb < p_re - p_rb ? q_re - q_rb : p_re - p_rb;
                             const int64_t mq = q_qe - q_qb < p_qe - p_qb ? q_qe - q_qb : p_qe - p_qb;
-                            if ((float)orr > opt.mask_level_redun * (float)mr && (float)oq > opt.mask_level_redun * (float)mq) cat = p_sc < q_sc ? 2 : 1;
-                            else if (q_rb < p_rb && dev_patch_pre(R, opt, q_rb, q_re, q_qb, q_qe, q_w, p_rb, p_re, p_qb, p_qe, p_w) >= 0) cat = 3;
+                            if ((float)orr > o_mask_level_redun * (float)mr && (float)oq > o_mask_level_redun * (float)mq) cat = p_sc < q_sc ? 2 : 1;
+                            else if (q_rb < p_rb && dev_patch_pre(l_pac, o_w, q_rb, q_re, q_qb, q_qe, q_w, p_rb, p_re, p_qb, p_qe, p_w) >= 0) cat = 3;
                         }
                         const unsigned long long evm = __ballot(cat >= 2);
                         const int first_ev = evm ? (int)__ffsll((long long)evm) - 1 : 64;
-                        if (cat == 1 && lane < first_ev) { ss->m_qe[qh] = q_qb; G[qh].qe = q_qb; }        // q.qe = q.qb
+                        if (cat == 1 && lane < first_ev) S.m_qe[qh] = q_qb;        // q.qe = q.qb (in the mirror; G[] gets it after the scan, see below)
                         fin_sync<MAXQ>();
                         if (first_ev == 64) {                // no p-changing event among the live lanes
                             if (first_stop < 64) break;
@@ -455,7 +499,7 @@ __device__ int dev_fin_regs(const DevRef &R, const Chunk &ck, const slx_opt &opt
                         const int ev_cat = __builtin_amdgcn_readlane(cat, first_ev);
                         const int ev_q = __builtin_amdgcn_readlane(qh, first_ev);
                         if (ev_cat == 2) {                   // p.qe = p.qb; break
-                            if (lane == 0) { ss->m_qe[ph] = p_qb; G[ph].qe = p_qb; }
+                            if (lane == 0) S.m_qe[ph] = p_qb;
                             fin_sync<MAXQ>();
                             break;
                         }
@@ -474,15 +518,20 @@ __device__ int dev_fin_regs(const DevRef &R, const Chunk &ck, const slx_opt &opt
                                 pp.w = ww;
                                 q.qb = q.qe;
                                 if (lane == 0) {
-                                    m_qb[ph] = m_qb[ev_q]; ss->m_rb[ph] = ss->m_rb[ev_q]; m_sc[ph] = score; ss->m_w[ph] = ww;
-                                    m_qb[ev_q] = ss->m_qe[ev_q];
+                                    m_qb[ph] = m_qb[ev_q]; S.m_rb[ph] = S.m_rb[ev_q]; m_sc[ph] = score; S.m_w[ph] = ww;
+                                    m_qb[ev_q] = S.m_qe[ev_q];
                                 }
                                 fin_sync<MAXQ>();
+                                p_rb = S.m_rb[ph]; p_qb = m_qb[ph]; p_sc = m_sc[ph]; p_w = S.m_w[ph];       // the new p (re, qe and rid stay)
                             }
                         }
                         jtop -= first_ev + 1;                // resume just below the event with the (possibly new) p
                     }
                 }
+                // A removal (qe = qb) went to the mirror only.  Nothing in the scan reads the qe of a removed region from G[]: mem_patch_reg is handed
+                // p, which ends the scan when it is removed, and a q that is still there.  So the records get their qe once, here, and a step of
+                // the scan holds no store to HBM at all.
+                for (int h = lane; h < n; h += 64) Gg[h].qe = S.m_qe[h];
                 __threadfence_block();
             } else
             for (int i = 1; i < n; ++i) {
@@ -513,16 +562,16 @@ __device__ int dev_fin_regs(const DevRef &R, const Chunk &ck, const slx_opt &opt
                 }
             }
             if (dbg) t2 = __builtin_readcyclecounter();
-            // lane-parallel compaction of the handle list when staged: ss->idx still holds a[] and kb / m_qe mirror qb / qe
+            // lane-parallel compaction of the handle list when staged: S.idx still holds a[] and kb / m_qe mirror qb / qe
             auto compact_staged = [&](int n_in, int first_forced) {
                 int m = 0;
                 for (int base = 0; base < n_in; base += 64) {
-                    const int i = base + ss->lane;
-                    const int h = i < n_in ? ss->idx[i] : 0;
-                    const bool keep = i < n_in && (i < first_forced || ss->m_qe[h] > ss->kb[h]);
+                    const int i = base + S.lane;
+                    const int h = i < n_in ? S.idx[i] : 0;
+                    const bool keep = i < n_in && (i < first_forced || S.m_qe[h] > S.kb[h]);
                     const unsigned long long km = __ballot(keep);
                     const int pos = m + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(km >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)km, 0u));
-                    if (keep) a[pos] = h;                          // pos <= i, and the source is the LDS copy
+                    if (keep) ag[pos] = h;                         // pos <= i, and the source is the LDS copy
                     m += (int)__popcll(km);
                 }
                 __threadfence_block();
@@ -532,20 +581,20 @@ __device__ int dev_fin_regs(const DevRef &R, const Chunk &ck, const slx_opt &opt
             if (staged) m = compact_staged(n, 0);
             else for (int i = 0; i < n; ++i) if (G[a[i]].qe > G[a[i]].qb) a[m++] = a[i];
             n = m;
-            sort_handles(n, [&](int h) { ss->ka[h] = G[h].score; ss->k64[h] = G[h].rb; ss->kb[h] = G[h].qb; },
+            sort_handles(n, [&](int h) { S.ka[h] = Gg[h].score; S.k64[h] = Gg[h].rb; S.kb[h] = Gg[h].qb; },
                          [&](int x, int y) {
-                             const int sx = ss->ka[x], sy = ss->ka[y];
-                             const int64_t bx = ss->k64[x], by = ss->k64[y];
-                             return sx > sy || (sx == sy && (bx < by || (bx == by && ss->kb[x] < ss->kb[y])));
+                             const int sx = S.ka[x], sy = S.ka[y];
+                             const int64_t bx = S.k64[x], by = S.k64[y];
+                             return sx > sy || (sx == sy && (bx < by || (bx == by && S.kb[x] < S.kb[y])));
                          },
                          [&](int x, int y) {
                              const DReg &X = G[x], &Y = G[y];
                              return X.score > Y.score || (X.score == Y.score && (X.rb < Y.rb || (X.rb == Y.rb && X.qb < Y.qb)));
                          });
             if (staged) {                                         // keys of the sort are in LDS by handle; the tests do not read what they change
-                for (int i = 1 + ss->lane; i < n; i += 64) {
-                    const int h = ss->idx[i], hp = ss->idx[i - 1];
-                    if (ss->ka[h] == ss->ka[hp] && ss->k64[h] == ss->k64[hp] && ss->kb[h] == ss->kb[hp]) { G[h].qe = ss->kb[h]; ss->m_qe[h] = ss->kb[h]; }
+                for (int i = 1 + S.lane; i < n; i += 64) {
+                    const int h = S.idx[i], hp = S.idx[i - 1];
+                    if (S.ka[h] == S.ka[hp] && S.k64[h] == S.k64[hp] && S.kb[h] == S.kb[hp]) { Gg[h].qe = S.kb[h]; S.m_qe[h] = S.kb[h]; }
                 }
                 fin_sync<MAXQ>();
                 n = compact_staged(n, 1);
@@ -566,34 +615,34 @@ __device__ int dev_fin_regs(const DevRef &R, const Chunk &ck, const slx_opt &opt
             int tmp = opt.a + opt.b;
             tmp = opt.o_del + opt.e_del > tmp ? opt.o_del + opt.e_del : tmp;
             tmp = opt.o_ins + opt.e_ins > tmp ? opt.o_ins + opt.e_ins : tmp;
-            // mem_mark_primary_se_core over ss->idx[0..m) on the wave.  The scan over the primaries found so far (z) is the serial
+            // mem_mark_primary_se_core over S.idx[0..m) on the wave.  The scan over the primaries found so far (z) is the serial
             // part: for a many-region read it is a few hundred entries long.  Region fields come from LDS (kb = qb, m_qe = qe, ka = score,
             // by handle; l_alt = is_alt by handle on an ALT-aware index), 64 primaries are tested per step and a ballot finds the first
             // that overlaps, as the scalar loop would; sub / sub_n / secondary are kept in LDS (m_rid, m_w and the two halves of k64, free
             // after a sort) and written back once.
-            auto core_staged = [&](int m, const int *l_alt) {
-                const int lane = ss->lane;
-                int *l_sub = ss->m_rid, *l_subn = ss->m_w, *l_sec = (int *)ss->k64, *l_z = (int *)ss->k64 + ss->nmax;
+            auto core_staged = [&](int m, lds_ptr<const int> l_alt) {
+                const int lane = S.lane;
+                const lds_ptr<int> l_sub = S.m_rid, l_subn = S.m_w, l_sec = (lds_ptr<int>)S.k64, l_z = (lds_ptr<int>)S.k64 + S.nmax;
                 fin_sync<MAXQ>();
-                for (int i = lane; i < m; i += 64) { const int h = ss->idx[i]; l_sub[h] = 0; l_subn[h] = G[h].sub_n; l_sec[h] = -1; }
+                for (int i = lane; i < m; i += 64) { const int h = S.idx[i]; l_sub[h] = 0; l_subn[h] = Gg[h].sub_n; l_sec[h] = -1; }
                 if (lane == 0) l_z[0] = 0;
                 fin_sync<MAXQ>();
                 int nz = 1;
                 for (int i = 1; i < m; ++i) {
-                    const int hi = ss->idx[i];
-                    const int i_qb = ss->kb[hi], i_qe = ss->m_qe[hi], i_sc = ss->ka[hi];
+                    const int hi = S.idx[i];
+                    const int i_qb = S.kb[hi], i_qe = S.m_qe[hi], i_sc = S.ka[hi];
                     int found = -1;
                     for (int kb0 = 0; kb0 < nz && found < 0; kb0 += 64) {
                         const int k = kb0 + lane;
                         bool hit = false;
                         if (k < nz) {
-                            const int hj = ss->idx[l_z[k]];
-                            const int j_qb = ss->kb[hj], j_qe = ss->m_qe[hj];
+                            const int hj = S.idx[l_z[k]];
+                            const int j_qb = S.kb[hj], j_qe = S.m_qe[hj];
                             const int b_max = j_qb > i_qb ? j_qb : i_qb;
                             const int e_min = j_qe < i_qe ? j_qe : i_qe;
                             if (e_min > b_max) {
                                 const int min_l = i_qe - i_qb < j_qe - j_qb ? i_qe - i_qb : j_qe - j_qb;
-                                hit = (float)(e_min - b_max) >= (float)min_l * opt.mask_level;
+                                hit = (float)(e_min - b_max) >= (float)min_l * o_mask_level;
                             }
                         }
                         const unsigned long long hm = __ballot(hit);
@@ -602,15 +651,15 @@ __device__ int dev_fin_regs(const DevRef &R, const Chunk &ck, const slx_opt &opt
                     if (found >= 0) {
                         if (lane == 0) {
                             const int zi = l_z[found];
-                            const int hj = ss->idx[zi];
+                            const int hj = S.idx[zi];
                             if (l_sub[hj] == 0) l_sub[hj] = i_sc;
-                            if (ss->ka[hj] - i_sc <= tmp && (!l_alt || l_alt[hj] || !l_alt[hi])) ++l_subn[hj];
+                            if (S.ka[hj] - i_sc <= tmp && (!l_alt || l_alt[hj] || !l_alt[hi])) ++l_subn[hj];
                             l_sec[hi] = zi;
                         }
                     } else { if (lane == 0) l_z[nz] = i; ++nz; }
                     fin_sync<MAXQ>();
                 }
-                for (int i = lane; i < m; i += 64) { const int h = ss->idx[i]; DReg &p = G[h]; p.sub = l_sub[h]; p.sub_n = l_subn[h]; p.secondary = l_sec[h]; }
+                for (int i = lane; i < m; i += 64) { const int h = S.idx[i]; const glb_ptr<DReg> p = Gg + h; p->sub = l_sub[h]; p->sub_n = l_subn[h]; p->secondary = l_sec[h]; }
                 __threadfence_block();
                 fin_sync<MAXQ>();
             };
@@ -618,52 +667,53 @@ __device__ int dev_fin_regs(const DevRef &R, const Chunk &ck, const slx_opt &opt
                 // ALT-aware index, many regions: bwa's two-round marking (dev_mark_primary_alt has the serial statement) with the sorts
                 // and both rounds of the core on the wave.  l_alt / l_par (is_alt and the first round's parent, by handle) live in the
                 // two halves of m_rb, which nothing reads after the de-duplication.
-                const int lane = ss->lane;
-                int *l_alt = (int *)ss->m_rb, *l_par = (int *)ss->m_rb + ss->nmax, *par = (int *)w.srt;
+                const int lane = S.lane;
+                const lds_ptr<int> l_alt = (lds_ptr<int>)S.m_rb, l_par = (lds_ptr<int>)S.m_rb + S.nmax;
+                const glb_ptr<int> par = as_glb_uniform((int *)w.srt);
                 fin_sync<MAXQ>();
                 int n_pri = 0;
                 for (int base = 0; base < n; base += 64) {
                     const int i = base + lane;
                     bool pri = false;
                     if (i < n) {
-                        const int h = a[i];
-                        DReg &p = G[h];
-                        p.sub = 0; p.secondary = -1; p.hash = dev_hash_64(id + (uint64_t)i);
-                        const int al = ref_is_alt(R, p.rid);
+                        const int h = ag[i];
+                        const glb_ptr<DReg> p = Gg + h;
+                        p->sub = 0; p->secondary = -1; p->hash = dev_hash_64(id + (uint64_t)i);
+                        const int al = ref_is_alt(R, p->rid);
                         l_alt[h] = al;
                         pri = !al;
                     }
                     n_pri += (int)__popcll(__ballot(pri));
                 }
                 __threadfence_block();
-                sort_handles(n, [&](int h) { ss->ka[h] = G[h].score; ss->k64[h] = (int64_t)G[h].hash; },
+                sort_handles(n, [&](int h) { S.ka[h] = Gg[h].score; S.k64[h] = (int64_t)Gg[h].hash; },
                              [&](int x, int y) {
-                                 const int sx = ss->ka[x], sy = ss->ka[y];
+                                 const int sx = S.ka[x], sy = S.ka[y];
                                  if (sx != sy) return sx > sy;
                                  const int ax = l_alt[x], ay = l_alt[y];
-                                 return ax < ay || (ax == ay && (uint64_t)ss->k64[x] < (uint64_t)ss->k64[y]);
+                                 return ax < ay || (ax == ay && (uint64_t)S.k64[x] < (uint64_t)S.k64[y]);
                              },
                              [&](int x, int y) { return false; });
                 core_staged(n, l_alt);
                 if (n_pri < n) {
-                    for (int i = lane; i < n; i += 64) { const int h = ss->idx[i], sidx = G[h].secondary; l_par[h] = sidx >= 0 ? ss->idx[sidx] : -1; }
+                    for (int i = lane; i < n; i += 64) { const int h = S.idx[i], sidx = Gg[h].secondary; l_par[h] = sidx >= 0 ? S.idx[sidx] : -1; }
                     fin_sync<MAXQ>();
                     if (n_pri > 0)
-                        sort_handles(n, [&](int h) { ss->ka[h] = G[h].score; ss->k64[h] = (int64_t)G[h].hash; },
+                        sort_handles(n, [&](int h) { S.ka[h] = Gg[h].score; S.k64[h] = (int64_t)Gg[h].hash; },
                                      [&](int x, int y) {
                                          const int ax = l_alt[x], ay = l_alt[y];
                                          if (ax != ay) return ax < ay;
-                                         const int sx = ss->ka[x], sy = ss->ka[y];
-                                         return sx > sy || (sx == sy && (uint64_t)ss->k64[x] < (uint64_t)ss->k64[y]);
+                                         const int sx = S.ka[x], sy = S.ka[y];
+                                         return sx > sy || (sx == sy && (uint64_t)S.k64[x] < (uint64_t)S.k64[y]);
                                      },
                                      [&](int x, int y) { return false; });
-                    int *l_rank = (int *)ss->k64;                     // handle -> rank in the final order (the hashes are done with)
+                    const lds_ptr<int> l_rank = (lds_ptr<int>)S.k64;                    // handle -> rank in the final order (the hashes are done with)
                     fin_sync<MAXQ>();
-                    for (int i = lane; i < n; i += 64) l_rank[ss->idx[i]] = i;
+                    for (int i = lane; i < n; i += 64) l_rank[S.idx[i]] = i;
                     fin_sync<MAXQ>();
                     for (int i = lane; i < n; i += 64) {
-                        const int h = ss->idx[i], ph = l_par[h];
-                        if (ph >= 0) { par[h] = l_rank[ph]; if (l_alt[h]) G[h].secondary = 0x7fffffff; }
+                        const int h = S.idx[i], ph = l_par[h];
+                        if (ph >= 0) { par[h] = l_rank[ph]; if (l_alt[h]) Gg[h].secondary = 0x7fffffff; }
                         else par[h] = -1;
                     }
                     if (n_pri > 0) {
@@ -671,24 +721,24 @@ __device__ int dev_fin_regs(const DevRef &R, const Chunk &ck, const slx_opt &opt
                         core_staged(n_pri, l_alt);                    // (resets sub / secondary of the primary-assembly hits, carries sub_n)
                     }
                 } else
-                    for (int i = lane; i < n; i += 64) { const int h = ss->idx[i]; par[h] = G[h].secondary; }
+                    for (int i = lane; i < n; i += 64) { const int h = S.idx[i]; par[h] = Gg[h].secondary; }
                 __threadfence_block();
                 fin_sync<MAXQ>();
             } else if (R.ann_alt) {
                 dev_mark_primary_alt(R, opt, w, n, id);              // one region list per lane: the serial statement
             } else {
             if (staged) {
-                for (int i = ss->lane; i < n; i += 64) { DReg &p = G[a[i]]; p.sub = 0; p.secondary = -1; p.hash = dev_hash_64(id + (uint64_t)i); }
+                for (int i = S.lane; i < n; i += 64) { const glb_ptr<DReg> p = Gg + ag[i]; p->sub = 0; p->secondary = -1; p->hash = dev_hash_64(id + (uint64_t)i); }
                 __threadfence_block();
             } else for (int i = 0; i < n; ++i) {
                 DReg &p = G[a[i]];
                 p.sub = 0; p.secondary = -1;
                 p.hash = dev_hash_64(id + (uint64_t)i);
             }
-            sort_handles(n, [&](int h) { ss->ka[h] = G[h].score; ss->k64[h] = (int64_t)G[h].hash; },
+            sort_handles(n, [&](int h) { S.ka[h] = Gg[h].score; S.k64[h] = (int64_t)Gg[h].hash; },
                          [&](int x, int y) {
-                             const int sx = ss->ka[x], sy = ss->ka[y];
-                             return sx > sy || (sx == sy && (uint64_t)ss->k64[x] < (uint64_t)ss->k64[y]);
+                             const int sx = S.ka[x], sy = S.ka[y];
+                             return sx > sy || (sx == sy && (uint64_t)S.k64[x] < (uint64_t)S.k64[y]);
                          },
                          [&](int x, int y) {
                              const DReg &X = G[x], &Y = G[y];

@@ -320,11 +320,13 @@ __device__ void dev_regs_read(const DevRef &R, const Chunk &ck, const slx_opt &o
     int nh = 0;
     if (ss) {                                         // wave per read: one region per lane, slots by a ballot prefix
         const bool drop_sec = !ck.sam_mode && (ck.keepSecFrac < 0.0 || ck.keepSecFrac > 1.0);
+        const glb_ptr<const DReg> Gg = as_glb_uniform(G);        // (one read per wave: scalar bases, global_ loads)
+        const glb_ptr<const int> ag = as_glb_uniform(a);
         for (int base = 0; base < n; base += 64) {
             const int i = base + ss->lane;
             DReg ar;
             bool keep = false;
-            if (i < n) { ar = G[a[i]]; keep = !(ar.secondary != 0 && drop_sec); }
+            if (i < n) { ar = glb_load<DReg>(Gg + ag[i]); keep = !(ar.secondary != 0 && drop_sec); }
             const unsigned long long km = __ballot(keep);
             const int pos = nh + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(km >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)km, 0u));
             if (keep) dev_reg_emit(ck, opt, fl, r, so + pos, ar, true);
@@ -415,12 +417,9 @@ template <int MAXQ, int NB>
 __global__ void __launch_bounds__(64) k_regs_wave(DevRef R, Chunk ck, DevOpt dopt, FinLists fl, const int *order, unsigned int *queue, const unsigned int *n_slots,
                                                   int min_regs, int max_regs)
 {
-    __shared__ int s_idx[NB], s_ka[NB], s_kb[NB], s_qe[NB], s_rid[NB], s_w[NB];
-    __shared__ int64_t s_k64[NB], s_rb[NB];
+    __shared__ SortTables<NB> tables;
     const int lane = threadIdx.x;
-    SortStage ss;
-    ss.idx = s_idx; ss.k64 = s_k64; ss.ka = s_ka; ss.kb = s_kb; ss.m_rb = s_rb; ss.m_qe = s_qe; ss.m_rid = s_rid; ss.m_w = s_w;
-    ss.nmax = NB; ss.lane = lane;
+    const SortStage ss = tables.stage(lane);
     const MatRows mr = make_matrows(dopt.o.mat);
     const int n_todo = __builtin_amdgcn_readfirstlane((int)*n_slots);
     for (;;) {
