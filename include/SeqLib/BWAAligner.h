@@ -34,6 +34,7 @@
 #include <deque>
 #include <exception>
 #include <functional>
+#include <iterator>
 #include <memory>
 #include <mutex>
 #include <stdexcept>
@@ -51,6 +52,7 @@
 #include "SeqLib/BWAIndex.h"
 #include "SeqLib/BamRecord.h"
 #include "SeqLib/BamReader.h"
+#include "SeqLib/FastqReader.h"
 #include "SeqLib/BamWriter.h"
 #include "SeqLib/UnalignedSequence.h"
 
@@ -495,6 +497,52 @@ public:
             slx_rec_batch rbat;
             throw_rc(slx_rec_build_from_bam(rb, &dh, reader.rd_, &b, hardclip ? 1 : 0, &rbat));
             if (rbat.n_bytes && !w.WriteDevice(rbat.d_stream, rbat.n_bytes, rbat.d_rec_off, rbat.n_records)) throw std::runtime_error(std::string("BWAAligner::alignToBam(BamReader&): ") + slx_last_error());
+            written += (size_t)rbat.n_records;
+        }
+        return written;
+    }
+    // ---- from a FASTA / FASTQ file (new): the reader's batches (FastqReader::NextBatch, parsed on the GPU) instead of a vector filled one GetNextSequence at a time.
+    // out gets one vector per read, in file order; read i of the file takes the lrand48 ordinal of the i-th successive call.  The records are host objects, so
+    // every batch comes down once (NextBatch(UnalignedSequenceVector&)) and goes through the batch entry above.  Throws as NextBatch and alignSequences do.
+    void alignSequences(FastqReader &reader, std::vector<BamRecordPtrVector> &out, bool hardclip, double keepSecFrac, int maxSecondary, size_t max_bytes = 64 << 20) const
+    {
+        out.clear();
+        if (index_->IsEmpty()) return;
+        Flush();
+        UnalignedSequenceVector reads;
+        std::vector<BamRecordPtrVector> part;
+        while (reader.NextBatch(reads, max_bytes)) {
+            part.clear();
+            part.resize(reads.size());
+            run_batch(reads, part, hardclip, keepSecFrac, maxSecondary);
+            out.insert(out.end(), std::make_move_iterator(part.begin()), std::make_move_iterator(part.end()));
+        }
+    }
+    // FASTQ -> BAM with nothing per read on the host: the batch is parsed into HBM (slx_fastq_next), aligned where it lies, its records are built from the
+    // device-resident hits and the batch's own names (slx_rec_build) and handed to the GPU deflater.  From the same lrand48 state the file is byte for byte the one
+    // alignToBam(reads, ...) writes for the reads of a GetNextSequence loop.  Comments (BC:Z) are not carried, as there.
+    size_t alignToBam(FastqReader &reader, BamWriter &w, bool hardclip, double keepSecFrac, int maxSecondary, size_t max_bytes = 64 << 20) const
+    {
+        check_bam_target(w);
+        if (index_->IsEmpty()) return 0;
+        Flush();
+        slx_aligner *al = handle();
+        slx_rec *rb = builder();
+        size_t written = 0;
+        FastqBatch b;
+        while (reader.NextBatch(b, max_bytes)) {
+            const int64_t n = b.dev.n_reads;
+            uint64_t state;
+            {
+                std::lock_guard<std::mutex> g(rng_mutex());
+                state = slx_lrand48_peek_libc();
+                slx_lrand48_skip_libc((uint64_t)n);
+            }
+            slx_hits dh;
+            throw_rc(slx_align_batch_device(al, &memopt_, b.dev.d_bases, b.dev.d_offs, n, state, 0, hardclip ? 1 : 0, keepSecFrac, maxSecondary, &dh));
+            slx_rec_batch rbat;
+            throw_rc(slx_rec_build(rb, &dh, b.dev.d_bases, b.dev.d_offs, b.dev.d_names, b.dev.d_name_offs, hardclip ? 1 : 0, &rbat));
+            if (rbat.n_bytes && !w.WriteDevice(rbat.d_stream, rbat.n_bytes, rbat.d_rec_off, rbat.n_records)) throw std::runtime_error(std::string("BWAAligner::alignToBam(FastqReader&): ") + slx_last_error());
             written += (size_t)rbat.n_records;
         }
         return written;

@@ -291,3 +291,12 @@ INF_FN uint32_t inf_crc_part(const uint32_t *tab, const uint8_t *p, uint32_t n, 
     if (e == a) return 0;
     return inf_crc_shift(inf_crc_bytes(tab, p + a, e - a), n - e);
 }
+
+#if defined(__HIPCC__)
+// ---- the launch of k_bgzf_inflate + k_bgzf_crc (slx_bam.hip), for the other translation units that inflate BGZF members (slx_fastq.hip) ----
+#include <hip/hip_runtime.h>
+// one member: its deflate stream lies at comp + in_off (in_len bytes), its isize bytes go to out + out_off, crc is its trailer's
+struct bam_mdesc { uint64_t in_off, out_off; uint32_t in_len, isize, crc, pad; };
+// both kernels on st over the n members of d_desc (one wave per member), everything in HBM: d_err[i] = INF_OK or an INF_E_* code.  The launches' hipGetLastError()
+hipError_t slx_bgzf_inflate_launch(hipStream_t st, const uint8_t *d_comp, uint64_t comp_bytes, const bam_mdesc *d_desc, int n, uint8_t *d_out, uint64_t out_bytes, uint32_t *d_err);
+#endif

@@ -31,8 +31,6 @@
 #define BAM_HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { slx_set_error("HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, __LINE__); return SLX_ENODEVICE; } } while (0)
 #define BAM_CHK(x) do { const int rc_ = (x); if (rc_ != SLX_OK) return rc_; } while (0)
 
-struct bam_mdesc { uint64_t in_off, out_off; uint32_t in_len, isize, crc, pad; };
-
 // ------------------------------------------------------------------ kernels
 __global__ __launch_bounds__(256) void k_bgzf_inflate(const uint8_t *comp, uint64_t comp_bytes, const bam_mdesc *m, int n, uint8_t *out, uint64_t out_bytes, uint32_t *err)
 {
@@ -60,6 +58,14 @@ __global__ __launch_bounds__(256) void k_bgzf_crc(const bam_mdesc *m, int n, con
     uint32_t c = inf_crc_part(tab, out + d.out_off, d.isize, lane, 64);
     for (int o = 32; o; o >>= 1) c ^= __shfl_xor(c, o, 64);
     if (lane == 0 && c != d.crc) err[idx] = INF_E_CRC;
+}
+
+hipError_t slx_bgzf_inflate_launch(hipStream_t st, const uint8_t *d_comp, uint64_t comp_bytes, const bam_mdesc *d_desc, int n, uint8_t *d_out, uint64_t out_bytes, uint32_t *d_err)
+{
+    if (n <= 0) return hipSuccess;
+    k_bgzf_inflate<<<(n + 3) / 4, 256, 0, st>>>(d_comp, comp_bytes, d_desc, n, d_out, out_bytes, d_err);
+    k_bgzf_crc<<<(n + 3) / 4, 256, 0, st>>>(d_desc, n, d_out, out_bytes, d_err);
+    return hipGetLastError();
 }
 
 // state of the index: [0] records, [1] repaired chunks, [2] lowest start of a record with block_size < 32, [3] end of the last whole record, [4] changed (rounds)
