@@ -141,6 +141,11 @@ void slx_aligner_free(slx_aligner *al);
  *                             maximum, with every remaining query column a match, can no longer change the score, the band trials' max_off or which end of the
  *                             alignment (local, or to the query's end) the region takes; only where the band never clips the row (band + 1 >= query length).
  *                             Same records; 0: the loops run to z-drop, an all-zero row or the tail bound
+ *   "ext_narrow" 0..3 (1)      a top-seed extension of a light read whose flank loses L <= 20 (default penalties) against a perfect match on its main diagonal, and starts
+ *                             above L, runs its dynamic program in the band floor((L - o) / e) instead of "w": no path outside it can reach a row's maximum (k_first_diag
+ *                             measures L; k_first_lanes clamps).  1: the jobs whose sides all have such a band run in a launch of their own on rows of 32 columns;
+ *                             2: the band only; 3: as 1, the narrow jobs binned by sqrt(left^2 + right^2) like the others (1 bins them by bases x band width).
+ *                             Same records; 0: every job in the band "w"
  *   "first_lanes" 0|1 (1)     the other top-seed extensions of the light reads (the dynamic program) one lane per job, binned by work (k_first_lanes); 0: one wave per job (k_ext_first)
  *   "lane_narrow" 0|1 (1)     k_ext_lanes keeps 8-bit H / E cells when no score can reach 256
  *   "p2_coop" 0|1 (1)         seeding pass 2: re-seeding calls inside repeats one wave per call (k_seed2_coop); needs p2_items
@@ -248,6 +253,8 @@ int  slx_aligner_probe_launches(const slx_aligner *al);
  * "chain_lds_reads" / "chain_lds_bail" = reads of the last batch whose chaining finished in LDS / gave the LDS pass up (a 10th chain) and ran again on the HBM columns;
  * "first_lane_jobs" = top-seed extensions of the last batch that k_first_lanes ran (the dynamic program, one lane per job), as the kernel counted them;
  * "walk_staged_chains" = chains of the last batch that k_extend_reg opened from a lane-made header ("walk_stage"; 0 with the knob off);
+ * "ext_narrow_sides" / "ext_narrow_jobs" = of the sides of k_first_lanes' jobs of the last batch that the diagonal does not answer, the ones given a narrow band /
+ * the jobs whose sides all fit the narrow launch's 32 columns ("ext_narrow"; both 0 with the knob off);
  * "ext_row_exits" = dynamic programs of the last batch's short-read extension kernels (band trials, in the lane kernels) that the row exit ended ("ext_row_exit"; 0 with the knob off) */
 int64_t slx_aligner_counter(const slx_aligner *al, const char *key);
 

@@ -94,6 +94,31 @@ __device__ __forceinline__ MatRows make_matrows(const int8_t *mat)
 //            and every later h1 is <= max - pen_clip.  A gscore that was above max - pen_clip cannot change (an update needs h1 >= gscore); one that
 //            was not stays at or below it, so `gscore <= 0 || gscore <= score - pen_clip` holds with and without the later rows, and that branch of
 //            dev_extend_core / lane_extend_core reads qle and tle only.  gscore / gtle may differ from ksw_extend2's there and nowhere else.
+//
+// The narrow band: a flank that loses little on its main diagonal needs no band beyond that loss (ext_narrow_band, dev_lane_rows.h; lane_rows_extend
+// clamps both band trials to it -- LaneSide::wband).  Let L be what the flank's main diagonal loses against a perfect match, the sum over the query of
+// amax - mat[t_p][q_p] (diag_extend's `loss`), and let h0 > L and tlen >= qlen.  The diagonal cell of row i < qlen then holds at least
+// h0 + (i + 1) * amax - L > 0: the diagonal never dies.  A path whose largest excursion from the main diagonal is d columns pays at least o + d * e for it
+// and has taken at most i + 1 diagonal steps by row i, so it holds at most h0 + (i + 1) * amax - o - d * e: with o + d * e > L that is strictly below the
+// diagonal cell of its row, and from column qlen - 1 on strictly below the diagonal's end, h0 + qlen * amax - L.  So every row's maximum and every cell
+// that attains it (the last arg-max with them), the running maximum with max_i / max_j, max_off, and gscore / gtle -- an update needs a cell of the last
+// column >= gscore, and the diagonal's end is one -- are decided by paths of excursion at most
+//     w' = floor((L - o) / e),     the larger of the two for (o_ins, e_ins) and (o_del, e_del) (< 0: that kind of gap allows none).
+// ksw_extend2 with band w' computes exactly the cells |j - i| <= w', and a cell's value there is at least that of its best path inside the band: the
+// six results are those of any wider band.  What the loop's own bookkeeping does under the narrower band changes none of that:
+//   - a clipped `end` is written (eh[end] = h1, e = 0) before the next row reads it, and a column the clip has kept out so far holds row -1's insertion
+//     ramp -- a path of j insertions, excursion j > w': below the diagonal like any other;
+//   - rows from qlen + w' on have an empty band (m == 0, the loop ends): they could change neither max (every cell there is below the diagonal's end,
+//     which max has reached) nor gscore (column qlen - 1 is out of the band);
+//   - z-drop: in the rows that matter max - m <= L + o + w' * e <= 2 L, so it fires in neither run when zdrop <= 0 or 2 L <= zdrop;
+//   - band doubling reads max and max_off, which are the same, so it decides as before; the band that goes into DReg::w stays opt.w << trial;
+//   - the row exit's precondition (ext_row_exit_ok) is evaluated on the clamped band, as for any band.
+// Conditions (ext_narrow_band returns -1 otherwise): no negative penalty and both gap extensions positive; amax > 0; 1 <= qlen <= tlen; L > oe - 1 (else
+// the diagonal answers the flank, diag_extend); h0 > L, where a lower bound of h0 does (the right side of a seed whose left side needs the dynamic
+// program starts from at least the seed's own score); zdrop <= 0 or 2 L <= zdrop; w' below the trial's effective band (else there is nothing to clamp);
+// w' <= EXT_NARROW_CAP, so that the 2 w' + 2 live columns of a row fit LaneRing's 32.  The bound holds for any L' >= L that is still below h0, which is how
+// a side the diagonal would answer gets a band when the job's other side sends it to the row loop (first_side_band, dev_ext_lane.h).
+// The bound is tight: tests/golden/ext_narrow_tight.txt holds flanks where w' - 1 changes a result (about 1 in 7 000 random flanks).
 
 // ---------------------------------------------------------------------------------------------- long extensions: the band in registers
 // A contig's extension runs for tens of thousands of rows inside a band of 2 w + 2 columns that slides one column per row.  Here the

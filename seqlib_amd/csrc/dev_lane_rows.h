@@ -53,11 +53,44 @@ LROW_FN int ext_row_bound(int m, int hb, int apos, int qlen, int beg, int tlen, 
 // end_bonus: the caller's pen_clip for the relaxed rule; < 0 = the strict rule only
 LROW_FN bool ext_row_done(int U, int max, int gscore, int end_bonus) { return (end_bonus >= 0 && U <= max - end_bonus) || ext_tail_done(U, max, gscore); }
 
+// A narrow band for flanks that lose little on the diagonal (derivation and conditions: dev_ext_wave.h, "the narrow band").  L = what the flank's
+// main diagonal loses against a perfect match, h0_lower = a lower bound of the score the extension starts from, w_eff = the trial's effective band.
+// The band that gives ksw_extend2's six results as w_eff does, or -1 where the bound does not hold or buys nothing.
+#define EXT_NARROW_CAP 14           // 2 * band + 3 columns fit LaneRing's 32 (with bwa's default penalties: L <= 20)
+template <typename O>
+LROW_FN int ext_narrow_band(const O &o, int amax, int L, int h0_lower, int qlen, int tlen, int w_eff)
+{
+    if (o.o_del < 0 || o.o_ins < 0 || o.e_del <= 0 || o.e_ins <= 0 || amax <= 0) return -1;
+    if (qlen < 1 || qlen > tlen) return -1;
+    const int oe_del = o.o_del + o.e_del, oe_ins = o.o_ins + o.e_ins;
+    if (L <= (oe_del < oe_ins ? oe_del : oe_ins) - 1) return -1;          // the diagonal answers it (diag_extend)
+    if (h0_lower <= L) return -1;
+    if (o.zdrop > 0 && 2ll * L > o.zdrop) return -1;
+    const int wd = L >= o.o_del ? (L - o.o_del) / o.e_del : -1, wi = L >= o.o_ins ? (L - o.o_ins) / o.e_ins : -1;
+    const int w = wd > wi ? wd : wi;
+    return w >= 0 && w < w_eff && w <= EXT_NARROW_CAP ? w : -1;
+}
+// the effective band of a trial: ksw_extend2's max_ins / max_del limits on w.  ksw_extend2 has (int)((double)x / e + 1.), then at least 1: in integers x / e + 1
+// is the same number wherever that is above 1 (x and e of one sign: the quotient's floor is its truncation, and a double holds it exactly enough), and at most
+// 1 wherever the other is -- without the two double divisions, which one lane of k_first_diag's 64 would make the whole wave wait for
+template <typename O>
+LROW_FN int ext_eff_band(const O &o, int qlen, int amax, int end_bonus, int w)
+{
+    const int xi = qlen * amax + end_bonus - o.o_ins, xd = qlen * amax + end_bonus - o.o_del;
+    int max_ins = o.e_ins ? xi / o.e_ins + 1 : (xi > 0 ? 0x7fffffff : 1);          // (e = 0: what the conversion of +-inf and NaN gives on the GPU)
+    max_ins = max_ins > 1 ? max_ins : 1;
+    w = w < max_ins ? w : max_ins;
+    int max_del = o.e_del ? xd / o.e_del + 1 : (xd > 0 ? 0x7fffffff : 1);
+    max_del = max_del > 1 ? max_del : 1;
+    return w < max_del ? w : max_del;
+}
+
 // Where a lane keeps its H/E row.  WIDE: one 32-bit word per column -- 14-bit H, 14-bit E, the column's query code above them.  NARROW: when
 // no score can reach 256 (150 bp reads with bwa's default scores: read length x max(mat) < 256) a column is 8-bit H + 8-bit E in a 16-bit
 // word and the query codes sit apart, eight 4-bit codes per word: half the LDS per wave, twice the waves per CU -- and the kernel's time
 // is inversely proportional to its waves per CU (measured by padding the rows: 4 / 3 / 2 waves per CU -> 30.8 / 40.4 / 60.3 ms).
 struct LaneWide {
+    static constexpr bool ring = false;
     uint32_t *eh;                                   // this lane's word of column 0; stride WAVE words
     static LROW_M size_t bytes(int cols) { return (size_t)cols * WAVE * 4; }
     LROW_M void init(uint32_t *base, int, int lane) { eh = base + lane; }
@@ -70,6 +103,7 @@ struct LaneWide {
     static LROW_M bool zero(uint32_t v) { return (v & 0x0fffffffu) == 0; }
 };
 struct LaneNarrow {
+    static constexpr bool ring = false;
     uint16_t *eh;                                   // 16-bit cells, stride WAVE
     uint32_t *qa;                                   // eight 4-bit query codes per word, stride WAVE words
     static LROW_M size_t bytes(int cols) { return (size_t)cols * WAVE * 2 + (size_t)((cols + 7) / 8) * WAVE * 4; }
@@ -89,8 +123,38 @@ struct LaneNarrow {
     static LROW_M bool zero(uint32_t v) { return v == 0; }
 };
 
+// RING: for jobs whose sides all run in a narrow band (LaneSide::wband <= EXT_NARROW_CAP).  A row of such a side reads and writes the columns
+// i - w .. i + w + 1 only -- at most 2 w + 2 <= 30 consecutive columns -- so the cells are a ring of 32, column j at j & 31; the query codes stay as
+// LaneNarrow keeps them.  The columns a trial has written so far are 0 .. top without a hole (a row writes beg .. end, and `end` grows by at most two
+// over the row before).  A column up to `top` holds its last value: column j + 32 is first written in row j + 31 - w, after the last row that reads
+// column j (row j + w).  A column beyond `top` holds row -1's ramp in the other layouts, and a row whose `end` was not clipped by the band in the row
+// before it does read one; here the row loop writes the ramp into such a column when `end` first reaches it (ring == true), into the slot column
+// j - 32 has left for good by then.
+#define LANE_RING_COLS 32
+struct LaneRing {
+    static constexpr bool ring = true;
+    uint16_t *eh;                                   // 16-bit cells, a ring of LANE_RING_COLS, stride WAVE
+    uint32_t *qa;                                   // eight 4-bit query codes per word, stride WAVE words
+    static LROW_M size_t bytes(int cols) { return (size_t)LANE_RING_COLS * WAVE * 2 + (size_t)((cols + 7) / 8) * WAVE * 4; }
+    LROW_M void init(uint32_t *base, int, int lane) { eh = (uint16_t *)base + lane; qa = base + (size_t)LANE_RING_COLS * WAVE / 2 + lane; }
+    LROW_M void put_all(int j, int h, int e, int q)
+    {
+        if (j < LANE_RING_COLS) eh[j * WAVE] = (uint16_t)(h | e << 8);
+        uint32_t w = (j & 7) ? qa[(j >> 3) * WAVE] : 0u;
+        w |= (uint32_t)q << ((j & 7) * 4);
+        qa[(j >> 3) * WAVE] = w;
+    }
+    LROW_M uint32_t get(int j) const { return eh[(j & (LANE_RING_COLS - 1)) * WAVE]; }
+    LROW_M int q_of(uint32_t, int j) const { return (int)((qa[(j >> 3) * WAVE] >> ((j & 7) * 4)) & 7u); }
+    static LROW_M int h_of(uint32_t v) { return (int)(v & 0xffu); }
+    static LROW_M int e_of(uint32_t v) { return (int)(v >> 8); }
+    LROW_M void put(int j, int h, int e, uint32_t) { eh[(j & (LANE_RING_COLS - 1)) * WAVE] = (uint16_t)(h | e << 8); }
+    static LROW_M bool zero(uint32_t v) { return v == 0; }
+};
+
 // ---------------------------------------------------------------------------------------------- the row loop
-struct LaneSide { int qlen, tlen, q0, end_bonus; int64_t t0; };          // query base j = F.q(q0 + dir * j), text base t = F.t(t0 + dir * t); dir = -1 for side 0 (left), +1 for side 1
+// wband: a band both trials are clamped to (ext_narrow_band), < 0 = none
+struct LaneSide { int qlen, tlen, q0, end_bonus; int64_t t0; int wband = -1; };          // query base j = F.q(q0 + dir * j), text base t = F.t(t0 + dir * t); dir = -1 for side 0 (left), +1 for side 1
 struct LaneRes { int score, qle, tle, gtle, gscore, max_off, aw; };      // ksw_extend2's six results and the band (opt.w << trial) they were found with
 
 // Extends side 0 (where s[0].qlen > 0) from score h0, then side 1 (where s[1].qlen > 0) from the score side 0 ended with, each with the band
@@ -112,6 +176,7 @@ LROW_FN void lane_rows_extend(const LaneSide s[2], int h0, const O &o, const MR 
     const int apos = amax > 0 ? amax : 0;
     int64_t t0 = 0;
     int max = 0, max_i = -1, max_j = -1, max_ie = -1, gscore = -1, max_off = 0, beg = 0, end = 0, i = 0;
+    int top = 0;                 // LaneRing: the last column that holds this trial's value (row -1's or a later row's)
     while (side < 2) {
         if (fresh) {             // a side's trial begins: its row -1
             fresh = false;
@@ -125,18 +190,15 @@ LROW_FN void lane_rows_extend(const LaneSide s[2], int h0, const O &o, const MR 
                 const int h = j == 0 ? h0 : (v > 0 ? v : 0);
                 row.put_all(j, h, 0, j < qlen ? fetch.q(q0 + dir * j) : 0);
             }
-            w = aw;
-            int max_ins = (int)((double)(qlen * amax + end_bonus - o_ins) / e_ins + 1.);
-            max_ins = max_ins > 1 ? max_ins : 1;
-            w = w < max_ins ? w : max_ins;
-            int max_del = (int)((double)(qlen * amax + end_bonus - o_del) / e_del + 1.);
-            max_del = max_del > 1 ? max_del : 1;
-            w = w < max_del ? w : max_del;
+            w = ext_eff_band(o, qlen, amax, end_bonus, aw);
+            const int wband = side ? s[1].wband : s[0].wband;
+            if (wband >= 0) w = w < wband ? w : wband;                  // the narrow band (dev_ext_wave.h): the same six results; aw stays the trial's
             tail_top = ext_tail_bound0(o, qlen, h0, amax);
             exit_ok = row_exit != EXT_ROW_EXIT_OFF && ext_row_exit_ok(o, qlen, w, h0);
             exit_bonus = row_exit == EXT_ROW_EXIT_RELAXED ? end_bonus : -1;
             max = h0;
             max_i = -1; max_j = -1; max_ie = -1; gscore = -1; max_off = 0; beg = 0; end = qlen; i = 0;
+            top = qlen < LANE_RING_COLS - 1 ? qlen : LANE_RING_COLS - 1;
         }
         bool stop = i >= tlen || (i >= qlen && ext_tail_done(tail_top - (i - qlen) * e_del, max, gscore));      // dev_ext_wave.h: rows that cannot matter
         if (!stop) {
@@ -147,6 +209,9 @@ LROW_FN void lane_rows_extend(const LaneSide s[2], int h0, const O &o, const MR 
             if (beg < i - w) beg = i - w;
             if (end > i + w + 1) end = i + w + 1;
             if (end > qlen) end = qlen;
+            if (L::ring) {                                              // columns this trial reaches for the first time: row -1's ramp, as the other layouts hold it
+                for (; top < end; ++top) { const int v = h0 - oe_ins - top * e_ins; row.put(top + 1, v > 0 ? v : 0, 0, 0u); }
+            }
             int h1 = 0;
             if (beg == 0) { h1 = h0 - (o_del + e_del * (i + 1)); if (h1 < 0) h1 = 0; }
             const int hb = h1;                                          // column -1 as the next row reads it

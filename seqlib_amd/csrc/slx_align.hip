@@ -556,6 +556,7 @@ extern "C" int slx_aligner_set(slx_aligner *al, const char *key, int64_t value)
     else if (!strcmp(key, "top_reuse")) al->top_reuse = value != 0;
     else if (!strcmp(key, "walk_stage")) al->walk_stage = value != 0;
     else if (!strcmp(key, "ext_row_exit")) al->ext_row_exit = value != 0;
+    else if (!strcmp(key, "ext_narrow")) { if (value < 0 || value > 3) return SLX_EINVAL; al->ext_narrow = (int)value; }
     else if (!strcmp(key, "p2_items")) al->p2_items = value != 0;
     else if (!strcmp(key, "p2_coop")) al->p2_coop = value != 0;
     else if (!strcmp(key, "p2_items_cap")) al->p2_items_cap = (int)value;
@@ -644,6 +645,13 @@ extern "C" int64_t slx_aligner_counter(const slx_aligner *al, const char *key)
         if (!strcmp(key, "first_lane_jobs")) {          // last batch: top-seed extensions k_first_lanes ran (the DP jobs, one lane each)
             long long v = 0;
             auto take = [&](const slx_aligner *a) { for (const Worker *wk : a->workers) v += (long long)wk->first_stat; };
+            if (al->is_group) for (const slx_aligner *sub : al->subs) take(sub); else take(al);
+            return v;
+        }
+        if (!strcmp(key, "ext_narrow_sides") || !strcmp(key, "ext_narrow_jobs")) {          // last batch: DP sides of the light reads' top seeds given a narrow band / jobs whose sides all have one (ext_narrow)
+            long long v = 0;
+            const int which = key[11] == 'j';
+            auto take = [&](const slx_aligner *a) { for (const Worker *wk : a->workers) v += (long long)wk->narrow_stat[which]; };
             if (al->is_group) for (const slx_aligner *sub : al->subs) take(sub); else take(al);
             return v;
         }
@@ -790,6 +798,7 @@ static int worker_run(slx_aligner *al, Worker *wk, const slx_opt *opt, const uin
     wk->first_stat = 0;
     wk->walk_stat = 0;
     wk->exit_stat = 0;
+    wk->narrow_stat[0] = wk->narrow_stat[1] = 0;
     int rc;
     const int64_t n_part = r_hi - r_lo;
     if ((rc = wk->o_hit_off.ensure(((size_t)n_part + 1) * 8)) != SLX_OK) return rc;

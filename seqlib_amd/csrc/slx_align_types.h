@@ -86,6 +86,7 @@ struct Worker {
     DevBuf chain_left;                                                             // chaining: the light reads k_chain_lds leaves to k_chain (their read numbers)
     DevBuf order_bin, bin_cnt;                                                     // finalize: the multi-region reads binned by region count
     DevBuf defer_list, hits_big;                                                   // finalize: reads k_regs defers to the wave kernel, reads k_hits leaves to k_hits_wave
+    DevBuf first_nar, first_nar_sorted;                                            // ... and those whose sides all run in a narrow band (k_first_lanes<LaneRing>), binned apart
     DevBuf first_sorted, first_bins;                                               // k_first_lanes: the DP jobs of the light reads' top seeds binned by work
     DevBuf p2mask, p2list, p2items, p2long, lane_jobs, first_dp, cig_lane_list;               // seeding pass 2: calls to make per read, reads with any (k_seed2_select)
     DevBuf job_key_in, job_key_out, job_val_in, job_val_out, job_sort_tmp;         // contigs: extension jobs ordered longest first
@@ -100,6 +101,7 @@ struct Worker {
     unsigned long long first_stat = 0;                                             // k_first_lanes: DP jobs it counted as run, of the last batch
     bool first_lanes_ran = false;                                                  // ... the chunk in flight took that path
     unsigned long long walk_stat = 0;                                              // k_extend_reg: chains it served from a lane-made header, of the last batch
+    unsigned long long narrow_stat[2] = {0, 0};                                    // k_first_diag: DP sides given a narrow band, jobs whose sides all have one, of the last batch
     unsigned long long exit_stat = 0;                                              // extension kernels: DPs (lane kernels: band trials) the row exit ended, of the last batch
     unsigned int pseg_stat = 0;                                                    // ... how many
     unsigned int gseg_stat[3] = {0, 0, 0};                                         // ... segments taken as speculated / run again / jobs cut
@@ -128,7 +130,7 @@ struct Worker {
                &c_pos, &c_head, &c_tail, &c_n, &c_rid, &c_w, &c_first, &c_kept, &ia, &ib, &ic, &srt, &regs, &hits, &n_chain, &n_reg, &n_hit,
                &na, &frac_rep, &zarena, &cigpool, &counters, &lists, &hit_cnt, &cig_cnt, &hit_off_c, &cig_off_c, &order_key_in,
                &order_key_out, &order_in, &order_out, &queues, &sort_tmp, &jobs, &fast_list, &dp_list, &part_flag, &part_pos, &cand, &cand_base,
-               &cand_cnt, &cand_off, &dbg_cyc, &order_tmp, &first_tab, &first_cnt, &first_off, &fb_list, &first_jobs, &len_stat, &s_score, &long_list, &long_scratch, &huge_rows, &p2mask, &p2list, &p2items, &p2long, &lane_jobs, &first_dp, &first_sorted, &first_bins, &cig_lane_list, &defer_list, &hits_big, &order_bin, &bin_cnt, &chain_left, &guard_cnt, &snap_ia, &snap_regs, &snap_nreg,
+               &cand_cnt, &cand_off, &dbg_cyc, &order_tmp, &first_tab, &first_cnt, &first_off, &fb_list, &first_jobs, &len_stat, &s_score, &long_list, &long_scratch, &huge_rows, &p2mask, &p2list, &p2items, &p2long, &lane_jobs, &first_dp, &first_sorted, &first_bins, &first_nar, &first_nar_sorted, &cig_lane_list, &defer_list, &hits_big, &order_bin, &bin_cnt, &chain_left, &guard_cnt, &snap_ia, &snap_regs, &snap_nreg,
                &memo_idx, &memo_jobs, &memo_tab, &round_list, &todo_a, &todo_b, &spec_cnt, &seed3_buf, &job_key_in, &job_key_out, &job_val_in, &job_val_out, &job_sort_tmp, &pseg_jobs, &pseg_idx, &pseg_cnt, &gseg_jobs, &gseg_units, &gseg_wrec, &gseg_wout, &gseg_scratch, &gseg_cnt, &xseg_jobs, &xseg_state, &xseg_units, &xseg_out, &xseg_wrec, &xseg_wout, &xseg_scratch, &xseg_cnt,
                &o_hit_off, &o_rid, &o_pos, &o_flag, &o_mapq, &o_score, &o_nm, &o_na, &o_ncig, &o_cig_off, &o_cigar, &o_xa, &o_sub};
         for (auto &e : ev) e = nullptr;
@@ -235,6 +237,8 @@ struct slx_aligner {
     int walk_stage = 1;           // 1 = k_extend_reg (short reads) opens its chains from headers made 64 at a time, one per lane (dev_chain_hdr.h); 0 = chain by chain on the whole wave
     int ext_row_exit = 1;         // 1 = the short-read extension loops (reg_ksw_extend2, lane_rows_extend) end after a row that rules out any change of what their caller
                                   // reads (dev_ext_wave.h, "the row exit"); 0 = they run to z-drop, an all-zero row or the tail bound
+    int ext_narrow = 1;           // 1 = a top-seed extension of a light read whose flank loses little on its main diagonal runs in the narrow band that bound allows (ext_narrow_band,
+                                  // dev_lane_rows.h), and the jobs whose sides all have one run on LaneRing rows in a launch of their own; 2 = the band only, one launch; 3 = as 1 with the narrow jobs binned by the wide launch's key (for measuring); 0 = neither
     int seed_free_cus = 0;        // see "seed_free_cus" in slx_aligner_set
     int stream_prio = 0;
     int n_workers = 3;            // concurrent parts of a large batch

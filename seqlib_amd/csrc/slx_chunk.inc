@@ -983,9 +983,16 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
                 const bool fl_narrow = al->lane_narrow && fl_amax * max_len < 256;
                 const bool first_lanes = al->first_lanes && al->first_diag && max_len <= 704 && (fl_narrow ? LaneNarrow::bytes(fl_cols) : LaneWide::bytes(fl_cols)) <= 64 * 1024 &&
                                          (int64_t)fl_amax * max_len < LANE_SCORE_LIMIT;
+                // "ext_narrow": the bands go with the jobs (FirstJob::pad) wherever lanes run them; the jobs whose sides all have one get LaneRing rows and a launch
+                // of their own where the 8-bit cells do (ring_cu: waves per CU that launch is sized for -- its 8.4 KB of LDS a wave would allow 19)
+                const int narrow = first_lanes ? al->ext_narrow : 0;
+                const bool ring = (narrow == 1 || narrow == 3) && fl_narrow;
+                const int by_band = narrow == 1;          // (3: the narrow jobs binned by the wide launch's key, to measure the binning by itself)
+                const int ring_cu = 16;
                 if (first_lanes) {
                     ENS(first_sorted, (size_t)top_cap * 4); ENS(first_bins, 1024);
-                    HIPCHK(hipMemsetAsync(wk->first_bins.p, 0, 512, st));
+                    HIPCHK(hipMemsetAsync(wk->first_bins.p, 0, 1024, st));          // [0, 128): the DP jobs' classes and cursors, [128, 256): the narrow jobs'
+                    if (ring) { ENS(first_nar, (size_t)top_cap * 4); ENS(first_nar_sorted, (size_t)top_cap * 4); }
                     wk->first_lanes_ran = true;
                 }
                 hipLaunchKernelGGL(k_first_prep, dim3(std::max(1, std::min(n / 128 + 1, al->n_cu * 12))), dim3(128), 0, st, al->ref, ck, dopt, n, wk->first_off.as<unsigned int>(),
@@ -994,18 +1001,28 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
                     constexpr int MAXQ = decltype(mq)::value;
                     if (al->first_diag) {   // what the diagonal answers, one lane per job; k_ext_first keeps the jobs that need the dynamic program
                         hipLaunchKernelGGL(k_first_diag, dim3((top_cap + 255) / 256), dim3(256), 0, st, al->ref, ck, dopt, n, wk->first_off.as<unsigned int>(), top_cap,
-                                           wk->first_jobs.as<FirstJob>(), wk->first_tab.as<DReg>(), wk->first_dp.as<unsigned int>(), q + 40);
+                                           wk->first_jobs.as<FirstJob>(), wk->first_tab.as<DReg>(), wk->first_dp.as<unsigned int>(), q + 40, narrow,
+                                           ring ? wk->first_nar.as<unsigned int>() : (unsigned int *)nullptr, q + 58);          // [58] narrow jobs (the narrow list's length), [59] narrow sides, [60] the narrow launch's queue
                     }
                     if (first_lanes) {
                         unsigned int *bins = wk->first_bins.as<unsigned int>(), *sorted = wk->first_sorted.as<unsigned int>();
                         const FirstJob *fj = wk->first_jobs.as<FirstJob>();
-                        hipLaunchKernelGGL(k_first_bin_count, dim3(al->n_cu * 4), dim3(256), 0, st, fj, (const unsigned int *)wk->first_dp.as<unsigned int>(), (const unsigned int *)(q + 40), max_len, bins);
+                        hipLaunchKernelGGL(k_first_bin_count, dim3(al->n_cu * 4), dim3(256), 0, st, fj, (const unsigned int *)wk->first_dp.as<unsigned int>(), (const unsigned int *)(q + 40), max_len, bins, 0);
                         hipLaunchKernelGGL(k_first_bin_scan, dim3(1), dim3(1), 0, st, bins);
-                        hipLaunchKernelGGL(k_first_bin_scatter, dim3(al->n_cu * 4), dim3(256), 0, st, fj, (const unsigned int *)wk->first_dp.as<unsigned int>(), (const unsigned int *)(q + 40), max_len, bins, sorted);
+                        hipLaunchKernelGGL(k_first_bin_scatter, dim3(al->n_cu * 4), dim3(256), 0, st, fj, (const unsigned int *)wk->first_dp.as<unsigned int>(), (const unsigned int *)(q + 40), max_len, bins, sorted, 0);
                         if (fl_narrow) hipLaunchKernelGGL(k_first_lanes<LaneNarrow>, dim3(al->n_cu * 8), dim3(64), LaneNarrow::bytes(fl_cols), st, al->ref, ck, dopt, q + 22, fj, wk->first_tab.as<DReg>(),
                                                           (const unsigned int *)sorted, (const unsigned int *)(q + 40), fl_cols, q + 54);
                         else hipLaunchKernelGGL(k_first_lanes<LaneWide>, dim3(al->n_cu * 4), dim3(64), LaneWide::bytes(fl_cols), st, al->ref, ck, dopt, q + 22, fj, wk->first_tab.as<DReg>(),
                                                 (const unsigned int *)sorted, (const unsigned int *)(q + 40), fl_cols, q + 54);
+                        if (ring) {          // the narrow jobs: binned by bases x band width, 32 columns of cells per lane
+                            const unsigned int *nar = wk->first_nar.as<unsigned int>();
+                            unsigned int *nbins = bins + 128, *nsorted = wk->first_nar_sorted.as<unsigned int>();
+                            hipLaunchKernelGGL(k_first_bin_count, dim3(al->n_cu * 4), dim3(256), 0, st, fj, nar, (const unsigned int *)(q + 58), max_len, nbins, by_band);
+                            hipLaunchKernelGGL(k_first_bin_scan, dim3(1), dim3(1), 0, st, nbins);
+                            hipLaunchKernelGGL(k_first_bin_scatter, dim3(al->n_cu * 4), dim3(256), 0, st, fj, nar, (const unsigned int *)(q + 58), max_len, nbins, nsorted, by_band);
+                            hipLaunchKernelGGL(k_first_lanes<LaneRing>, dim3(al->n_cu * ring_cu), dim3(64), LaneRing::bytes(fl_cols), st, al->ref, ck, dopt, q + 60, fj, wk->first_tab.as<DReg>(),
+                                               (const unsigned int *)nsorted, (const unsigned int *)(q + 58), fl_cols, q + 54);
+                        }
                     } else
                     hipLaunchKernelGGL(k_ext_first<MAXQ>, dim3(gf), dim3(64), 0, st, al->ref, ck, dopt, n, wk->first_off.as<unsigned int>(), top_cap, q + 22,
                                        wk->first_jobs.as<FirstJob>(), wk->first_tab.as<DReg>(), al->first_diag ? wk->first_dp.as<unsigned int>() : (const unsigned int *)nullptr, q + 40);
@@ -1062,7 +1079,7 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
         m_defer = part(wk->queues.as<unsigned int>() + 46, 1);          // reads k_regs deferred to the wave kernel
         m_big = part(wk->queues.as<unsigned int>() + 48, 1);            // reads k_hits left to k_hits_wave
         m_chain = part(wk->queues.as<unsigned int>() + 50, 2);          // reads k_chain_lds started over on the HBM columns, reads it finished in LDS
-        m_walk = part(wk->queues.as<unsigned int>() + 55, 2);           // chains k_extend_reg opened from a lane-made header, DPs the row exit ended
+        m_walk = part(wk->queues.as<unsigned int>() + 55, 5);           // chains k_extend_reg opened from a lane-made header, DPs the row exit ended, -, narrow jobs, narrow sides
         if (wk->first_lanes_ran) m_first = part(wk->queues.as<unsigned int>() + 54, 1);          // jobs k_first_lanes counted as run
         if (m_hits < 0 || m_cig < 0 || m_flags < 0 || m_defer < 0 || m_big < 0 || m_chain < 0 || m_walk < 0 || (wk->first_lanes_ran && m_first < 0)) {
             slx_set_error("run_chunk: more counters than k_mail has parts (SLX_MAIL_PARTS)");
@@ -1078,6 +1095,7 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
     wk->chain_stat[0] += wk->h_mail[m_chain]; wk->chain_stat[1] += wk->h_mail[m_chain + 1];
     wk->walk_stat += wk->h_mail[m_walk];
     wk->exit_stat += wk->h_mail[m_walk + 1];
+    wk->narrow_stat[0] += wk->h_mail[m_walk + 4]; wk->narrow_stat[1] += wk->h_mail[m_walk + 3];
     if (m_first >= 0) wk->first_stat += wk->h_mail[m_first];
     // grow the outputs and compact
     const size_t H = (size_t)*hit_base + Hc, C = (size_t)*cig_base + Cc;
