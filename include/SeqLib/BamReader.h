@@ -12,7 +12,11 @@
 // New next to the reference: GetNextRecord (the README's spelling, README.md:150-181), NextBatch (many records at once through the slab path of
 // BamRecord.h), SetBatchBytes, HasIndex, and SetReadFilter / ClearReadFilter: a Filter::ReadFilterCollection evaluated on the GPU, so that Next, NextBatch and
 // BWAAligner::alignSequences(BamReader&) see the kept records only -- for the whole file and for regions.
-// Refused loudly: SetRegion / SetRegions with anything but a GenomicRegion / a GRC, CRAM and SAM-text input, "-" (stdin), a second Open.
+// Open takes SAM text too (plain, gzip'd or bgzip'd; the reference's "BAM/SAM/CRAM", SeqLib/BamReader.h:22-26): slx_sam_sniff tells the two apart, and the lines are
+// parsed into BAM records on the GPU behind include/seqlib_amd_sam.h (which lists the grammar and its deviations from htslib).  Everything after Open is the same
+// code on both: Next, GetNextRecord, NextBatch, Reset, Header, SetReadFilter, BWAAligner::alignSequences(BamReader&) and alignToBam(BamReader&).  SAM text has no
+// index: HasIndex() is false, SetRegion / SetRegions return false with a message.
+// Refused loudly: SetRegion / SetRegions with anything but a GenomicRegion / a GRC, CRAM input, "-" (stdin), a second Open.
 #pragma once
 #include <cstdint>
 #include <cstring>
@@ -27,6 +31,7 @@
 #include "SeqLib/ReadFilter.h"
 #include "seqlib_amd_bam.h"
 #include "seqlib_amd_filter.h"
+#include "seqlib_amd_sam.h"
 
 namespace SeqLib {
 
@@ -44,7 +49,8 @@ public:
         if (path == "-") { std::cerr << "BamReader::Open - reading from stdin is not available in the MI355X drop-in" << std::endl; return false; }
         path_ = path;
         slx_bam *rd = nullptr;
-        if (slx_bam_open(path.c_str(), -1, &rd) != SLX_OK) {
+        const bool sam = slx_sam_sniff(path.c_str()) == 1;          // (anything else, an unreadable file included, is slx_bam_open's to name)
+        if ((sam ? slx_sam_open(path.c_str(), -1, &rd) : slx_bam_open(path.c_str(), -1, &rd)) != SLX_OK) {
             std::cerr << "BamReader::Open - failed to open '" << path << "': " << slx_last_error() << std::endl;
             return false;
         }
@@ -80,18 +86,19 @@ public:
     // false when the reader is not open, has no index or the region names a reference outside the header
     bool SetRegion(const GenomicRegion &gr)
     {
-        if (!rd_ || !HasIndex()) return false;
+        if (!rd_ || no_index_in_sam("SetRegion") || !HasIndex()) return false;
         const slx_bam_region r = {gr.chr, gr.pos1, gr.pos2};
         return arm(&r, 1);
     }
     bool SetRegions(const GRC &grc)
     {
-        if (!rd_ || !HasIndex() || !grc.size()) return false;
+        if (!rd_ || no_index_in_sam("SetRegions") || !HasIndex() || !grc.size()) return false;
         std::vector<slx_bam_region> r;
         for (const GenomicRegion &g : grc) r.push_back(slx_bam_region{g.chr, g.pos1, g.pos2});
         return arm(r.data(), (int64_t)r.size());
     }
     bool HasIndex() const { return rd_ && slx_bam_has_index(rd_) != 0; }
+    bool IsSAM() const { return rd_ && slx_bam_counter(rd_, "sam") == 1; }          // new next to the reference: the open file is SAM text
     template <class Region> bool SetRegion(const Region &)
     {
         std::cerr << "BamReader::SetRegion - region iteration needs a BAI index and GenomicRegion; not available in the MI355X drop-in for this argument type (pass a SeqLib::GenomicRegion)" << std::endl;
@@ -206,6 +213,12 @@ private:
         r->mempolicy = BAM_USER_OWNS_DATA;
         fill(r, p, l_data);
         return std::allocate_shared<BamRecord>(detail::SlabAlloc<BamRecord>(slab), std::shared_ptr<bam1_t>(box, r));
+    }
+    bool no_index_in_sam(const char *who) const
+    {
+        if (!IsSAM()) return false;
+        std::cerr << "BamReader::" << who << " - '" << path_ << "' is SAM text, which has no index: region iteration is not available on it" << std::endl;
+        return true;
     }
     void clear_batch() { std::memset(&batch_, 0, sizeof batch_); cur_ = 0; eof_ = false; }
     bool arm(const slx_bam_region *r, int64_t n)

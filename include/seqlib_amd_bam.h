@@ -37,7 +37,8 @@
  * Not done: htslib's post-pass that merges chunks lying in one BGZF block and lifts sparse bins into their parents (the index is valid without it,
  * byte parity with `samtools index` is not claimed), and CSI.
  *
- * No CPU fallback: without a GPU slx_bam_open, slx_bam_inflate_file, slx_bam_index_build and slx_bgzf_open return SLX_ENODEVICE.  Not carried: CRAM, SAM text, CSI.
+ * No CPU fallback: without a GPU slx_bam_open, slx_bam_inflate_file, slx_bam_index_build and slx_bgzf_open return SLX_ENODEVICE.  Not carried: CRAM, CSI.
+ * SAM text is read by slx_sam_open (seqlib_amd_sam.h), whose handle is an slx_bam; slx_bam_open itself takes BAM only.
  */
 #ifndef SEQLIB_AMD_BAM_H
 #define SEQLIB_AMD_BAM_H
@@ -94,7 +95,7 @@ int  slx_bam_rewind(slx_bam *rd);
 int  slx_bam_set(slx_bam *rd, const char *key, int64_t value);
 /* "members", "members_done", "repaired_chunks", "index_rounds", "missing_eof", "records", and kernel times of the last batch from HIP events in
  * microseconds: "us_inflate", "us_crc", "us_index", "us_unpack"; of the region iteration "regions_done", "region_candidates" (records walked),
- * "region_kept" and "us_region"; -1 = unknown name */
+ * "region_kept" and "us_region"; "sam" 0|1: the reader is over SAM text (seqlib_amd_sam.h lists that reader's further names); -1 = unknown name */
 int64_t slx_bam_counter(const slx_bam *rd, const char *name);
 
 /* The index of the reader's file: bai_path, or when NULL <path>.bai, then <path> with ".bam" replaced by ".bai".  slx_bam_open tries the same two names

@@ -27,6 +27,7 @@
 #include "dev_bamidx.h"
 #include "dev_bai.h"
 #include "bai_host.h"
+#include "sam_reader.h"
 
 #define BAM_HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { slx_set_error("HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, __LINE__); return SLX_ENODEVICE; } } while (0)
 #define BAM_CHK(x) do { const int rc_ = (x); if (rc_ != SLX_OK) return rc_; } while (0)
@@ -487,6 +488,7 @@ struct slx_bam {
     bool region_mode = false;
     slx_filter *flt = nullptr;                             // a read filter attached by slx_filter_attach; nullptr: nothing new is launched
     BamDBuf d_fkeep;                                       // its keep bytes
+    slx_samsrc *sam = nullptr;                             // a reader over SAM text (slx_sam_open): the batches come from slx_sam.hip, there are no members
     std::vector<BamDBuf *> dbufs() { return {&d_fkeep, &d_comp, &d_desc, &d_err, &d_out, &d_guess, &d_used, &d_exit_a, &d_exit_b, &d_count, &d_base, &d_state, &d_rec, &d_keep, &d_blen, &d_kidx, &d_boff, &d_tmp, &d_bases, &d_offs, &d_map, &d_cs, &d_cr}; }
     std::vector<BamHBuf *> hbufs() { return {&h_comp, &h_desc, &h_err, &h_out, &h_rec, &h_state, &h_map}; }
 };
@@ -720,6 +722,7 @@ extern "C" int slx_bam_open(const char *path, int device, slx_bam **out) { retur
 extern "C" int slx_bam_index_load(slx_bam *rd, const char *bai_path)
 {
     if (!rd) { slx_set_error("slx_bam_index_load: reader is null"); return SLX_EINVAL; }
+    if (rd->sam) { slx_set_error("slx_bam_index_load: '%s': SAM text has no index", rd->f.path.c_str()); return SLX_EINVAL; }
     std::string bp = bai_path ? std::string(bai_path) : bai_beside(rd->f.path);
     if (bp.empty()) { slx_set_error("BAI: no index beside '%s' (<path>.bai, or .bai in place of .bam)", rd->f.path.c_str()); return SLX_EIO; }
     return bam_load_index(rd, bp);
@@ -735,6 +738,7 @@ static void bam_whole_file(slx_bam *rd)
 extern "C" int slx_bam_set_regions(slx_bam *rd, const slx_bam_region *regs, int64_t n)
 {
     if (!rd || n < 0 || (n && !regs)) { slx_set_error("slx_bam_set_regions: null argument"); return SLX_EINVAL; }
+    if (rd->sam) { slx_set_error("slx_bam_set_regions: '%s': SAM text has no index", rd->f.path.c_str()); return SLX_EINVAL; }
     if (n == 0) { bam_whole_file(rd); return SLX_OK; }
     if (!rd->has_bai) { slx_set_error("slx_bam_set_regions: '%s' has no index loaded (slx_bam_index_build writes one, slx_bam_index_load reads it)", rd->f.path.c_str()); return SLX_EINVAL; }
     const int64_t nm = (int64_t)rd->f.mem.size();
@@ -773,6 +777,7 @@ extern "C" int slx_bam_set_regions(slx_bam *rd, const slx_bam_region *regs, int6
 extern "C" void slx_bam_close(slx_bam *rd)
 {
     if (!rd) return;
+    if (rd->sam) slx_samsrc_close(rd->sam);
     bam_dev_free(rd);
     delete rd;
 }
@@ -791,6 +796,7 @@ extern "C" int64_t slx_bam_ref_len(const slx_bam *rd, int i) { return rd && i >=
 extern "C" int slx_bam_rewind(slx_bam *rd)
 {
     if (!rd) { slx_set_error("slx_bam_rewind: reader is null"); return SLX_EINVAL; }
+    if (rd->sam) BAM_CHK(slx_samsrc_rewind(rd->sam));
     bam_whole_file(rd);                  // the regions go too: the reference's Reset reopens the file (src/BamReader.cpp:56-62)
     return SLX_OK;
 }
@@ -799,6 +805,8 @@ extern "C" int slx_bam_set(slx_bam *rd, const char *key, int64_t value)
 {
     if (!rd || !key) { slx_set_error("slx_bam_set: null argument"); return SLX_EINVAL; }
     const std::string k(key);
+    int sam_rc = SLX_OK;
+    if (rd->sam && slx_samsrc_set(rd->sam, key, value, &sam_rc)) return sam_rc;
     if (k == "chunk_bytes" && value >= 64 && value <= (1ll << 30)) { rd->chunk_bytes = (uint64_t)value; return SLX_OK; }
     if (k == "idx_fail" && (value == 0 || value == 1)) { rd->idx_fail = (int)value; return SLX_OK; }
     slx_set_error("slx_bam_set: unknown key or value out of range: %s = %lld", key, (long long)value);
@@ -809,6 +817,9 @@ extern "C" int64_t slx_bam_counter(const slx_bam *rd, const char *name)
 {
     if (!rd || !name) return -1;
     const std::string k(name);
+    int64_t sam_v = 0;
+    if (rd->sam && slx_samsrc_counter(rd->sam, name, &sam_v)) return sam_v;
+    if (k == "sam") return 0;
     if (k == "members") return (int64_t)rd->f.mem.size();
     if (k == "members_done") return rd->c_members_done;
     if (k == "repaired_chunks") return rd->c_repaired;
@@ -948,15 +959,45 @@ static int bam_next_regions(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
     return SLX_OK;
 }
 
+// the attached filter's verdicts on the n_rec records of s[0, end) (offsets rec, all in HBM), and the kept ones compacted into d_cs / d_cr, bytes unchanged: *kn of
+// them in *kb bytes (the gather is still in flight on return).
+static int bam_filter_compact(slx_bam *rd, const uint8_t *s, const uint64_t *rec, uint64_t n_rec, uint64_t end, uint64_t *kn_out, uint64_t *kb_out)
+{
+    typedef unsigned long long ull;
+    hipStream_t st = rd->st;
+    BAM_CHK(rd->h_state.ensure(64));
+    ull *hs = rd->h_state.as<ull>();
+    uint64_t kn = 0, kb = 0;
+    *kn_out = *kb_out = 0;
+    for (BamDBuf *b : {&rd->d_keep, &rd->d_blen, &rd->d_kidx, &rd->d_boff}) BAM_CHK(b->ensure(8 * (n_rec + 1)));
+    BAM_CHK(rd->d_fkeep.ensure(n_rec + 8));
+    BAM_CHK(slx_filter_eval_device(rd->flt, rd->device, st, s, rec, n_rec, end, rd->d_fkeep.as<uint8_t>(), nullptr));
+    k_bam_keep_bytes<<<(unsigned)((n_rec + 1 + 255) / 256), 256, 0, st>>>(rd->d_fkeep.as<uint8_t>(), rec, n_rec, 0, rd->d_keep.as<ull>(), rd->d_blen.as<ull>());
+    BAM_HIPCHK(hipGetLastError());
+    size_t tb = 0;
+    BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, rd->d_keep.as<ull>(), rd->d_kidx.as<ull>(), (int)(n_rec + 1), st));
+    BAM_CHK(rd->d_tmp.ensure(tb + 8));
+    BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(rd->d_tmp.p, tb, rd->d_keep.as<ull>(), rd->d_kidx.as<ull>(), (int)(n_rec + 1), st));
+    BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(rd->d_tmp.p, tb, rd->d_blen.as<ull>(), rd->d_boff.as<ull>(), (int)(n_rec + 1), st));
+    BAM_HIPCHK(hipMemcpyAsync(hs + 5, rd->d_kidx.as<ull>() + n_rec, 8, hipMemcpyDeviceToHost, st));
+    BAM_HIPCHK(hipMemcpyAsync(hs + 6, rd->d_boff.as<ull>() + n_rec, 8, hipMemcpyDeviceToHost, st));
+    BAM_HIPCHK(slx_wait_stream(st));
+    kn = hs[5]; kb = hs[6];
+    if (kn) {
+        BAM_CHK(rd->d_cs.ensure(kb + 8)); BAM_CHK(rd->d_cr.ensure(8 * (kn + 1)));
+        k_bam_gather<<<(unsigned)((n_rec + 3) / 4), 256, 0, st>>>(s, rec, n_rec, rd->d_kidx.as<ull>(), rd->d_boff.as<ull>(), rd->d_cs.as<uint8_t>(), rd->d_cr.as<uint64_t>(), 0, 0);
+        BAM_HIPCHK(hipGetLastError());
+    }
+    *kn_out = kn; *kb_out = kb;
+    return SLX_OK;
+}
+
 // the whole file with a read filter attached: spans as without one, the filter's keep bytes, the two exclusive sums and k_bam_gather into d_cs / d_cr as for a
 // region; a span whose records are all dropped goes on to the next, since n_records == 0 is the end of the file
 static int bam_next_filtered(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
 {
-    typedef unsigned long long ull;
     hipStream_t st = rd->st;
     const int64_t nm = (int64_t)rd->f.mem.size();
-    BAM_CHK(rd->h_state.ensure(64));
-    ull *hs = rd->h_state.as<ull>();
     uint64_t kn = 0, kb = 0, repaired = 0;
     int64_t members = 0;
     while (!kn) {
@@ -970,26 +1011,8 @@ static int bam_next_filtered(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
         BAM_CHK(bam_take_carry(rd, end, total));
         BAM_HIPCHK(slx_wait_stream(st));
         if (!n_rec) break;
-        const uint8_t *s = rd->d_out.as<uint8_t>();
-        const uint64_t *rec = rd->d_rec.as<uint64_t>();
-        for (BamDBuf *b : {&rd->d_keep, &rd->d_blen, &rd->d_kidx, &rd->d_boff}) BAM_CHK(b->ensure(8 * (n_rec + 1)));
-        BAM_CHK(rd->d_fkeep.ensure(n_rec + 8));
-        BAM_CHK(slx_filter_eval_device(rd->flt, rd->device, st, s, rec, n_rec, end, rd->d_fkeep.as<uint8_t>(), nullptr));
-        k_bam_keep_bytes<<<(unsigned)((n_rec + 1 + 255) / 256), 256, 0, st>>>(rd->d_fkeep.as<uint8_t>(), rec, n_rec, 0, rd->d_keep.as<ull>(), rd->d_blen.as<ull>());
-        BAM_HIPCHK(hipGetLastError());
-        size_t tb = 0;
-        BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, rd->d_keep.as<ull>(), rd->d_kidx.as<ull>(), (int)(n_rec + 1), st));
-        BAM_CHK(rd->d_tmp.ensure(tb + 8));
-        BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(rd->d_tmp.p, tb, rd->d_keep.as<ull>(), rd->d_kidx.as<ull>(), (int)(n_rec + 1), st));
-        BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(rd->d_tmp.p, tb, rd->d_blen.as<ull>(), rd->d_boff.as<ull>(), (int)(n_rec + 1), st));
-        BAM_HIPCHK(hipMemcpyAsync(hs + 5, rd->d_kidx.as<ull>() + n_rec, 8, hipMemcpyDeviceToHost, st));
-        BAM_HIPCHK(hipMemcpyAsync(hs + 6, rd->d_boff.as<ull>() + n_rec, 8, hipMemcpyDeviceToHost, st));
-        BAM_HIPCHK(slx_wait_stream(st));
-        kn = hs[5]; kb = hs[6];
+        BAM_CHK(bam_filter_compact(rd, rd->d_out.as<uint8_t>(), rd->d_rec.as<uint64_t>(), n_rec, end, &kn, &kb));
         if (!kn) continue;
-        BAM_CHK(rd->d_cs.ensure(kb + 8)); BAM_CHK(rd->d_cr.ensure(8 * (kn + 1)));
-        k_bam_gather<<<(unsigned)((n_rec + 3) / 4), 256, 0, st>>>(s, rec, n_rec, rd->d_kidx.as<ull>(), rd->d_boff.as<ull>(), rd->d_cs.as<uint8_t>(), rd->d_cr.as<uint64_t>(), 0, 0);
-        BAM_HIPCHK(hipGetLastError());
         BAM_CHK(rd->h_out.ensure(kb + 8)); BAM_CHK(rd->h_rec.ensure(8 * (kn + 1)));
         BAM_HIPCHK(hipMemcpyAsync(rd->h_out.p, rd->d_cs.p, kb, hipMemcpyDeviceToHost, st));
         BAM_HIPCHK(hipMemcpyAsync(rd->h_rec.p, rd->d_cr.p, 8 * (kn + 1), hipMemcpyDeviceToHost, st));
@@ -1004,6 +1027,52 @@ static int bam_next_filtered(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
     return SLX_OK;
 }
 
+// a reader over SAM text: the batch comes from slx_sam.hip as records in HBM; with a read filter attached it is compacted as above
+static int bam_next_sam(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
+{
+    hipStream_t st = rd->st;
+    uint64_t kn = 0, kb = 0;
+    int64_t members = 0;
+    const void *ds = nullptr, *dr = nullptr;
+    for (;;) {
+        uint64_t n_rec = 0, end = 0;
+        int64_t nm = 0;
+        BAM_CHK(slx_samsrc_next(rd->sam, max_bytes, &ds, &dr, &n_rec, &end, &nm));
+        members += nm;
+        if (!n_rec) return SLX_OK;
+        if (!rd->flt) { kn = n_rec; kb = end; break; }
+        BAM_CHK(bam_filter_compact(rd, (const uint8_t *)ds, (const uint64_t *)dr, n_rec, end, &kn, &kb));
+        if (kn) { ds = rd->d_cs.p; dr = rd->d_cr.p; break; }
+    }
+    BAM_CHK(rd->h_out.ensure(kb + 8)); BAM_CHK(rd->h_rec.ensure(8 * (kn + 1)));
+    BAM_HIPCHK(hipMemcpyAsync(rd->h_out.p, ds, kb, hipMemcpyDeviceToHost, st));
+    BAM_HIPCHK(hipMemcpyAsync(rd->h_rec.p, dr, 8 * (kn + 1), hipMemcpyDeviceToHost, st));
+    BAM_HIPCHK(slx_wait_stream(st));
+    rd->c_records += (int64_t)kn;
+    out->n_records = (int64_t)kn; out->n_bytes = (int64_t)kb;
+    out->stream = rd->h_out.as<uint8_t>(); out->rec_off = rd->h_rec.as<uint64_t>();
+    out->d_stream = ds; out->d_rec_off = dr;
+    out->n_members = members; out->n_repaired_chunks = 0;
+    rd->cur_stream = ds; rd->cur_rec = dr; rd->map_stream = nullptr;
+    return SLX_OK;
+}
+
+extern "C" int slx_sam_open(const char *path, int device, slx_bam **out)
+{
+    if (!path || !out) { slx_set_error("slx_sam_open: null argument"); return SLX_EINVAL; }
+    *out = nullptr;
+    slx_samsrc *src = nullptr;
+    BAM_CHK(slx_samsrc_open(path, device, &src));
+    slx_bam *rd = new slx_bam();
+    rd->f.path = path; rd->f.has_eof = 1;
+    const int rc = bam_dev_init(rd, slx_samsrc_device(src));
+    if (rc != SLX_OK) { slx_samsrc_close(src); bam_dev_free(rd); delete rd; return rc; }
+    rd->sam = src;
+    slx_samsrc_header(src, &rd->text, &rd->ref_names, &rd->ref_lens);
+    *out = rd;
+    return SLX_OK;
+}
+
 void slx_reader_set_filter(slx_bam *rd, slx_filter *f) { rd->flt = f; }
 
 extern "C" int slx_bam_next(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
@@ -1012,6 +1081,7 @@ extern "C" int slx_bam_next(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
     memset(out, 0, sizeof *out);
     BAM_HIPCHK(hipSetDevice(rd->device));
     rd->us[0] = rd->us[1] = rd->us[2] = rd->us[4] = 0;
+    if (rd->sam) return bam_next_sam(rd, max_bytes, out);
     if (rd->region_mode) return bam_next_regions(rd, max_bytes, out);
     if (rd->flt) return bam_next_filtered(rd, max_bytes, out);
     const int64_t nm = (int64_t)rd->f.mem.size();

@@ -5,6 +5,8 @@
 //   k_fq_count / k_fq_lines   line feeds per tile, then (after hipCUB's scan of the counts) the line starts, by a wave prefix per 1 KiB step
 //   k_fq_check                one lane per record taken as four lines: the acceptance test, the fields' places and lengths     dev_fastq.h
 //   k_fq_gather               one launch per stream (bases, qualities, names, comments): one wave per tile of the OUTPUT, through LDS, aligned 16-byte stores
+// The source side (producer thread, BGZF inflate, the text window, the line starts) is fq_text.h's FqText, which the SAM reader (slx_sam.hip) is built on too; its
+// functions are defined here.
 // From the first record that fails the test the rest of the batch's text comes down and goes through fq_host.h; its reads go up and are gathered like the others.
 // Waves take tiles / members / records by a static map: there is no work queue here (DESIGN.md section 4 does not arise), and the only atomic is one
 // atomicMin per wave that holds a failing record.
@@ -30,11 +32,11 @@
 #include "dev_inflate.h"
 #include "dev_fastq.h"
 #include "fq_host.h"
+#include "fq_text.h"
 
 #define FQ_HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { slx_set_error("HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, __LINE__); return SLX_ENODEVICE; } } while (0)
 #define FQ_CHK(x) do { const int rc_ = (x); if (rc_ != SLX_OK) return rc_; } while (0)
 
-typedef unsigned long long fq_u64;
 typedef uint32_t fq_v4 __attribute__((ext_vector_type(4)));
 
 #define FQ_GATHER_MAX 4096u          // LDS image of one output tile, per wave
@@ -150,153 +152,35 @@ __global__ __launch_bounds__(256) void k_fq_gather(const fq_u64 *src, const fq_u
     for (uint32_t o = lane << 4; o < n16; o += 64 << 4) *reinterpret_cast<fq_v4 *>(out + t0 + o) = *reinterpret_cast<const fq_v4 *>(&img[wave][o]);
 }
 
-// ------------------------------------------------------------------ host: buffers
-struct FqDBuf {
-    void *p = nullptr; size_t cap = 0;
-    int ensure(size_t n, hipStream_t st = nullptr, size_t keep = 0)       // keep: leading bytes that survive a growth
-    {
-        if (n <= cap) return SLX_OK;
-        const size_t want = n + n / 4 + 256;
-        void *q = nullptr;
-        if (hipMalloc(&q, want) != hipSuccess) { (void)hipGetLastError(); slx_set_error("FASTQ reader: cannot allocate %zu bytes of HBM", want); return SLX_ENOMEM; }
-        if (keep && p) {
-            if (hipMemcpyAsync(q, p, keep, hipMemcpyDeviceToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { (void)hipFree(q); slx_set_error("FASTQ reader: device copy failed"); return SLX_ENODEVICE; }
-        }
-        if (p) (void)hipFree(p);
-        p = q; cap = want;
-        return SLX_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <typename T> T *as() const { return (T *)p; }
-};
-struct FqHBuf {
-    void *p = nullptr; size_t cap = 0;
-    int ensure(size_t n)
-    {
-        if (n <= cap) return SLX_OK;
-        const size_t want = n + n / 4 + 256;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; cap = 0;
-        if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); p = nullptr; slx_set_error("FASTQ reader: cannot pin %zu bytes", want); return SLX_ENOMEM; }
-        cap = want;
-        return SLX_OK;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-    template <typename T> T *as() const { return (T *)p; }
-};
-
-// ------------------------------------------------------------------ host: the producer of a plain or gzip file's bytes
-// A thread of its own reads (plain) or inflates (gzip: one DEFLATE stream is serial) the next chunks into pinned slots while the batch before is on the GPU.
-struct FqProducer {
-    static constexpr int NSLOT = 3;
-    struct Slot { uint8_t *p = nullptr; size_t n = 0; bool eof = false, err = false; };
-    Slot slot[NSLOT];
-    size_t chunk = 8u << 20;
-    std::thread th;
-    std::mutex mu;
-    std::condition_variable cv;
-    int head = 0, tail = 0, count = 0;
-    bool stop = false, running = false;
-    int fd = -1;
-    gzFile gz = nullptr;
-    size_t tail_pos = 0;          // bytes of slot[tail] already taken
-
-    void run()
-    {
-        for (;;) {
-            {
-                std::unique_lock<std::mutex> g(mu);
-                cv.wait(g, [&] { return stop || count < NSLOT; });
-                if (stop) return;
-            }
-            Slot &s = slot[head];
-            s.n = 0; s.eof = false; s.err = false;
-            while (s.n < chunk) {
-                long r;
-                if (gz) r = gzread(gz, s.p + s.n, (unsigned)std::min<size_t>(chunk - s.n, 1u << 30));
-                else r = (long)::read(fd, s.p + s.n, chunk - s.n);
-                if (r < 0) { s.err = true; break; }
-                if (r == 0) { s.eof = true; break; }
-                s.n += (size_t)r;
-            }
-            const bool last = s.eof || s.err;
-            {
-                std::lock_guard<std::mutex> g(mu);
-                head = (head + 1) % NSLOT; ++count;
-            }
-            cv.notify_all();
-            if (last) return;
-        }
-    }
-    void halt()
-    {
-        if (running) {
-            { std::lock_guard<std::mutex> g(mu); stop = true; }
-            cv.notify_all();
-            th.join();
-            running = false;
-        }
-        if (gz) { gzclose(gz); gz = nullptr; fd = -1; }
-        if (fd >= 0) { ::close(fd); fd = -1; }
-        head = tail = count = 0; stop = false; tail_pos = 0;
-    }
-    int start(const std::string &path, bool gzip)
-    {
-        halt();
-        fd = ::open(path.c_str(), O_RDONLY);
-        if (fd < 0) { slx_set_error("FASTQ reader: cannot open '%s'", path.c_str()); return SLX_EIO; }
-        if (gzip) {
-            gz = gzdopen(fd, "r");
-            if (!gz) { ::close(fd); fd = -1; slx_set_error("FASTQ reader: zlib cannot open '%s'", path.c_str()); return SLX_EIO; }
-            gzbuffer(gz, 1u << 20);
-        }
-        for (Slot &s : slot)
-            if (!s.p && hipHostMalloc((void **)&s.p, chunk, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); s.p = nullptr; slx_set_error("FASTQ reader: cannot pin %zu bytes", chunk); return SLX_ENOMEM; }
-        th = std::thread([this] { run(); });
-        running = true;
-        return SLX_OK;
-    }
-    // the slot to take bytes from (blocks until the producer has one)
-    Slot &front()
-    {
-        std::unique_lock<std::mutex> g(mu);
-        cv.wait(g, [&] { return count > 0; });
-        return slot[tail];
-    }
-    void pop()
-    {
-        { std::lock_guard<std::mutex> g(mu); tail = (tail + 1) % NSLOT; --count; tail_pos = 0; }
-        cv.notify_all();
-    }
-    void release() { halt(); for (Slot &s : slot) { if (s.p) (void)hipHostFree(s.p); s.p = nullptr; } }
-};
 
 // ------------------------------------------------------------------ host: the reader
-struct slx_fastq {
-    std::string path;
-    int device = 0, source = 0;
-    hipStream_t st = nullptr;
-    hipEvent_t ev[10] = {};
-    // BGZF: the file mapped, its members
-    int fd = -1; const uint8_t *map = nullptr; uint64_t fsize = 0;
-    std::vector<slx_bam_member> mem; int64_t next_member = 0;
-    FqProducer prod;
-    // the text window: d_text[cur][used, have) is text not yet delivered, [0, used) has been
-    FqDBuf d_text[2]; int cur = 0; uint64_t have = 0, used = 0; bool src_eof = false, done = false;
-    uint32_t tile_bytes = 4096, gather_tile = 2048; int fast_fail = 0;
-    FqDBuf d_comp, d_desc, d_err, d_count, d_base, d_tmp, d_line, d_first, d_slow;
+struct slx_fastq : FqText {          // the source, the text window and its line starts: fq_text.h
+    bool done = false;
+    uint32_t gather_tile = 2048; int fast_fail = 0;
+    FqDBuf d_first, d_slow;
     FqDBuf d_len_b, d_len_n, d_len_c, d_src_b, d_src_q, d_src_n, d_src_c, d_flags, d_off_b, d_off_n, d_off_c, d_bases, d_quals, d_names, d_coms;
-    FqHBuf h_comp, h_desc, h_err, h_small, h_tail, h_slow;
+    FqHBuf h_tail, h_slow;
     int64_t c_reads = 0, c_fast = 0, c_slow = 0, c_batches = 0, c_bad_tail = 0;
-    float us[4] = {0, 0, 0, 0};          // lines, check, gather, inflate
     slx_fastq_batch last = {};
     uint64_t tot_b = 0, tot_n = 0, tot_c = 0;
-    std::vector<FqDBuf *> dbufs() { return {&d_text[0], &d_text[1], &d_comp, &d_desc, &d_err, &d_count, &d_base, &d_tmp, &d_line, &d_first, &d_slow, &d_len_b, &d_len_n, &d_len_c, &d_src_b, &d_src_q, &d_src_n, &d_src_c,
+    std::vector<FqDBuf *> dbufs() { return {&d_first, &d_slow, &d_len_b, &d_len_n, &d_len_c, &d_src_b, &d_src_q, &d_src_n, &d_src_c,
                                            &d_flags, &d_off_b, &d_off_n, &d_off_c, &d_bases, &d_quals, &d_names, &d_coms}; }
-    std::vector<FqHBuf *> hbufs() { return {&h_comp, &h_desc, &h_err, &h_small, &h_tail, &h_slow}; }
+    std::vector<FqHBuf *> hbufs() { return {&h_tail, &h_slow}; }
 };
 
-static float fq_ev_us(hipEvent_t a, hipEvent_t b) { float ms = 0; return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms * 1000.f : 0.f; }
+void fq_text_free(FqText *t)
+{
+    t->prod.release();
+    if (t->st) { (void)hipSetDevice(t->device); (void)hipStreamSynchronize(t->st); }
+    for (FqDBuf *b : t->text_dbufs()) b->release();
+    for (FqHBuf *b : t->text_hbufs()) b->release();
+    for (auto &e : t->ev) if (e) (void)hipEventDestroy(e);
+    if (t->st) (void)hipStreamDestroy(t->st);
+    if (t->map) munmap((void *)t->map, t->fsize);
+    if (t->fd >= 0) ::close(t->fd);
+    t->st = nullptr; t->map = nullptr; t->fd = -1;
+    for (auto &e : t->ev) e = nullptr;
+}
 
 static void fq_free(slx_fastq *fq)
 {
@@ -304,31 +188,33 @@ static void fq_free(slx_fastq *fq)
     if (fq->st) { (void)hipSetDevice(fq->device); (void)hipStreamSynchronize(fq->st); }
     for (FqDBuf *b : fq->dbufs()) b->release();
     for (FqHBuf *b : fq->hbufs()) b->release();
-    for (auto &e : fq->ev) if (e) (void)hipEventDestroy(e);
-    if (fq->st) (void)hipStreamDestroy(fq->st);
-    if (fq->map) munmap((void *)fq->map, fq->fsize);
-    if (fq->fd >= 0) ::close(fq->fd);
+    fq_text_free(fq);
     delete fq;
+}
+
+int fq_text_start(FqText *t)
+{
+    t->have = t->used = 0; t->src_eof = false; t->next_member = 0; t->c_members = 0;
+    for (float &u : t->us) u = 0;
+    if (t->source != 1) FQ_CHK(t->prod.start(t->path, t->source == 2));
+    return SLX_OK;
 }
 
 static int fq_start(slx_fastq *fq)
 {
-    fq->have = fq->used = 0; fq->src_eof = false; fq->done = false; fq->next_member = 0;
+    fq->done = false;
     fq->c_reads = fq->c_fast = fq->c_slow = fq->c_batches = fq->c_bad_tail = 0;
-    for (float &u : fq->us) u = 0;
     fq->last = slx_fastq_batch{};
-    if (fq->source != 1) FQ_CHK(fq->prod.start(fq->path, fq->source == 2));
-    return SLX_OK;
+    return fq_text_start(fq);
 }
 
-extern "C" int slx_fastq_open(const char *path, int device, slx_fastq **out)
+int fq_text_open(FqText *t, const char *path, int device)
 {
-    if (!path || !out) { slx_set_error("slx_fastq_open: null argument"); return SLX_EINVAL; }
-    *out = nullptr;
+    const char *who = t->who;
     struct stat sb;
-    if (stat(path, &sb) != 0 || !S_ISREG(sb.st_mode)) { slx_set_error("FASTQ reader: '%s' is missing or not a regular file", path); return SLX_EIO; }
+    if (stat(path, &sb) != 0 || !S_ISREG(sb.st_mode)) { slx_set_error("%s: '%s' is missing or not a regular file", who, path); return SLX_EIO; }
     const int fd = ::open(path, O_RDONLY);
-    if (fd < 0) { slx_set_error("FASTQ reader: cannot open '%s'", path); return SLX_EIO; }
+    if (fd < 0) { slx_set_error("%s: cannot open '%s'", who, path); return SLX_EIO; }
     uint8_t h[18] = {0};
     const ssize_t got = ::pread(fd, h, sizeof h, 0);
     int source = 0;
@@ -337,30 +223,36 @@ extern "C" int slx_fastq_open(const char *path, int device, slx_fastq **out)
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         (void)hipGetLastError();
         ::close(fd);
-        slx_set_error("no HIP device: the FASTQ reader parses on MI355X only (no CPU fallback)");
+        slx_set_error("no HIP device: the %s parses on MI355X only (no CPU fallback)", who);
         return SLX_ENODEVICE;
     }
-    slx_fastq *fq = new slx_fastq();
-    fq->path = path; fq->source = source;
+    t->path = path; t->source = source;
     if (source == 1) {
-        fq->fd = fd; fq->fsize = (uint64_t)sb.st_size;
-        void *p = mmap(nullptr, fq->fsize, PROT_READ, MAP_PRIVATE, fd, 0);
-        if (p == MAP_FAILED) { fq_free(fq); slx_set_error("FASTQ reader: cannot map '%s'", path); return SLX_EIO; }
-        fq->map = (const uint8_t *)p;
+        t->fd = fd; t->fsize = (uint64_t)sb.st_size;
+        void *p = mmap(nullptr, t->fsize, PROT_READ, MAP_PRIVATE, fd, 0);
+        if (p == MAP_FAILED) { slx_set_error("%s: cannot map '%s'", who, path); return SLX_EIO; }
+        t->map = (const uint8_t *)p;
         slx_bam_member *m = nullptr; int64_t nm = 0;
-        const int rc = slx_bam_scan_members(path, &m, &nm, nullptr);
-        if (rc != SLX_OK) { fq_free(fq); return rc; }
-        fq->mem.assign(m, m + nm);
+        FQ_CHK(slx_bam_scan_members(path, &m, &nm, nullptr));
+        t->mem.assign(m, m + nm);
         slx_bam_members_free(m);
     } else ::close(fd);
-    auto fail = [&](int rc) { fq_free(fq); return rc; };
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) { slx_set_error("FASTQ reader: no current device"); return fail(SLX_ENODEVICE); }
-    if (device >= ndev) { slx_set_error("FASTQ reader: device %d is not one of the %d visible", device, ndev); return fail(SLX_EINVAL); }
-    fq->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&fq->st, hipStreamNonBlocking) != hipSuccess) { slx_set_error("FASTQ reader: cannot create a stream on device %d", device); return fail(SLX_ENODEVICE); }
-    for (auto &e : fq->ev) if (hipEventCreate(&e) != hipSuccess) { slx_set_error("FASTQ reader: cannot create an event"); return fail(SLX_ENODEVICE); }
-    const int rc = fq_start(fq);
-    if (rc != SLX_OK) return fail(rc);
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) { slx_set_error("%s: no current device", who); return SLX_ENODEVICE; }
+    if (device >= ndev) { slx_set_error("%s: device %d is not one of the %d visible", who, device, ndev); return SLX_EINVAL; }
+    t->device = device;
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&t->st, hipStreamNonBlocking) != hipSuccess) { slx_set_error("%s: cannot create a stream on device %d", who, device); return SLX_ENODEVICE; }
+    for (auto &e : t->ev) if (hipEventCreate(&e) != hipSuccess) { slx_set_error("%s: cannot create an event", who); return SLX_ENODEVICE; }
+    return SLX_OK;
+}
+
+extern "C" int slx_fastq_open(const char *path, int device, slx_fastq **out)
+{
+    if (!path || !out) { slx_set_error("slx_fastq_open: null argument"); return SLX_EINVAL; }
+    *out = nullptr;
+    slx_fastq *fq = new slx_fastq();
+    int rc = fq_text_open(fq, path, device);
+    if (rc == SLX_OK) rc = fq_start(fq);
+    if (rc != SLX_OK) { fq_free(fq); return rc; }
     *out = fq;
     return SLX_OK;
 }
@@ -403,7 +295,7 @@ extern "C" int64_t slx_fastq_counter(const slx_fastq *fq, const char *name)
 }
 
 // at least `want` more bytes of text (fewer only at the end of the source) behind d_text[cur][have)
-static int fq_pull(slx_fastq *fq, uint64_t want)
+int fq_pull(FqText *fq, uint64_t want)
 {
     hipStream_t st = fq->st;
     FqDBuf &T = fq->d_text[fq->cur];
@@ -434,7 +326,7 @@ static int fq_pull(slx_fastq *fq, uint64_t want)
             FQ_HIPCHK(hipEventRecord(fq->ev[9], st));
             FQ_HIPCHK(hipMemcpyAsync(fq->h_err.p, fq->d_err.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
             FQ_HIPCHK(slx_wait_stream(st));
-            fq->us[3] += fq_ev_us(fq->ev[8], fq->ev[9]);
+            fq->us[3] += fq_ev_us(fq->ev[8], fq->ev[9]); fq->c_members += n;
             const uint32_t *err = fq->h_err.as<uint32_t>();
             for (int i = 0; i < n; ++i)
                 if (err[i]) { slx_set_error("BGZF: '%s': the member at file offset %llu does not inflate (code %u)", fq->path.c_str(), (unsigned long long)fq->mem[a + i].file_off, err[i]); return SLX_EIO; }
@@ -447,7 +339,7 @@ static int fq_pull(slx_fastq *fq, uint64_t want)
     uint64_t got = 0;
     while (got < want && !fq->src_eof) {
         FqProducer::Slot &s = fq->prod.front();
-        if (s.err) { slx_set_error("FASTQ reader: reading '%s' failed%s", fq->path.c_str(), fq->source == 2 ? " (zlib refuses the stream)" : ""); return SLX_EIO; }
+        if (s.err) { slx_set_error("%s: reading '%s' failed%s", fq->who, fq->path.c_str(), fq->source == 2 ? " (zlib refuses the stream)" : ""); return SLX_EIO; }
         const uint64_t take = std::min<uint64_t>(want - got, s.n - fq->prod.tail_pos);
         if (take) {
             FQ_CHK(T.ensure(fq->have + take + 64, st, fq->have));
@@ -463,7 +355,7 @@ static int fq_pull(slx_fastq *fq, uint64_t want)
     return SLX_OK;
 }
 
-static int fq_scan(slx_fastq *fq, const fq_u64 *in, fq_u64 *out, uint64_t n)
+int fq_scan(FqText *fq, const fq_u64 *in, fq_u64 *out, uint64_t n)
 {
     size_t tb = 0;
     FQ_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int64_t)n, fq->st));
@@ -472,18 +364,15 @@ static int fq_scan(slx_fastq *fq, const fq_u64 *in, fq_u64 *out, uint64_t n)
     return SLX_OK;
 }
 
-// one attempt on d_text[cur][0, have): *n_reads reads into the output arrays, *consumed bytes of text used up (also when no read came of it)
-static int fq_parse(slx_fastq *fq, int64_t *n_reads, int64_t *n_slow, uint64_t *consumed)
+int fq_line_starts(FqText *fq, uint64_t *n_lines, int *virt_out)
 {
     hipStream_t st = fq->st;
     const uint8_t *text = fq->d_text[fq->cur].as<uint8_t>();
     const uint64_t n = fq->have;
-    const bool eof = fq->src_eof;
     const uint32_t tile = fq->tile_bytes;
     const uint64_t n_tiles = (n + tile - 1) / tile;
     FQ_CHK(fq->h_small.ensure(256));
     fq_u64 *hs = fq->h_small.as<fq_u64>();
-    // ---- line starts
     FQ_CHK(fq->d_count.ensure(8 * (n_tiles + 1))); FQ_CHK(fq->d_base.ensure(8 * (n_tiles + 1)));
     FQ_HIPCHK(hipMemsetAsync(fq->d_count.p, 0, 8 * (n_tiles + 1), st));
     FQ_HIPCHK(hipEventRecord(fq->ev[0], st));
@@ -494,12 +383,38 @@ static int fq_parse(slx_fastq *fq, int64_t *n_reads, int64_t *n_slow, uint64_t *
     FQ_HIPCHK(hipMemcpyAsync(hs + 1, text + n - 1, 1, hipMemcpyDeviceToHost, st));
     FQ_HIPCHK(slx_wait_stream(st));
     const uint64_t n_nl = hs[0];
-    const int virt = eof && *(const uint8_t *)(hs + 1) != '\n' ? 1 : 0;
+    const int virt = fq->src_eof && *(const uint8_t *)(hs + 1) != '\n' ? 1 : 0;
     const uint64_t L = n_nl + (uint64_t)virt;
     FQ_CHK(fq->d_line.ensure(8 * (L + 2)));
     k_fq_lines<<<(unsigned)((n_tiles + 3) / 4), 256, 0, st>>>(text, n, tile, n_tiles, fq->d_base.as<fq_u64>(), virt, fq->d_line.as<fq_u64>());
     FQ_HIPCHK(hipGetLastError());
     FQ_HIPCHK(hipEventRecord(fq->ev[1], st));
+    *n_lines = L; *virt_out = virt;
+    return SLX_OK;
+}
+
+int fq_shift(FqText *fq, uint64_t room)
+{
+    const uint64_t left = fq->have - fq->used;
+    FqDBuf &O = fq->d_text[fq->cur ^ 1];
+    FQ_CHK(O.ensure(left + room + 64));
+    if (left) FQ_HIPCHK(hipMemcpyAsync(O.p, fq->d_text[fq->cur].as<uint8_t>() + fq->used, left, hipMemcpyDeviceToDevice, fq->st));
+    FQ_HIPCHK(slx_wait_stream(fq->st));
+    fq->cur ^= 1; fq->have = left; fq->used = 0;
+    return SLX_OK;
+}
+
+// one attempt on d_text[cur][0, have): *n_reads reads into the output arrays, *consumed bytes of text used up (also when no read came of it)
+static int fq_parse(slx_fastq *fq, int64_t *n_reads, int64_t *n_slow, uint64_t *consumed)
+{
+    hipStream_t st = fq->st;
+    const uint8_t *text = fq->d_text[fq->cur].as<uint8_t>();
+    const uint64_t n = fq->have;
+    const bool eof = fq->src_eof;
+    uint64_t L = 0;
+    int virt = 0;
+    FQ_CHK(fq_line_starts(fq, &L, &virt));          // ---- line starts
+    fq_u64 *hs = fq->h_small.as<fq_u64>();
     // ---- the records taken as four lines each
     const uint64_t n_cand = L / 4 + 1;
     FqDBuf *per8[7] = {&fq->d_len_b, &fq->d_len_n, &fq->d_len_c, &fq->d_src_b, &fq->d_src_q, &fq->d_src_n, &fq->d_src_c};
@@ -624,14 +539,7 @@ extern "C" int slx_fastq_next(slx_fastq *fq, int64_t max_bytes, slx_fastq_batch 
     hipStream_t st = fq->st;
     uint64_t target = (uint64_t)max_bytes, text_bytes = 0;
     for (;;) {
-        if (fq->used) {          // the cut tail moves to the front of the other buffer
-            const uint64_t left = fq->have - fq->used;
-            FqDBuf &O = fq->d_text[fq->cur ^ 1];
-            FQ_CHK(O.ensure(left + target + 64));
-            if (left) FQ_HIPCHK(hipMemcpyAsync(O.p, fq->d_text[fq->cur].as<uint8_t>() + fq->used, left, hipMemcpyDeviceToDevice, st));
-            FQ_HIPCHK(slx_wait_stream(st));
-            fq->cur ^= 1; fq->have = left; fq->used = 0;
-        }
+        if (fq->used) FQ_CHK(fq_shift(fq, target));          // the cut tail moves to the front of the other buffer
         if (fq->have < target && !fq->src_eof) FQ_CHK(fq_pull(fq, target - fq->have));
         if (fq->have == 0) {
             if (fq->src_eof) { fq->done = true; return SLX_OK; }
