@@ -25,9 +25,9 @@ def build(force=False, verbose=False):
     is_fml = lambda f: "fml" in f
     is_bam = lambda f: f in ("slx_bam.hip", "slx_bai.cpp", "slx_bgzf.hip", "slx_rec.hip", "slx_sort.hip", "slx_filter.hip", "slx_fastq.hip", "slx_sam.hip", "dev_fastq.h", "fq_host.h", "fq_text.h", "dev_sam.h", "sam_host.h", "sam_reader.h", "dev_rfilter.h", "rfilter_host.h", "dev_inflate.h", "dev_deflate.h", "dev_bamidx.h", "dev_bai.h", "bai_host.h", "dev_rec.h", "dev_recsort.h", "recsort_host.h")          # the BamReader / BamWriter path (slx_bam.hip, slx_bgzf.hip, slx_rec.hip, slx_sort.hip, slx_filter.hip, slx_fastq.hip, slx_sam.hip), a third group
     hdr_align = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc")) and not is_fml(f) and not is_bam(f)] + [os.path.join(ROOT, "include", "seqlib_amd.h")]
-    hdr_bam = [os.path.join(CSRC, f) for f in ("dev_inflate.h", "dev_deflate.h", "dev_bamidx.h", "dev_bai.h", "bai_host.h", "dev_rec.h", "dev_recsort.h", "recsort_host.h", "dev_rfilter.h", "rfilter_host.h", "dev_fastq.h", "fq_host.h", "fq_text.h", "dev_sam.h", "sam_host.h", "sam_reader.h", "dev_wave.h", "slx_internal.h")] + [os.path.join(ROOT, "include", f) for f in ("seqlib_amd.h", "seqlib_amd_bam.h", "seqlib_amd_rec.h", "seqlib_amd_sort.h", "seqlib_amd_filter.h", "seqlib_amd_fastq.h", "seqlib_amd_sam.h")]
+    hdr_bam = [os.path.join(CSRC, f) for f in ("dev_inflate.h", "dev_deflate.h", "dev_bamidx.h", "dev_bai.h", "bai_host.h", "dev_rec.h", "dev_recsort.h", "recsort_host.h", "dev_rfilter.h", "rfilter_host.h", "dev_fastq.h", "fq_host.h", "fq_text.h", "dev_sam.h", "sam_host.h", "sam_reader.h", "dev_wave.h", "slx_internal.h", "slx_hip.h")] + [os.path.join(ROOT, "include", f) for f in ("seqlib_amd.h", "seqlib_amd_bam.h", "seqlib_amd_rec.h", "seqlib_amd_sort.h", "seqlib_amd_filter.h", "seqlib_amd_fastq.h", "seqlib_amd_sam.h")]
     hdr_fml = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h") and is_fml(f)] + \
-              [os.path.join(CSRC, "slx_internal.h"), os.path.join(CSRC, "dev_wave.h"), os.path.join(ROOT, "include", "seqlib_amd.h"), os.path.join(ROOT, "include", "seqlib_amd_fml.h")]
+              [os.path.join(CSRC, "slx_internal.h"), os.path.join(CSRC, "slx_hip.h"), os.path.join(CSRC, "dev_wave.h"), os.path.join(ROOT, "include", "seqlib_amd.h"), os.path.join(ROOT, "include", "seqlib_amd_fml.h")]
     objs, procs = [], []
     os.makedirs(os.path.join(HERE, "build"), exist_ok=True)
     for s in SOURCES:                      # the translation units compile side by side

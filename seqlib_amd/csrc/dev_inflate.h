@@ -293,10 +293,20 @@ INF_FN uint32_t inf_crc_part(const uint32_t *tab, const uint8_t *p, uint32_t n, 
 }
 
 #if defined(__HIPCC__)
-// ---- the launch of k_bgzf_inflate + k_bgzf_crc (slx_bam.hip), for the other translation units that inflate BGZF members (slx_fastq.hip) ----
-#include <hip/hip_runtime.h>
+// ---- members of a mapped BGZF file staged, inflated by k_bgzf_inflate and checked by k_bgzf_crc (slx_bam.hip): for every reader of BGZF (slx_bam.hip, slx_fastq.hip) ----
+#include "slx_hip.h"
+#include "seqlib_amd_bam.h"
 // one member: its deflate stream lies at comp + in_off (in_len bytes), its isize bytes go to out + out_off, crc is its trailer's
 struct bam_mdesc { uint64_t in_off, out_off; uint32_t in_len, isize, crc, pad; };
-// both kernels on st over the n members of d_desc (one wave per member), everything in HBM: d_err[i] = INF_OK or an INF_E_* code.  The launches' hipGetLastError()
-hipError_t slx_bgzf_inflate_launch(hipStream_t st, const uint8_t *d_comp, uint64_t comp_bytes, const bam_mdesc *d_desc, int n, uint8_t *d_out, uint64_t out_bytes, uint32_t *d_err);
+// what a reader keeps for the call below: the members' compressed bytes, their descriptors and their error words, pinned and in HBM (1/4 + 256: kept as found)
+struct bgzf_stage {
+    SlxPinBuf<SlxMargin<4, 256>> h_comp, h_desc, h_err;
+    SlxDevBuf<SlxMargin<4, 256>> d_comp, d_desc, d_err;
+    void release() { h_comp.release(); h_desc.release(); h_err.release(); d_comp.release(); d_desc.release(); d_err.release(); }
+};
+// Members [a, b) of mem, whose bytes lie in the mapped file `map`, inflated to d_out[dst_off ..) one behind the other and CRC-checked, one wave per member; d_out
+// holds out_bytes (SLX_EINTERNAL when the members do not fit).  Returns after st has drained; SLX_EIO names the first member that does not inflate (path is the
+// file's name in that message).  us[0] += the inflate kernel's microseconds (ev0 .. ev_mid), us[1] += the CRC kernel's (ev_mid .. ev1); without ev_mid us[0] takes both.
+int slx_bgzf_inflate_members(const uint8_t *map, const char *path, const slx_bam_member *mem, int64_t a, int64_t b, bgzf_stage &S, uint8_t *d_out, uint64_t dst_off,
+                             uint64_t out_bytes, hipStream_t st, hipEvent_t ev0, hipEvent_t ev_mid, hipEvent_t ev1, float us[2]);
 #endif

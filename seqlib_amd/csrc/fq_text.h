@@ -1,5 +1,5 @@
 // fq_text.h -- where the bytes of a text file come from, for the readers that parse text on the GPU (slx_fastq.hip, slx_sam.hip): plain text read and gzip inflated
-// (zlib, one DEFLATE stream is serial) by a producer thread into pinned slots, BGZF members inflated and CRC-checked on the GPU (slx_bgzf_inflate_launch), the window
+// (zlib, one DEFLATE stream is serial) by a producer thread into pinned slots, BGZF members inflated and CRC-checked on the GPU (slx_bgzf_inflate_members), the window
 // of text in HBM, and its line starts (k_fq_count / k_fq_lines).  DESIGN.md section 9.6.  The functions are defined in slx_fastq.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -18,42 +18,14 @@
 #include <vector>
 #include "slx_internal.h"
 #include "seqlib_amd_bam.h"
+#include "slx_hip.h"
+#include "dev_inflate.h"
 
 typedef unsigned long long fq_u64;
 // ------------------------------------------------------------------ host: buffers
-struct FqDBuf {
-    void *p = nullptr; size_t cap = 0;
-    int ensure(size_t n, hipStream_t st = nullptr, size_t keep = 0)       // keep: leading bytes that survive a growth
-    {
-        if (n <= cap) return SLX_OK;
-        const size_t want = n + n / 4 + 256;
-        void *q = nullptr;
-        if (hipMalloc(&q, want) != hipSuccess) { (void)hipGetLastError(); slx_set_error("text reader: cannot allocate %zu bytes of HBM", want); return SLX_ENOMEM; }
-        if (keep && p) {
-            if (hipMemcpyAsync(q, p, keep, hipMemcpyDeviceToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { (void)hipFree(q); slx_set_error("text reader: device copy failed"); return SLX_ENODEVICE; }
-        }
-        if (p) (void)hipFree(p);
-        p = q; cap = want;
-        return SLX_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <typename T> T *as() const { return (T *)p; }
-};
-struct FqHBuf {
-    void *p = nullptr; size_t cap = 0;
-    int ensure(size_t n)
-    {
-        if (n <= cap) return SLX_OK;
-        const size_t want = n + n / 4 + 256;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; cap = 0;
-        if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); p = nullptr; slx_set_error("text reader: cannot pin %zu bytes", want); return SLX_ENOMEM; }
-        cap = want;
-        return SLX_OK;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-    template <typename T> T *as() const { return (T *)p; }
-};
+// the text readers' buffers in HBM and pinned: a margin of 1/4 + 256 bytes on every growth, kept as found
+typedef SlxDevBuf<SlxMargin<4, 256>> FqDBuf;
+typedef SlxPinBuf<SlxMargin<4, 256>> FqHBuf;
 
 // ------------------------------------------------------------------ host: the producer of a plain or gzip file's bytes
 // A thread of its own reads (plain) or inflates (gzip: one DEFLATE stream is serial) the next chunks into pinned slots while the batch before is on the GPU.
@@ -155,15 +127,14 @@ struct FqText {
     // the text window: d_text[cur][used, have) is text not yet delivered, [0, used) has been
     FqDBuf d_text[2]; int cur = 0; uint64_t have = 0, used = 0; bool src_eof = false;
     uint32_t tile_bytes = 4096;
-    FqDBuf d_comp, d_desc, d_err, d_count, d_base, d_tmp, d_line;
-    FqHBuf h_comp, h_desc, h_err, h_small;
+    bgzf_stage stage;                    // slx_bgzf_inflate_members' buffers
+    FqDBuf d_count, d_base, d_tmp, d_line;
+    FqHBuf h_small;
     float us[4] = {0, 0, 0, 0};          // lines, check, gather, inflate
     int64_t c_members = 0;               // BGZF members inflated since the last fq_text_start
-    std::vector<FqDBuf *> text_dbufs() { return {&d_text[0], &d_text[1], &d_comp, &d_desc, &d_err, &d_count, &d_base, &d_tmp, &d_line}; }
-    std::vector<FqHBuf *> text_hbufs() { return {&h_comp, &h_desc, &h_err, &h_small}; }
+    std::vector<FqDBuf *> text_dbufs() { return {&d_text[0], &d_text[1], &d_count, &d_base, &d_tmp, &d_line}; }
+    std::vector<FqHBuf *> text_hbufs() { return {&h_small}; }
 };
-
-static inline float fq_ev_us(hipEvent_t a, hipEvent_t b) { float ms = 0; return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms * 1000.f : 0.f; }
 
 // the kind of source from the file's first bytes, the BGZF member table, the device, the stream and the events.  SLX_ENODEVICE without a GPU
 int fq_text_open(FqText *t, const char *path, int device);
@@ -176,7 +147,7 @@ int fq_pull(FqText *t, uint64_t want);
 // the cut tail d_text[cur][used, have) moves to the front of the other buffer, which is made to hold room bytes behind it
 int fq_shift(FqText *t, uint64_t room);
 // exclusive sum of n values on the reader's stream
-int fq_scan(FqText *t, const fq_u64 *in, fq_u64 *out, uint64_t n);
+static inline int fq_scan(FqText *t, const fq_u64 *in, fq_u64 *out, uint64_t n) { return slx_exclusive_sum(t->d_tmp, in, out, n, t->st, 16); }
 // d_line = the line starts of d_text[cur][0, have): *n_lines + 1 entries, entry 0 = 0, entry 1 + j = the byte behind line feed j; at the end of the source a last line
 // without a line feed counts (*virt = 1, its entry have + 1).  Returns after the stream has drained up to the count (the starts themselves may still be in flight).
 int fq_line_starts(FqText *t, uint64_t *n_lines, int *virt);

@@ -7,49 +7,16 @@
 #include <string>
 #include <vector>
 #include "slx_internal.h"
+#include "slx_hip.h"
 #include "dev_fm.h"
 #include "dev_types.h"
 
-#define HIPCHK(x)                                                                                   \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) {                                                                     \
-            slx_set_error("HIP error %s at %s:%d (%s)", hipGetErrorString(e_), __FILE__, __LINE__, #x); \
-            return e_ == hipErrorOutOfMemory ? SLX_ENOMEM : SLX_ENODEVICE;                          \
-        }                                                                                           \
-    } while (0)
+#define HIPCHK(x) SLX_HIPCHK(x)
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes)
-    {
-        if (bytes <= cap) return SLX_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        size_t want = bytes + bytes / 8 + 256;
-        HIPCHK(hipMalloc(&p, want));
-        cap = want;
-        return SLX_OK;
-    }
-    // grow keeping contents
-    int grow(size_t bytes, size_t keep, hipStream_t st)
-    {
-        if (bytes <= cap) return SLX_OK;
-        void *q = nullptr;
-        size_t want = bytes + bytes / 2 + 256;
-        HIPCHK(hipMalloc(&q, want));
-        if (p && keep) {
-            hipError_t e = hipMemcpyAsync(q, p, keep, hipMemcpyDeviceToDevice, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) { (void)hipFree(q); HIPCHK(e); }
-        }
-        if (p) (void)hipFree(p);
-        p = q; cap = want;
-        return SLX_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <typename T> T *as() const { return (T *)p; }
+// The aligner's work areas and results: a margin of 1/8 + 256 bytes on every growth, kept as found.  grow keeps the leading `keep` bytes (results gathered chunk
+// after chunk, lists enlarged in the middle of a chunk) and takes a margin of 1/2 + 256, kept as found.
+struct DevBuf : SlxDevBuf<SlxMargin<8, 256>> {
+    int grow(size_t bytes, size_t keep, hipStream_t st) { return bytes <= cap ? SLX_OK : slx_dev_realloc(&p, &cap, SlxMargin<2, 256>::want(bytes), st, keep); }
 };
 
 // The host sizes every stage by a few counters of the one before.  Each used to come back with a hipMemcpyAsync of its own into a pageable local -- five after

@@ -28,9 +28,7 @@
 #include "dev_bai.h"
 #include "bai_host.h"
 #include "sam_reader.h"
-
-#define BAM_HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { slx_set_error("HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, __LINE__); return SLX_ENODEVICE; } } while (0)
-#define BAM_CHK(x) do { const int rc_ = (x); if (rc_ != SLX_OK) return rc_; } while (0)
+#include "slx_hip.h"
 
 // ------------------------------------------------------------------ kernels
 __global__ __launch_bounds__(256) void k_bgzf_inflate(const uint8_t *comp, uint64_t comp_bytes, const bam_mdesc *m, int n, uint8_t *out, uint64_t out_bytes, uint32_t *err)
@@ -61,12 +59,62 @@ __global__ __launch_bounds__(256) void k_bgzf_crc(const bam_mdesc *m, int n, con
     if (lane == 0 && c != d.crc) err[idx] = INF_E_CRC;
 }
 
-hipError_t slx_bgzf_inflate_launch(hipStream_t st, const uint8_t *d_comp, uint64_t comp_bytes, const bam_mdesc *d_desc, int n, uint8_t *d_out, uint64_t out_bytes, uint32_t *d_err)
+static const char *inf_errtext(uint32_t e)
 {
-    if (n <= 0) return hipSuccess;
-    k_bgzf_inflate<<<(n + 3) / 4, 256, 0, st>>>(d_comp, comp_bytes, d_desc, n, d_out, out_bytes, d_err);
-    k_bgzf_crc<<<(n + 3) / 4, 256, 0, st>>>(d_desc, n, d_out, out_bytes, d_err);
-    return hipGetLastError();
+    switch (e) {
+    case INF_E_EOF: return "the deflate stream runs past the member's compressed bytes";
+    case INF_E_BTYPE: return "invalid deflate block type";
+    case INF_E_STORED: return "stored block with LEN / NLEN mismatch or bytes past the member";
+    case INF_E_CODE: return "invalid, incomplete or over-subscribed Huffman code";
+    case INF_E_SYM: return "invalid length or distance symbol";
+    case INF_E_DIST: return "match distance beyond the output so far";
+    case INF_E_OUT: return "output passes ISIZE";
+    case INF_E_ISIZE: return "stream ends before ISIZE bytes";
+    case INF_E_CRC: return "CRC32 mismatch";
+    case INF_E_DESC: return "member descriptor outside the buffers";
+    }
+    return "unknown error";
+}
+
+int slx_bgzf_inflate_members(const uint8_t *map, const char *path, const slx_bam_member *mem, int64_t a, int64_t b, bgzf_stage &S, uint8_t *d_out, uint64_t dst_off,
+                             uint64_t out_bytes, hipStream_t st, hipEvent_t ev0, hipEvent_t ev_mid, hipEvent_t ev1, float us[2])
+{
+    const int n = (int)(b - a);
+    if (n <= 0) return SLX_OK;
+    uint64_t comp = 0;
+    for (int64_t i = a; i < b; ++i) comp += mem[i].data_len;
+    SLX_CHK(S.h_comp.ensure(comp + 8)); SLX_CHK(S.d_comp.ensure(comp + 8));
+    SLX_CHK(S.h_desc.ensure(sizeof(bam_mdesc) * n)); SLX_CHK(S.d_desc.ensure(sizeof(bam_mdesc) * n));
+    SLX_CHK(S.h_err.ensure(4 * (size_t)n)); SLX_CHK(S.d_err.ensure(4 * (size_t)n));
+    bam_mdesc *d = S.h_desc.as<bam_mdesc>();
+    uint64_t ci = 0, oo = dst_off;
+    for (int64_t i = a; i < b; ++i) {
+        const slx_bam_member &m = mem[i];
+        memcpy(S.h_comp.as<uint8_t>() + ci, map + m.file_off + m.data_off, m.data_len);
+        d[i - a] = bam_mdesc{ci, oo, m.data_len, m.isize, m.crc32, 0};
+        ci += m.data_len; oo += m.isize;
+    }
+    if (oo > out_bytes) { slx_set_error("BGZF: internal: span of %llu bytes does not fit %llu", (unsigned long long)oo, (unsigned long long)out_bytes); return SLX_EINTERNAL; }
+    SLX_HIPCHK(hipMemcpyAsync(S.d_comp.p, S.h_comp.p, comp, hipMemcpyHostToDevice, st));
+    SLX_HIPCHK(hipMemcpyAsync(S.d_desc.p, S.h_desc.p, sizeof(bam_mdesc) * n, hipMemcpyHostToDevice, st));
+    SLX_HIPCHK(hipEventRecord(ev0, st));
+    k_bgzf_inflate<<<(n + 3) / 4, 256, 0, st>>>(S.d_comp.as<uint8_t>(), comp, S.d_desc.as<bam_mdesc>(), n, d_out, out_bytes, S.d_err.as<uint32_t>());
+    SLX_HIPCHK(hipGetLastError());
+    if (ev_mid) SLX_HIPCHK(hipEventRecord(ev_mid, st));
+    k_bgzf_crc<<<(n + 3) / 4, 256, 0, st>>>(S.d_desc.as<bam_mdesc>(), n, d_out, out_bytes, S.d_err.as<uint32_t>());
+    SLX_HIPCHK(hipGetLastError());
+    SLX_HIPCHK(hipEventRecord(ev1, st));
+    SLX_HIPCHK(hipMemcpyAsync(S.h_err.p, S.d_err.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(slx_wait_stream(st));
+    if (ev_mid) { us[0] += slx_ev_us(ev0, ev_mid); us[1] += slx_ev_us(ev_mid, ev1); }
+    else us[0] += slx_ev_us(ev0, ev1);
+    const uint32_t *err = S.h_err.as<uint32_t>();
+    for (int i = 0; i < n; ++i)
+        if (err[i]) {
+            slx_set_error("BGZF: '%s': the member at file offset %llu does not inflate: %s", path, (unsigned long long)mem[a + i].file_off, inf_errtext(err[i]));
+            return SLX_EIO;
+        }
+    return SLX_OK;
 }
 
 // state of the index: [0] records, [1] repaired chunks, [2] lowest start of a record with block_size < 32, [3] end of the last whole record, [4] changed (rounds)
@@ -415,7 +463,7 @@ extern "C" int slx_bam_scan_members(const char *path, slx_bam_member **members, 
 {
     if (!members || !n_members) { slx_set_error("slx_bam_scan_members: null output"); return SLX_EINVAL; }
     BamFile f;
-    BAM_CHK(bam_scan(path, f));
+    SLX_CHK(bam_scan(path, f));
     slx_bam_member *m = (slx_bam_member *)malloc(sizeof(slx_bam_member) * f.mem.size());
     if (!m) { slx_set_error("out of memory"); return SLX_ENOMEM; }
     memcpy(m, f.mem.data(), sizeof(slx_bam_member) * f.mem.size());
@@ -426,37 +474,9 @@ extern "C" int slx_bam_scan_members(const char *path, slx_bam_member **members, 
 extern "C" void slx_bam_members_free(slx_bam_member *members) { free(members); }
 
 // ------------------------------------------------------------------ host: the device side
-struct BamDBuf {
-    void *p = nullptr; size_t cap = 0;
-    int ensure(size_t n, hipStream_t st = nullptr, size_t keep = 0)       // keep: leading bytes that survive a growth
-    {
-        if (n <= cap) return SLX_OK;
-        const size_t want = n + n / 4 + 256;
-        void *q = nullptr;
-        if (hipMalloc(&q, want) != hipSuccess) { (void)hipGetLastError(); slx_set_error("BAM reader: cannot allocate %zu bytes of HBM", want); return SLX_ENOMEM; }
-        if (keep && p) { BAM_HIPCHK(hipMemcpyAsync(q, p, keep, hipMemcpyDeviceToDevice, st)); BAM_HIPCHK(hipStreamSynchronize(st)); }
-        if (p) (void)hipFree(p);
-        p = q; cap = want;
-        return SLX_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <typename T> T *as() const { return (T *)p; }
-};
-struct BamHBuf {
-    void *p = nullptr; size_t cap = 0;
-    int ensure(size_t n)
-    {
-        if (n <= cap) return SLX_OK;
-        const size_t want = n + n / 4 + 256;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; cap = 0;
-        if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); p = nullptr; slx_set_error("BAM reader: cannot pin %zu bytes", want); return SLX_ENOMEM; }
-        cap = want;
-        return SLX_OK;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-    template <typename T> T *as() const { return (T *)p; }
-};
+// the reader's buffers in HBM and pinned: a margin of 1/4 + 256 bytes on every growth, kept as found
+typedef SlxDevBuf<SlxMargin<4, 256>> BamDBuf;
+typedef SlxPinBuf<SlxMargin<4, 256>> BamHBuf;
 
 struct slx_bam {
     BamFile f;
@@ -470,9 +490,10 @@ struct slx_bam {
     std::vector<uint8_t> carry0, carry;
     uint64_t chunk_bytes = 65536;
     int idx_fail = 0;
-    BamDBuf d_comp, d_desc, d_err, d_out, d_guess, d_used, d_exit_a, d_exit_b, d_count, d_base, d_state, d_rec, d_keep, d_blen, d_kidx, d_boff, d_tmp, d_bases, d_offs, d_map;
+    bgzf_stage stage;                                      // slx_bgzf_inflate_members' buffers
+    BamDBuf d_out, d_guess, d_used, d_exit_a, d_exit_b, d_count, d_base, d_state, d_rec, d_keep, d_blen, d_kidx, d_boff, d_tmp, d_bases, d_offs, d_map;
     BamDBuf d_cs, d_cr;                                    // region mode: the kept records compacted, and their offsets
-    BamHBuf h_comp, h_desc, h_err, h_out, h_rec, h_state, h_map;
+    BamHBuf h_out, h_rec, h_state, h_map;
     int64_t c_members_done = 0, c_repaired = 0, c_rounds = 0, c_records = 0, c_region_cand = 0, c_region_kept = 0;
     float us[5] = {0, 0, 0, 0, 0};
     const void *map_stream = nullptr; int64_t map_reads = 0; // the batch slx_bam_reads_device last unpacked (d_bases, d_offs, d_map hold its reads), and how many
@@ -489,41 +510,15 @@ struct slx_bam {
     slx_filter *flt = nullptr;                             // a read filter attached by slx_filter_attach; nullptr: nothing new is launched
     BamDBuf d_fkeep;                                       // its keep bytes
     slx_samsrc *sam = nullptr;                             // a reader over SAM text (slx_sam_open): the batches come from slx_sam.hip, there are no members
-    std::vector<BamDBuf *> dbufs() { return {&d_fkeep, &d_comp, &d_desc, &d_err, &d_out, &d_guess, &d_used, &d_exit_a, &d_exit_b, &d_count, &d_base, &d_state, &d_rec, &d_keep, &d_blen, &d_kidx, &d_boff, &d_tmp, &d_bases, &d_offs, &d_map, &d_cs, &d_cr}; }
-    std::vector<BamHBuf *> hbufs() { return {&h_comp, &h_desc, &h_err, &h_out, &h_rec, &h_state, &h_map}; }
+    std::vector<BamDBuf *> dbufs() { return {&d_fkeep, &d_out, &d_guess, &d_used, &d_exit_a, &d_exit_b, &d_count, &d_base, &d_state, &d_rec, &d_keep, &d_blen, &d_kidx, &d_boff, &d_tmp, &d_bases, &d_offs, &d_map, &d_cs, &d_cr}; }
+    std::vector<BamHBuf *> hbufs() { return {&h_out, &h_rec, &h_state, &h_map}; }
 };
-
-static const char *inf_errtext(uint32_t e)
-{
-    switch (e) {
-    case INF_E_EOF: return "the deflate stream runs past the member's compressed bytes";
-    case INF_E_BTYPE: return "invalid deflate block type";
-    case INF_E_STORED: return "stored block with LEN / NLEN mismatch or bytes past the member";
-    case INF_E_CODE: return "invalid, incomplete or over-subscribed Huffman code";
-    case INF_E_SYM: return "invalid length or distance symbol";
-    case INF_E_DIST: return "match distance beyond the output so far";
-    case INF_E_OUT: return "output passes ISIZE";
-    case INF_E_ISIZE: return "stream ends before ISIZE bytes";
-    case INF_E_CRC: return "CRC32 mismatch";
-    case INF_E_DESC: return "member descriptor outside the buffers";
-    }
-    return "unknown error";
-}
 
 static int bam_dev_init(slx_bam *rd, int device)
 {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        slx_set_error("no HIP device: the BAM reader inflates and indexes on MI355X only (no CPU fallback)");
-        return SLX_ENODEVICE;
-    }
-    if (device < 0) { BAM_HIPCHK(hipGetDevice(&device)); }
-    if (device >= ndev) { slx_set_error("BAM reader: device %d is not one of the %d visible", device, ndev); return SLX_EINVAL; }
-    BAM_HIPCHK(hipSetDevice(device));
-    rd->device = device;
-    BAM_HIPCHK(hipStreamCreateWithFlags(&rd->st, hipStreamNonBlocking));
-    for (auto &e : rd->ev) BAM_HIPCHK(hipEventCreate(&e));
+    SLX_CHK(slx_pick_device(device, "no HIP device: the BAM reader inflates and indexes on MI355X only (no CPU fallback)", "BAM reader", &rd->device));
+    SLX_HIPCHK(hipStreamCreateWithFlags(&rd->st, hipStreamNonBlocking));
+    for (auto &e : rd->ev) SLX_HIPCHK(hipEventCreate(&e));
     return SLX_OK;
 }
 
@@ -535,52 +530,17 @@ static void bam_dev_free(slx_bam *rd)
     }
     for (BamDBuf *b : rd->dbufs()) b->release();
     for (BamHBuf *b : rd->hbufs()) b->release();
+    rd->stage.release();
     for (auto &e : rd->ev) if (e) (void)hipEventDestroy(e);
     if (rd->st) (void)hipStreamDestroy(rd->st);
     rd->st = nullptr;
 }
 
-static float ev_us(hipEvent_t a, hipEvent_t b) { float ms = 0; return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms * 1000.f : 0.f; }
-
 // members [a, b) inflated to d_out[dst_off ..), CRC-checked; d_out holds out_bytes.  Returns after the stream has drained.
 static int bam_inflate_span(slx_bam *rd, int64_t a, int64_t b, uint64_t dst_off, uint64_t out_bytes)
 {
-    const int n = (int)(b - a);
-    if (n <= 0) return SLX_OK;
-    uint64_t comp = 0;
-    for (int64_t i = a; i < b; ++i) comp += rd->f.mem[i].data_len;
-    BAM_CHK(rd->h_comp.ensure(comp + 8)); BAM_CHK(rd->d_comp.ensure(comp + 8));
-    BAM_CHK(rd->h_desc.ensure(sizeof(bam_mdesc) * n)); BAM_CHK(rd->d_desc.ensure(sizeof(bam_mdesc) * n));
-    BAM_CHK(rd->h_err.ensure(4 * (size_t)n)); BAM_CHK(rd->d_err.ensure(4 * (size_t)n));
-    bam_mdesc *d = rd->h_desc.as<bam_mdesc>();
-    uint64_t ci = 0, oo = dst_off;
-    for (int64_t i = a; i < b; ++i) {
-        const slx_bam_member &m = rd->f.mem[i];
-        memcpy(rd->h_comp.as<uint8_t>() + ci, rd->f.map + m.file_off + m.data_off, m.data_len);
-        d[i - a] = bam_mdesc{ci, oo, m.data_len, m.isize, m.crc32, 0};
-        ci += m.data_len; oo += m.isize;
-    }
-    if (oo > out_bytes) { slx_set_error("BAM reader: internal: span of %llu bytes does not fit %llu", (unsigned long long)oo, (unsigned long long)out_bytes); return SLX_EINTERNAL; }
-    hipStream_t st = rd->st;
-    BAM_HIPCHK(hipMemcpyAsync(rd->d_comp.p, rd->h_comp.p, comp, hipMemcpyHostToDevice, st));
-    BAM_HIPCHK(hipMemcpyAsync(rd->d_desc.p, rd->h_desc.p, sizeof(bam_mdesc) * n, hipMemcpyHostToDevice, st));
-    BAM_HIPCHK(hipEventRecord(rd->ev[0], st));
-    k_bgzf_inflate<<<(n + 3) / 4, 256, 0, st>>>(rd->d_comp.as<uint8_t>(), comp, rd->d_desc.as<bam_mdesc>(), n, rd->d_out.as<uint8_t>(), out_bytes, rd->d_err.as<uint32_t>());
-    BAM_HIPCHK(hipGetLastError());
-    BAM_HIPCHK(hipEventRecord(rd->ev[1], st));
-    k_bgzf_crc<<<(n + 3) / 4, 256, 0, st>>>(rd->d_desc.as<bam_mdesc>(), n, rd->d_out.as<uint8_t>(), out_bytes, rd->d_err.as<uint32_t>());
-    BAM_HIPCHK(hipGetLastError());
-    BAM_HIPCHK(hipEventRecord(rd->ev[2], st));
-    BAM_HIPCHK(hipMemcpyAsync(rd->h_err.p, rd->d_err.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
-    BAM_HIPCHK(slx_wait_stream(st));
-    rd->us[0] += ev_us(rd->ev[0], rd->ev[1]); rd->us[1] += ev_us(rd->ev[1], rd->ev[2]);
-    rd->c_members_done += n;
-    const uint32_t *err = rd->h_err.as<uint32_t>();
-    for (int i = 0; i < n; ++i)
-        if (err[i]) {
-            slx_set_error("BGZF: '%s': the member at file offset %llu does not inflate: %s", rd->f.path.c_str(), (unsigned long long)rd->f.mem[a + i].file_off, inf_errtext(err[i]));
-            return SLX_EIO;
-        }
+    SLX_CHK(slx_bgzf_inflate_members(rd->f.map, rd->f.path.c_str(), rd->f.mem.data(), a, b, rd->stage, rd->d_out.as<uint8_t>(), dst_off, out_bytes, rd->st, rd->ev[0], rd->ev[1], rd->ev[2], rd->us));
+    if (b > a) rd->c_members_done += b - a;
     return SLX_OK;
 }
 
@@ -591,40 +551,40 @@ static int bam_index(slx_bam *rd, uint64_t start, uint64_t n, int32_t n_ref, uin
     const uint64_t chunk = rd->chunk_bytes, K = (n + chunk - 1) / chunk;
     *n_rec = 0; *end = 0; *repaired = 0;
     if (!K) return SLX_OK;
-    for (BamDBuf *b : {&rd->d_guess, &rd->d_used, &rd->d_exit_a, &rd->d_exit_b, &rd->d_base}) BAM_CHK(b->ensure(8 * K));
-    BAM_CHK(rd->d_count.ensure(4 * K)); BAM_CHK(rd->d_state.ensure(64)); BAM_CHK(rd->h_state.ensure(64));
+    for (BamDBuf *b : {&rd->d_guess, &rd->d_used, &rd->d_exit_a, &rd->d_exit_b, &rd->d_base}) SLX_CHK(b->ensure(8 * K));
+    SLX_CHK(rd->d_count.ensure(4 * K)); SLX_CHK(rd->d_state.ensure(64)); SLX_CHK(rd->h_state.ensure(64));
     unsigned long long *hs = rd->h_state.as<unsigned long long>(), *ds = rd->d_state.as<unsigned long long>();
     hs[0] = 0; hs[1] = 0; hs[2] = ~0ull; hs[3] = 0; hs[4] = 0;
-    BAM_HIPCHK(hipMemcpyAsync(ds, hs, 40, hipMemcpyHostToDevice, st));
-    BAM_HIPCHK(hipEventRecord(rd->ev[3], st));
+    SLX_HIPCHK(hipMemcpyAsync(ds, hs, 40, hipMemcpyHostToDevice, st));
+    SLX_HIPCHK(hipEventRecord(rd->ev[3], st));
     const uint8_t *s = rd->d_out.as<uint8_t>() + start;
     const unsigned grid = (unsigned)((K + 63) / 64);
     uint64_t *ex_a = rd->d_exit_a.as<uint64_t>(), *ex_b = rd->d_exit_b.as<uint64_t>();
     k_bam_guess<<<grid, 64, 0, st>>>(s, n, chunk, K, n_ref, rd->idx_fail, rd->d_guess.as<uint64_t>(), rd->d_used.as<uint64_t>(), ex_a, rd->d_count.as<uint32_t>());
-    BAM_HIPCHK(hipGetLastError());
+    SLX_HIPCHK(hipGetLastError());
     for (uint64_t round = 0; K > 1; ++round) {
         if (round > K) { slx_set_error("BAM reader: internal: the record index did not settle in %llu rounds", (unsigned long long)K); return SLX_EINTERNAL; }
-        if (round) BAM_HIPCHK(hipMemsetAsync(ds + 4, 0, 8, st));
+        if (round) SLX_HIPCHK(hipMemsetAsync(ds + 4, 0, 8, st));
         k_bam_round<<<grid, 64, 0, st>>>(s, n, chunk, K, rd->d_used.as<uint64_t>(), ex_a, ex_b, rd->d_count.as<uint32_t>(), ds);
-        BAM_HIPCHK(hipGetLastError());
-        BAM_HIPCHK(hipMemcpyAsync(hs + 4, ds + 4, 8, hipMemcpyDeviceToHost, st));
-        BAM_HIPCHK(slx_wait_stream(st));
+        SLX_HIPCHK(hipGetLastError());
+        SLX_HIPCHK(hipMemcpyAsync(hs + 4, ds + 4, 8, hipMemcpyDeviceToHost, st));
+        SLX_HIPCHK(slx_wait_stream(st));
         std::swap(ex_a, ex_b);
         ++rd->c_rounds;
         if (!hs[4]) break;
     }
     k_bam_scan<<<1, 1024, 0, st>>>(rd->d_count.as<uint32_t>(), rd->d_base.as<uint64_t>(), K, ds);
-    BAM_HIPCHK(hipGetLastError());
-    BAM_HIPCHK(hipMemcpyAsync(hs, ds, 8, hipMemcpyDeviceToHost, st));
-    BAM_HIPCHK(slx_wait_stream(st));
+    SLX_HIPCHK(hipGetLastError());
+    SLX_HIPCHK(hipMemcpyAsync(hs, ds, 8, hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(slx_wait_stream(st));
     const uint64_t nr = hs[0];
-    BAM_CHK(rd->d_rec.ensure(8 * (nr + 1)));
+    SLX_CHK(rd->d_rec.ensure(8 * (nr + 1)));
     k_bam_fill<<<grid, 64, 0, st>>>(s, n, chunk, K, ex_a, rd->d_guess.as<uint64_t>(), rd->d_base.as<uint64_t>(), rd->d_rec.as<uint64_t>(), ds);
-    BAM_HIPCHK(hipGetLastError());
-    BAM_HIPCHK(hipEventRecord(rd->ev[4], st));
-    BAM_HIPCHK(hipMemcpyAsync(hs, ds, 32, hipMemcpyDeviceToHost, st));
-    BAM_HIPCHK(slx_wait_stream(st));
-    rd->us[2] += ev_us(rd->ev[3], rd->ev[4]);
+    SLX_HIPCHK(hipGetLastError());
+    SLX_HIPCHK(hipEventRecord(rd->ev[4], st));
+    SLX_HIPCHK(hipMemcpyAsync(hs, ds, 32, hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(slx_wait_stream(st));
+    rd->us[2] += slx_ev_us(rd->ev[3], rd->ev[4]);
     if (hs[2] != ~0ull) { slx_set_error("BAM: '%s': a record's block_size is below its 32 fixed bytes (inflated offset %llu of the batch)", rd->f.path.c_str(), hs[2]); return SLX_EIO; }
     *n_rec = nr; *end = hs[3]; *repaired = hs[1];
     return SLX_OK;
@@ -642,30 +602,30 @@ static int bam_parse_header(slx_bam *rd)
             if (b >= nm) { slx_set_error("BAM: '%s': the file ends inside the BAM header", rd->f.path.c_str()); return SLX_EIO; }
             int64_t e = b; uint64_t bytes = 0;
             while (e < nm && (e == b || bytes < upto - h.size())) bytes += rd->f.mem[e++].isize;
-            BAM_CHK(rd->d_out.ensure(bytes + 8));
-            BAM_CHK(bam_inflate_span(rd, b, e, 0, bytes));
+            SLX_CHK(rd->d_out.ensure(bytes + 8));
+            SLX_CHK(bam_inflate_span(rd, b, e, 0, bytes));
             const size_t at = h.size();
             h.resize(at + bytes);
-            if (bytes) { BAM_HIPCHK(hipMemcpyAsync(h.data() + at, rd->d_out.p, bytes, hipMemcpyDeviceToHost, rd->st)); BAM_HIPCHK(hipStreamSynchronize(rd->st)); }
+            if (bytes) { SLX_HIPCHK(hipMemcpyAsync(h.data() + at, rd->d_out.p, bytes, hipMemcpyDeviceToHost, rd->st)); SLX_HIPCHK(hipStreamSynchronize(rd->st)); }
             b = e;
         }
         return SLX_OK;
     };
-    BAM_CHK(need(12));
+    SLX_CHK(need(12));
     if (memcmp(h.data(), "BAM\1", 4) != 0) { slx_set_error("BAM: '%s' is BGZF but does not hold a BAM stream (bad magic; SAM text and CRAM are not read)", rd->f.path.c_str()); return SLX_EIO; }
     const uint64_t l_text = bidx_u32(h.data() + 4);
     if (l_text > (1ull << 31)) { slx_set_error("BAM: '%s': header text length %llu", rd->f.path.c_str(), (unsigned long long)l_text); return SLX_EIO; }
-    BAM_CHK(need(12 + l_text));
+    SLX_CHK(need(12 + l_text));
     rd->text.assign((const char *)h.data() + 8, l_text);
     while (!rd->text.empty() && rd->text.back() == '\0') rd->text.pop_back();
     const int32_t n_ref = (int32_t)bidx_u32(h.data() + 8 + l_text);
     if (n_ref < 0) { slx_set_error("BAM: '%s': negative reference count", rd->f.path.c_str()); return SLX_EIO; }
     uint64_t p = 12 + l_text;
     for (int32_t i = 0; i < n_ref; ++i) {
-        BAM_CHK(need(p + 4));
+        SLX_CHK(need(p + 4));
         const uint64_t l_name = bidx_u32(h.data() + p);
         if (l_name < 1 || l_name > (1u << 20)) { slx_set_error("BAM: '%s': reference %d has name length %llu", rd->f.path.c_str(), i, (unsigned long long)l_name); return SLX_EIO; }
-        BAM_CHK(need(p + 4 + l_name + 4));
+        SLX_CHK(need(p + 4 + l_name + 4));
         rd->ref_names.emplace_back((const char *)h.data() + p + 4, strnlen((const char *)h.data() + p + 4, l_name));
         rd->ref_lens.push_back((int64_t)bidx_u32(h.data() + p + 4 + l_name));
         p += 8 + l_name;
@@ -688,7 +648,7 @@ static std::string bai_beside(const std::string &path)
 static int bam_load_index(slx_bam *rd, const std::string &bai_path)
 {
     Bai b;
-    BAM_CHK(bai_load_file(bai_path.c_str(), b));
+    SLX_CHK(bai_load_file(bai_path.c_str(), b));
     if (b.refs.size() != rd->ref_names.size()) {
         slx_set_error("BAI: '%s' indexes %zu references, the header of '%s' has %zu: not this file's index", bai_path.c_str(), b.refs.size(), rd->f.path.c_str(), rd->ref_names.size());
         return SLX_EINVAL;
@@ -796,7 +756,7 @@ extern "C" int64_t slx_bam_ref_len(const slx_bam *rd, int i) { return rd && i >=
 extern "C" int slx_bam_rewind(slx_bam *rd)
 {
     if (!rd) { slx_set_error("slx_bam_rewind: reader is null"); return SLX_EINVAL; }
-    if (rd->sam) BAM_CHK(slx_samsrc_rewind(rd->sam));
+    if (rd->sam) SLX_CHK(slx_samsrc_rewind(rd->sam));
     bam_whole_file(rd);                  // the regions go too: the reference's Reset reopens the file (src/BamReader.cpp:56-62)
     return SLX_OK;
 }
@@ -846,9 +806,9 @@ static int bam_span(slx_bam *rd, int64_t max_bytes, int64_t a, int64_t lim, uint
     hipStream_t st = rd->st;
     if (max_bytes < 1) max_bytes = 1;
     uint64_t total = rd->carry.size();
-    BAM_CHK(rd->d_out.ensure(total + 8));
-    if (total) BAM_HIPCHK(hipMemcpyAsync(rd->d_out.p, rd->carry.data(), total, hipMemcpyHostToDevice, st));
-    BAM_HIPCHK(hipStreamSynchronize(st));
+    SLX_CHK(rd->d_out.ensure(total + 8));
+    if (total) SLX_HIPCHK(hipMemcpyAsync(rd->d_out.p, rd->carry.data(), total, hipMemcpyHostToDevice, st));
+    SLX_HIPCHK(hipStreamSynchronize(st));
     int64_t done = a, b = a;
     *n_rec = 0; *end = 0; *repaired = 0;
     for (;;) {
@@ -857,13 +817,13 @@ static int bam_span(slx_bam *rd, int64_t max_bytes, int64_t a, int64_t lim, uint
         if (b == done) { while (b < lim && (b == done || bytes + rd->f.mem[b].isize <= (uint64_t)max_bytes)) bytes += rd->f.mem[b++].isize; }
         uint64_t span = 0;
         for (int64_t i = done; i < b; ++i) span += rd->f.mem[i].isize;
-        BAM_CHK(rd->d_out.ensure(total + span + 8, st, total));
-        BAM_CHK(bam_inflate_span(rd, done, b, total, total + span));
+        SLX_CHK(rd->d_out.ensure(total + span + 8, st, total));
+        SLX_CHK(bam_inflate_span(rd, done, b, total, total + span));
         total += span; done = b;
         const uint64_t cut = done >= lim ? tail_cut : 0;
         if (total < start + cut) { slx_set_error("BAM: '%s': the index does not fit the file (a chunk of %llu bytes begins at %llu and leaves out %llu)", rd->f.path.c_str(), (unsigned long long)total, (unsigned long long)start, (unsigned long long)cut); return SLX_EIO; }
         *n_out = total - cut;
-        BAM_CHK(bam_index(rd, start, *n_out - start, (int32_t)rd->ref_names.size(), n_rec, end, repaired));
+        SLX_CHK(bam_index(rd, start, *n_out - start, (int32_t)rd->ref_names.size(), n_rec, end, repaired));
         if (*n_rec || done >= lim) break;
         b = std::min(lim, done + std::max<int64_t>(1, done - a));
     }
@@ -875,7 +835,7 @@ static int bam_span(slx_bam *rd, int64_t max_bytes, int64_t a, int64_t lim, uint
 static int bam_take_carry(slx_bam *rd, uint64_t from, uint64_t upto)
 {
     rd->carry.resize(upto - from);
-    if (upto > from) BAM_HIPCHK(hipMemcpyAsync(rd->carry.data(), rd->d_out.as<uint8_t>() + from, upto - from, hipMemcpyDeviceToHost, rd->st));
+    if (upto > from) SLX_HIPCHK(hipMemcpyAsync(rd->carry.data(), rd->d_out.as<uint8_t>() + from, upto - from, hipMemcpyDeviceToHost, rd->st));
     return SLX_OK;
 }
 
@@ -885,7 +845,7 @@ static int bam_next_regions(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
     typedef unsigned long long ull;
     hipStream_t st = rd->st;
     if (max_bytes < 1) max_bytes = 1;
-    BAM_CHK(rd->d_state.ensure(64)); BAM_CHK(rd->h_state.ensure(64));
+    SLX_CHK(rd->d_state.ensure(64)); SLX_CHK(rd->h_state.ensure(64));
     ull *hs = rd->h_state.as<ull>(), *ds = rd->d_state.as<ull>();
     uint64_t kept = 0, bytes = 0, used = 0, repaired = 0;
     int64_t members = 0;
@@ -899,57 +859,54 @@ static int bam_next_regions(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
         const uint64_t start = a == P.ma ? P.start : 0;
         int64_t done = a;
         uint64_t n = 0, n_rec = 0, end = 0, rep = 0;
-        BAM_CHK(bam_span(rd, room, a, P.mb, start, P.tail_cut, &done, &n, &n_rec, &end, &rep));
+        SLX_CHK(bam_span(rd, room, a, P.mb, start, P.tail_cut, &done, &n, &n_rec, &end, &rep));
         for (int64_t i = a; i < done; ++i) used += rd->f.mem[i].isize;
         members += done - a; repaired += rep;
         if (done >= P.mb) {
             if (start + end != n) { slx_set_error("BAM: '%s': the index does not fit the file (the chunk that ends in the member at %llu ends inside a record)", rd->f.path.c_str(), (unsigned long long)rd->f.mem[P.mb - 1].file_off); return SLX_EIO; }
             rd->carry.clear();
-        } else BAM_CHK(bam_take_carry(rd, start + end, n));
+        } else SLX_CHK(bam_take_carry(rd, start + end, n));
         if (n_rec) {
             const slx_bam_region &g = rd->regions[P.region];
-            for (BamDBuf *b : {&rd->d_keep, &rd->d_blen, &rd->d_kidx, &rd->d_boff}) BAM_CHK(b->ensure(8 * (n_rec + 1)));
-            BAM_HIPCHK(hipMemsetAsync(ds + 5, 0, 8, st));
-            BAM_HIPCHK(hipEventRecord(rd->ev[7], st));
+            for (BamDBuf *b : {&rd->d_keep, &rd->d_blen, &rd->d_kidx, &rd->d_boff}) SLX_CHK(b->ensure(8 * (n_rec + 1)));
+            SLX_HIPCHK(hipMemsetAsync(ds + 5, 0, 8, st));
+            SLX_HIPCHK(hipEventRecord(rd->ev[7], st));
             const uint8_t *s = rd->d_out.as<uint8_t>() + start;
             const uint64_t *rec = rd->d_rec.as<uint64_t>();
             k_bam_region_keep<<<(unsigned)((n_rec + 1 + 255) / 256), 256, 0, st>>>(s, rec, n_rec, g.tid, g.beg, g.end, rd->d_keep.as<ull>(), rd->d_blen.as<ull>(), ds + 5);
-            BAM_HIPCHK(hipGetLastError());
+            SLX_HIPCHK(hipGetLastError());
             if (rd->flt) {                                 // keep = region test AND filter
-                BAM_CHK(rd->d_fkeep.ensure(n_rec + 8));
-                BAM_CHK(slx_filter_eval_device(rd->flt, rd->device, st, s, rec, n_rec, end, rd->d_fkeep.as<uint8_t>(), nullptr));
+                SLX_CHK(rd->d_fkeep.ensure(n_rec + 8));
+                SLX_CHK(slx_filter_eval_device(rd->flt, rd->device, st, s, rec, n_rec, end, rd->d_fkeep.as<uint8_t>(), nullptr));
                 k_bam_keep_bytes<<<(unsigned)((n_rec + 1 + 255) / 256), 256, 0, st>>>(rd->d_fkeep.as<uint8_t>(), rec, n_rec, 1, rd->d_keep.as<ull>(), rd->d_blen.as<ull>());
-                BAM_HIPCHK(hipGetLastError());
+                SLX_HIPCHK(hipGetLastError());
             }
-            size_t tb = 0;
-            BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, rd->d_keep.as<ull>(), rd->d_kidx.as<ull>(), (int)(n_rec + 1), st));
-            BAM_CHK(rd->d_tmp.ensure(tb + 8));
-            BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(rd->d_tmp.p, tb, rd->d_keep.as<ull>(), rd->d_kidx.as<ull>(), (int)(n_rec + 1), st));
-            BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(rd->d_tmp.p, tb, rd->d_blen.as<ull>(), rd->d_boff.as<ull>(), (int)(n_rec + 1), st));
-            BAM_HIPCHK(hipMemcpyAsync(hs + 5, rd->d_kidx.as<ull>() + n_rec, 8, hipMemcpyDeviceToHost, st));
-            BAM_HIPCHK(hipMemcpyAsync(hs + 6, rd->d_boff.as<ull>() + n_rec, 8, hipMemcpyDeviceToHost, st));
-            BAM_HIPCHK(hipMemcpyAsync(hs + 7, ds + 5, 8, hipMemcpyDeviceToHost, st));
-            BAM_HIPCHK(slx_wait_stream(st));
+            SLX_CHK(slx_exclusive_sum(rd->d_tmp, rd->d_keep.as<ull>(), rd->d_kidx.as<ull>(), n_rec + 1, st, 8));
+            SLX_CHK(slx_exclusive_sum(rd->d_tmp, rd->d_blen.as<ull>(), rd->d_boff.as<ull>(), n_rec + 1, st, 8));
+            SLX_HIPCHK(hipMemcpyAsync(hs + 5, rd->d_kidx.as<ull>() + n_rec, 8, hipMemcpyDeviceToHost, st));
+            SLX_HIPCHK(hipMemcpyAsync(hs + 6, rd->d_boff.as<ull>() + n_rec, 8, hipMemcpyDeviceToHost, st));
+            SLX_HIPCHK(hipMemcpyAsync(hs + 7, ds + 5, 8, hipMemcpyDeviceToHost, st));
+            SLX_HIPCHK(slx_wait_stream(st));
             if (hs[7]) { slx_set_error("BAM: '%s': a record's name and CIGAR pass its block_size", rd->f.path.c_str()); return SLX_EIO; }
             const uint64_t kn = hs[5], kb = hs[6];
-            BAM_CHK(rd->d_cs.ensure(bytes + kb + 8, st, bytes)); BAM_CHK(rd->d_cr.ensure(8 * (kept + kn + 1), st, 8 * kept));
+            SLX_CHK(rd->d_cs.ensure(bytes + kb + 8, st, bytes)); SLX_CHK(rd->d_cr.ensure(8 * (kept + kn + 1), st, 8 * kept));
             k_bam_gather<<<(unsigned)((n_rec + 3) / 4), 256, 0, st>>>(s, rec, n_rec, rd->d_kidx.as<ull>(), rd->d_boff.as<ull>(), rd->d_cs.as<uint8_t>(), rd->d_cr.as<uint64_t>(), kept, bytes);
-            BAM_HIPCHK(hipGetLastError());
-            BAM_HIPCHK(hipEventRecord(rd->ev[8], st));
-            BAM_HIPCHK(slx_wait_stream(st));
-            rd->us[4] += ev_us(rd->ev[7], rd->ev[8]);
+            SLX_HIPCHK(hipGetLastError());
+            SLX_HIPCHK(hipEventRecord(rd->ev[8], st));
+            SLX_HIPCHK(slx_wait_stream(st));
+            rd->us[4] += slx_ev_us(rd->ev[7], rd->ev[8]);
             kept += kn; bytes += kb;
             rd->c_region_cand += (int64_t)n_rec; rd->c_region_kept += (int64_t)kn;
-        } else BAM_HIPCHK(slx_wait_stream(st));
+        } else SLX_HIPCHK(slx_wait_stream(st));
         if (done >= P.mb) { ++rd->piece_i; rd->piece_cur = -1; }
         else { rd->piece_cur = done; if (kept) break; used = 0; }
     }
     rd->c_repaired += (int64_t)repaired; rd->c_records += (int64_t)kept;
     if (kept) {
-        BAM_CHK(rd->h_out.ensure(bytes + 8)); BAM_CHK(rd->h_rec.ensure(8 * (kept + 1)));
-        BAM_HIPCHK(hipMemcpyAsync(rd->h_out.p, rd->d_cs.p, bytes, hipMemcpyDeviceToHost, st));
-        BAM_HIPCHK(hipMemcpyAsync(rd->h_rec.p, rd->d_cr.p, 8 * (kept + 1), hipMemcpyDeviceToHost, st));
-        BAM_HIPCHK(slx_wait_stream(st));
+        SLX_CHK(rd->h_out.ensure(bytes + 8)); SLX_CHK(rd->h_rec.ensure(8 * (kept + 1)));
+        SLX_HIPCHK(hipMemcpyAsync(rd->h_out.p, rd->d_cs.p, bytes, hipMemcpyDeviceToHost, st));
+        SLX_HIPCHK(hipMemcpyAsync(rd->h_rec.p, rd->d_cr.p, 8 * (kept + 1), hipMemcpyDeviceToHost, st));
+        SLX_HIPCHK(slx_wait_stream(st));
     }
     out->n_records = (int64_t)kept; out->n_bytes = (int64_t)bytes;
     out->stream = rd->h_out.as<uint8_t>(); out->rec_off = rd->h_rec.as<uint64_t>();
@@ -965,28 +922,25 @@ static int bam_filter_compact(slx_bam *rd, const uint8_t *s, const uint64_t *rec
 {
     typedef unsigned long long ull;
     hipStream_t st = rd->st;
-    BAM_CHK(rd->h_state.ensure(64));
+    SLX_CHK(rd->h_state.ensure(64));
     ull *hs = rd->h_state.as<ull>();
     uint64_t kn = 0, kb = 0;
     *kn_out = *kb_out = 0;
-    for (BamDBuf *b : {&rd->d_keep, &rd->d_blen, &rd->d_kidx, &rd->d_boff}) BAM_CHK(b->ensure(8 * (n_rec + 1)));
-    BAM_CHK(rd->d_fkeep.ensure(n_rec + 8));
-    BAM_CHK(slx_filter_eval_device(rd->flt, rd->device, st, s, rec, n_rec, end, rd->d_fkeep.as<uint8_t>(), nullptr));
+    for (BamDBuf *b : {&rd->d_keep, &rd->d_blen, &rd->d_kidx, &rd->d_boff}) SLX_CHK(b->ensure(8 * (n_rec + 1)));
+    SLX_CHK(rd->d_fkeep.ensure(n_rec + 8));
+    SLX_CHK(slx_filter_eval_device(rd->flt, rd->device, st, s, rec, n_rec, end, rd->d_fkeep.as<uint8_t>(), nullptr));
     k_bam_keep_bytes<<<(unsigned)((n_rec + 1 + 255) / 256), 256, 0, st>>>(rd->d_fkeep.as<uint8_t>(), rec, n_rec, 0, rd->d_keep.as<ull>(), rd->d_blen.as<ull>());
-    BAM_HIPCHK(hipGetLastError());
-    size_t tb = 0;
-    BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, rd->d_keep.as<ull>(), rd->d_kidx.as<ull>(), (int)(n_rec + 1), st));
-    BAM_CHK(rd->d_tmp.ensure(tb + 8));
-    BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(rd->d_tmp.p, tb, rd->d_keep.as<ull>(), rd->d_kidx.as<ull>(), (int)(n_rec + 1), st));
-    BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(rd->d_tmp.p, tb, rd->d_blen.as<ull>(), rd->d_boff.as<ull>(), (int)(n_rec + 1), st));
-    BAM_HIPCHK(hipMemcpyAsync(hs + 5, rd->d_kidx.as<ull>() + n_rec, 8, hipMemcpyDeviceToHost, st));
-    BAM_HIPCHK(hipMemcpyAsync(hs + 6, rd->d_boff.as<ull>() + n_rec, 8, hipMemcpyDeviceToHost, st));
-    BAM_HIPCHK(slx_wait_stream(st));
+    SLX_HIPCHK(hipGetLastError());
+    SLX_CHK(slx_exclusive_sum(rd->d_tmp, rd->d_keep.as<ull>(), rd->d_kidx.as<ull>(), n_rec + 1, st, 8));
+    SLX_CHK(slx_exclusive_sum(rd->d_tmp, rd->d_blen.as<ull>(), rd->d_boff.as<ull>(), n_rec + 1, st, 8));
+    SLX_HIPCHK(hipMemcpyAsync(hs + 5, rd->d_kidx.as<ull>() + n_rec, 8, hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(hipMemcpyAsync(hs + 6, rd->d_boff.as<ull>() + n_rec, 8, hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(slx_wait_stream(st));
     kn = hs[5]; kb = hs[6];
     if (kn) {
-        BAM_CHK(rd->d_cs.ensure(kb + 8)); BAM_CHK(rd->d_cr.ensure(8 * (kn + 1)));
+        SLX_CHK(rd->d_cs.ensure(kb + 8)); SLX_CHK(rd->d_cr.ensure(8 * (kn + 1)));
         k_bam_gather<<<(unsigned)((n_rec + 3) / 4), 256, 0, st>>>(s, rec, n_rec, rd->d_kidx.as<ull>(), rd->d_boff.as<ull>(), rd->d_cs.as<uint8_t>(), rd->d_cr.as<uint64_t>(), 0, 0);
-        BAM_HIPCHK(hipGetLastError());
+        SLX_HIPCHK(hipGetLastError());
     }
     *kn_out = kn; *kb_out = kb;
     return SLX_OK;
@@ -1005,18 +959,18 @@ static int bam_next_filtered(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
         if (a >= nm && rd->carry.empty()) break;
         int64_t done = a;
         uint64_t total = 0, n_rec = 0, end = 0, rep = 0;
-        BAM_CHK(bam_span(rd, max_bytes, a, nm, 0, 0, &done, &total, &n_rec, &end, &rep));
+        SLX_CHK(bam_span(rd, max_bytes, a, nm, 0, 0, &done, &total, &n_rec, &end, &rep));
         if (!n_rec && total) { slx_set_error("BAM: '%s' ends inside a record (%llu bytes after the last whole record)", rd->f.path.c_str(), (unsigned long long)total); return SLX_EIO; }
         rd->next_member = done; members += done - a; repaired += rep;
-        BAM_CHK(bam_take_carry(rd, end, total));
-        BAM_HIPCHK(slx_wait_stream(st));
+        SLX_CHK(bam_take_carry(rd, end, total));
+        SLX_HIPCHK(slx_wait_stream(st));
         if (!n_rec) break;
-        BAM_CHK(bam_filter_compact(rd, rd->d_out.as<uint8_t>(), rd->d_rec.as<uint64_t>(), n_rec, end, &kn, &kb));
+        SLX_CHK(bam_filter_compact(rd, rd->d_out.as<uint8_t>(), rd->d_rec.as<uint64_t>(), n_rec, end, &kn, &kb));
         if (!kn) continue;
-        BAM_CHK(rd->h_out.ensure(kb + 8)); BAM_CHK(rd->h_rec.ensure(8 * (kn + 1)));
-        BAM_HIPCHK(hipMemcpyAsync(rd->h_out.p, rd->d_cs.p, kb, hipMemcpyDeviceToHost, st));
-        BAM_HIPCHK(hipMemcpyAsync(rd->h_rec.p, rd->d_cr.p, 8 * (kn + 1), hipMemcpyDeviceToHost, st));
-        BAM_HIPCHK(slx_wait_stream(st));
+        SLX_CHK(rd->h_out.ensure(kb + 8)); SLX_CHK(rd->h_rec.ensure(8 * (kn + 1)));
+        SLX_HIPCHK(hipMemcpyAsync(rd->h_out.p, rd->d_cs.p, kb, hipMemcpyDeviceToHost, st));
+        SLX_HIPCHK(hipMemcpyAsync(rd->h_rec.p, rd->d_cr.p, 8 * (kn + 1), hipMemcpyDeviceToHost, st));
+        SLX_HIPCHK(slx_wait_stream(st));
     }
     rd->c_repaired += (int64_t)repaired; rd->c_records += (int64_t)kn;
     out->n_records = (int64_t)kn; out->n_bytes = (int64_t)kb;
@@ -1037,17 +991,17 @@ static int bam_next_sam(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
     for (;;) {
         uint64_t n_rec = 0, end = 0;
         int64_t nm = 0;
-        BAM_CHK(slx_samsrc_next(rd->sam, max_bytes, &ds, &dr, &n_rec, &end, &nm));
+        SLX_CHK(slx_samsrc_next(rd->sam, max_bytes, &ds, &dr, &n_rec, &end, &nm));
         members += nm;
         if (!n_rec) return SLX_OK;
         if (!rd->flt) { kn = n_rec; kb = end; break; }
-        BAM_CHK(bam_filter_compact(rd, (const uint8_t *)ds, (const uint64_t *)dr, n_rec, end, &kn, &kb));
+        SLX_CHK(bam_filter_compact(rd, (const uint8_t *)ds, (const uint64_t *)dr, n_rec, end, &kn, &kb));
         if (kn) { ds = rd->d_cs.p; dr = rd->d_cr.p; break; }
     }
-    BAM_CHK(rd->h_out.ensure(kb + 8)); BAM_CHK(rd->h_rec.ensure(8 * (kn + 1)));
-    BAM_HIPCHK(hipMemcpyAsync(rd->h_out.p, ds, kb, hipMemcpyDeviceToHost, st));
-    BAM_HIPCHK(hipMemcpyAsync(rd->h_rec.p, dr, 8 * (kn + 1), hipMemcpyDeviceToHost, st));
-    BAM_HIPCHK(slx_wait_stream(st));
+    SLX_CHK(rd->h_out.ensure(kb + 8)); SLX_CHK(rd->h_rec.ensure(8 * (kn + 1)));
+    SLX_HIPCHK(hipMemcpyAsync(rd->h_out.p, ds, kb, hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(hipMemcpyAsync(rd->h_rec.p, dr, 8 * (kn + 1), hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(slx_wait_stream(st));
     rd->c_records += (int64_t)kn;
     out->n_records = (int64_t)kn; out->n_bytes = (int64_t)kb;
     out->stream = rd->h_out.as<uint8_t>(); out->rec_off = rd->h_rec.as<uint64_t>();
@@ -1062,7 +1016,7 @@ extern "C" int slx_sam_open(const char *path, int device, slx_bam **out)
     if (!path || !out) { slx_set_error("slx_sam_open: null argument"); return SLX_EINVAL; }
     *out = nullptr;
     slx_samsrc *src = nullptr;
-    BAM_CHK(slx_samsrc_open(path, device, &src));
+    SLX_CHK(slx_samsrc_open(path, device, &src));
     slx_bam *rd = new slx_bam();
     rd->f.path = path; rd->f.has_eof = 1;
     const int rc = bam_dev_init(rd, slx_samsrc_device(src));
@@ -1079,7 +1033,7 @@ extern "C" int slx_bam_next(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
 {
     if (!rd || !out) { slx_set_error("slx_bam_next: null argument"); return SLX_EINVAL; }
     memset(out, 0, sizeof *out);
-    BAM_HIPCHK(hipSetDevice(rd->device));
+    SLX_HIPCHK(hipSetDevice(rd->device));
     rd->us[0] = rd->us[1] = rd->us[2] = rd->us[4] = 0;
     if (rd->sam) return bam_next_sam(rd, max_bytes, out);
     if (rd->region_mode) return bam_next_regions(rd, max_bytes, out);
@@ -1090,17 +1044,17 @@ extern "C" int slx_bam_next(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
     hipStream_t st = rd->st;
     int64_t done = a;
     uint64_t total = 0, n_rec = 0, end = 0, repaired = 0;
-    BAM_CHK(bam_span(rd, max_bytes, a, nm, 0, 0, &done, &total, &n_rec, &end, &repaired));
+    SLX_CHK(bam_span(rd, max_bytes, a, nm, 0, 0, &done, &total, &n_rec, &end, &repaired));
     if (!n_rec && total) {
         slx_set_error("BAM: '%s' ends inside a record (%llu bytes after the last whole record)", rd->f.path.c_str(), (unsigned long long)total);
         return SLX_EIO;
     }
     rd->next_member = done;
-    BAM_CHK(rd->h_out.ensure(end + 8)); BAM_CHK(rd->h_rec.ensure(8 * (n_rec + 1)));
-    if (end) BAM_HIPCHK(hipMemcpyAsync(rd->h_out.p, rd->d_out.p, end, hipMemcpyDeviceToHost, st));
-    if (n_rec) BAM_HIPCHK(hipMemcpyAsync(rd->h_rec.p, rd->d_rec.p, 8 * (n_rec + 1), hipMemcpyDeviceToHost, st));
-    BAM_CHK(bam_take_carry(rd, end, total));
-    BAM_HIPCHK(slx_wait_stream(st));
+    SLX_CHK(rd->h_out.ensure(end + 8)); SLX_CHK(rd->h_rec.ensure(8 * (n_rec + 1)));
+    if (end) SLX_HIPCHK(hipMemcpyAsync(rd->h_out.p, rd->d_out.p, end, hipMemcpyDeviceToHost, st));
+    if (n_rec) SLX_HIPCHK(hipMemcpyAsync(rd->h_rec.p, rd->d_rec.p, 8 * (n_rec + 1), hipMemcpyDeviceToHost, st));
+    SLX_CHK(bam_take_carry(rd, end, total));
+    SLX_HIPCHK(slx_wait_stream(st));
     rd->c_repaired += (int64_t)repaired; rd->c_records += (int64_t)n_rec;
     out->n_records = (int64_t)n_rec; out->n_bytes = (int64_t)end;
     out->stream = rd->h_out.as<uint8_t>(); out->rec_off = rd->h_rec.as<uint64_t>();
@@ -1138,30 +1092,30 @@ static int bai_build_body(slx_bam *rd, int64_t batch_bytes, BaiBuild &B, std::st
     for (int32_t t = 0; t < n_ref; ++t) lin_off[t + 1] = lin_off[t] + ((uint64_t)std::max<int64_t>(rd->ref_lens[t], 0) >> 14) + 2;
     const uint64_t nn = ne_start.size(), n_win = lin_off[n_ref], R = (uint64_t)std::max(n_ref, 1);
     auto up = [&](BamDBuf &b, const void *src, size_t bytes) -> int {
-        BAM_CHK(b.ensure(bytes + 8));
-        if (bytes) BAM_HIPCHK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st));
+        SLX_CHK(b.ensure(bytes + 8));
+        if (bytes) SLX_HIPCHK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st));
         return SLX_OK;
     };
     auto fill = [&](BamDBuf &b, int byte, size_t bytes) -> int {
-        BAM_CHK(b.ensure(bytes + 8));
-        BAM_HIPCHK(hipMemsetAsync(b.p, byte, bytes + 8, st));
+        SLX_CHK(b.ensure(bytes + 8));
+        SLX_HIPCHK(hipMemsetAsync(b.p, byte, bytes + 8, st));
         return SLX_OK;
     };
     auto down = [&](void *dst, const void *src, size_t bytes) -> int {
-        if (bytes) BAM_HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
+        if (bytes) SLX_HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
         return SLX_OK;
     };
-    BAM_CHK(up(B.ne_start, ne_start.data(), 8 * nn)); BAM_CHK(up(B.ne_file, ne_file.data(), 8 * nn)); BAM_CHK(up(B.lin_off, lin_off.data(), 8 * (size_t)(n_ref + 1)));
-    BAM_CHK(fill(B.lin, 0xff, 8 * n_win)); BAM_CHK(fill(B.first, 0xff, 8 * R)); BAM_CHK(fill(B.last, 0, 8 * R)); BAM_CHK(fill(B.n_map, 0, 8 * R)); BAM_CHK(fill(B.n_unmap, 0, 8 * R));
-    BAM_CHK(fill(B.n_intv, 0, 4 * R));
+    SLX_CHK(up(B.ne_start, ne_start.data(), 8 * nn)); SLX_CHK(up(B.ne_file, ne_file.data(), 8 * nn)); SLX_CHK(up(B.lin_off, lin_off.data(), 8 * (size_t)(n_ref + 1)));
+    SLX_CHK(fill(B.lin, 0xff, 8 * n_win)); SLX_CHK(fill(B.first, 0xff, 8 * R)); SLX_CHK(fill(B.last, 0, 8 * R)); SLX_CHK(fill(B.n_map, 0, 8 * R)); SLX_CHK(fill(B.n_unmap, 0, 8 * R));
+    SLX_CHK(fill(B.n_intv, 0, 4 * R));
     const ull bst0[3] = {0, ~0ull, 0}, carry0[4] = {BAI_NOKEY, 0, BAI_NOKEY, 0};
-    BAM_CHK(up(B.bst, bst0, sizeof bst0)); BAM_CHK(up(B.carry, carry0, sizeof carry0));
-    BAM_HIPCHK(hipStreamSynchronize(st));                  // (the uploads read this frame's memory)
+    SLX_CHK(up(B.bst, bst0, sizeof bst0)); SLX_CHK(up(B.carry, carry0, sizeof carry0));
+    SLX_HIPCHK(hipStreamSynchronize(st));                  // (the uploads read this frame's memory)
     bai_dev d;
     d.ne_start = B.ne_start.as<uint64_t>(); d.ne_file = B.ne_file.as<uint64_t>(); d.nn = nn; d.total = start_all[nm]; d.behind = behind;
     d.lin_off = B.lin_off.as<uint64_t>(); d.lin = B.lin.as<ull>(); d.ref_first = B.first.as<ull>(); d.ref_last = B.last.as<ull>(); d.n_map = B.n_map.as<ull>(); d.n_unmap = B.n_unmap.as<ull>();
     d.n_intv = B.n_intv.as<uint32_t>(); d.n_ref = n_ref;
-    BAM_CHK(rd->h_state.ensure(64));
+    SLX_CHK(rd->h_state.ensure(64));
     ull *hs = rd->h_state.as<ull>(), *bst = B.bst.as<ull>();
     uint64_t chunk_base = 0, ord_base = 0;
     int flip = 0;
@@ -1171,33 +1125,30 @@ static int bai_build_body(slx_bam *rd, int64_t batch_bytes, BaiBuild &B, std::st
         const uint64_t base_off = start_all[a] - rd->carry.size();
         int64_t done = a;
         uint64_t total = 0, n = 0, end = 0, rep = 0;
-        BAM_CHK(bam_span(rd, batch_bytes, a, nm, 0, 0, &done, &total, &n, &end, &rep));
+        SLX_CHK(bam_span(rd, batch_bytes, a, nm, 0, 0, &done, &total, &n, &end, &rep));
         if (!n && total) { slx_set_error("BAM: '%s' ends inside a record (%llu bytes after the last whole record)", rd->f.path.c_str(), (unsigned long long)total); return SLX_EIO; }
         rd->next_member = done;
-        BAM_CHK(bam_take_carry(rd, end, total));
-        BAM_HIPCHK(slx_wait_stream(st));
+        SLX_CHK(bam_take_carry(rd, end, total));
+        SLX_HIPCHK(slx_wait_stream(st));
         if (!n) break;
-        for (BamDBuf *b : {&B.key, &B.tp, &B.vbeg, &B.vend, &B.head, &B.hidx}) BAM_CHK(b->ensure(8 * (n + 1)));
-        for (BamDBuf *b : {&B.ckey, &B.cbeg, &B.cend}) BAM_CHK(b->ensure(8 * (chunk_base + n + 1), st, 8 * chunk_base));
+        for (BamDBuf *b : {&B.key, &B.tp, &B.vbeg, &B.vend, &B.head, &B.hidx}) SLX_CHK(b->ensure(8 * (n + 1)));
+        for (BamDBuf *b : {&B.ckey, &B.cbeg, &B.cend}) SLX_CHK(b->ensure(8 * (chunk_base + n + 1), st, 8 * chunk_base));
         const uint64_t cap = chunk_base + n + 1;
         const uint8_t *s = rd->d_out.as<uint8_t>();
         const uint64_t *rec = rd->d_rec.as<uint64_t>();
-        BAM_HIPCHK(hipEventRecord(rd->ev[7], st));
+        SLX_HIPCHK(hipEventRecord(rd->ev[7], st));
         k_bai_rec<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(s, rec, n, base_off, d, B.key.as<ull>(), B.tp.as<ull>(), B.vbeg.as<ull>(), B.vend.as<ull>(), bst);
-        BAM_HIPCHK(hipGetLastError());
+        SLX_HIPCHK(hipGetLastError());
         k_bai_heads<<<(unsigned)((n + 1 + 255) / 256), 256, 0, st>>>(B.key.as<ull>(), B.tp.as<ull>(), n, ord_base, B.carry.as<ull>() + 2 * flip, B.carry.as<ull>() + 2 * (flip ^ 1), B.head.as<ull>(), bst);
-        BAM_HIPCHK(hipGetLastError());
-        size_t tb = 0;
-        BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, B.head.as<ull>(), B.hidx.as<ull>(), (int)(n + 1), st));
-        BAM_CHK(B.tmp.ensure(tb + 8));
-        BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(B.tmp.p, tb, B.head.as<ull>(), B.hidx.as<ull>(), (int)(n + 1), st));
+        SLX_HIPCHK(hipGetLastError());
+        SLX_CHK(slx_exclusive_sum(B.tmp, B.head.as<ull>(), B.hidx.as<ull>(), n + 1, st, 8));
         k_bai_chunks<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(B.key.as<ull>(), B.vbeg.as<ull>(), B.vend.as<ull>(), B.head.as<ull>(), B.hidx.as<ull>(), n, chunk_base, cap, B.ckey.as<ull>(),
                                                                   B.cbeg.as<ull>(), B.cend.as<ull>());
-        BAM_HIPCHK(hipGetLastError());
-        BAM_HIPCHK(hipEventRecord(rd->ev[8], st));
-        BAM_CHK(down(hs, B.hidx.as<ull>() + n, 8)); BAM_CHK(down(hs + 1, bst, 16));
-        BAM_HIPCHK(slx_wait_stream(st));
-        rd->us[4] += ev_us(rd->ev[7], rd->ev[8]);
+        SLX_HIPCHK(hipGetLastError());
+        SLX_HIPCHK(hipEventRecord(rd->ev[8], st));
+        SLX_CHK(down(hs, B.hidx.as<ull>() + n, 8)); SLX_CHK(down(hs + 1, bst, 16));
+        SLX_HIPCHK(slx_wait_stream(st));
+        rd->us[4] += slx_ev_us(rd->ev[7], rd->ev[8]);
         if (hs[2] != ~0ull) { slx_set_error("BAM: '%s' is not coordinate-sorted: record %llu sorts before its predecessor; no index written", rd->f.path.c_str(), hs[2]); return SLX_EINVAL; }
         if (hs[1] & BAI_E_CIGAR) { slx_set_error("BAM: '%s': a record's name and CIGAR pass its block_size", rd->f.path.c_str()); return SLX_EIO; }
         if (hs[1] & BAI_E_TID) { slx_set_error("BAM: '%s': a record names a reference outside the header's %d", rd->f.path.c_str(), n_ref); return SLX_EIO; }
@@ -1212,23 +1163,23 @@ static int bai_build_body(slx_bam *rd, int64_t batch_bytes, BaiBuild &B, std::st
     ull n_no_coor = 0;
     if (nc) {
         if (nc >= (1ull << 31)) { slx_set_error("BAI: %llu chunks", (ull)nc); return SLX_EUNSUPPORTED; }
-        BAM_CHK(B.skey.ensure(8 * nc)); BAM_CHK(B.sidx_in.ensure(4 * nc)); BAM_CHK(B.sidx.ensure(4 * nc));
+        SLX_CHK(B.skey.ensure(8 * nc)); SLX_CHK(B.sidx_in.ensure(4 * nc)); SLX_CHK(B.sidx.ensure(4 * nc));
         k_bai_iota<<<(unsigned)((nc + 255) / 256), 256, 0, st>>>(B.sidx_in.as<uint32_t>(), nc);
-        BAM_HIPCHK(hipGetLastError());
+        SLX_HIPCHK(hipGetLastError());
         size_t tb = 0;
-        BAM_HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, B.ckey.as<ull>(), B.skey.as<ull>(), B.sidx_in.as<uint32_t>(), B.sidx.as<uint32_t>(), (int)nc, 0, 64, st));
-        BAM_CHK(B.tmp.ensure(tb + 8));
-        BAM_HIPCHK(hipcub::DeviceRadixSort::SortPairs(B.tmp.p, tb, B.ckey.as<ull>(), B.skey.as<ull>(), B.sidx_in.as<uint32_t>(), B.sidx.as<uint32_t>(), (int)nc, 0, 64, st));
-        BAM_CHK(down(skey.data(), B.skey.p, 8 * nc)); BAM_CHK(down(sidx.data(), B.sidx.p, 4 * nc)); BAM_CHK(down(cbeg.data(), B.cbeg.p, 8 * nc)); BAM_CHK(down(cend.data(), B.cend.p, 8 * nc));
+        SLX_HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, B.ckey.as<ull>(), B.skey.as<ull>(), B.sidx_in.as<uint32_t>(), B.sidx.as<uint32_t>(), (int)nc, 0, 64, st));
+        SLX_CHK(B.tmp.ensure(tb + 8));
+        SLX_HIPCHK(hipcub::DeviceRadixSort::SortPairs(B.tmp.p, tb, B.ckey.as<ull>(), B.skey.as<ull>(), B.sidx_in.as<uint32_t>(), B.sidx.as<uint32_t>(), (int)nc, 0, 64, st));
+        SLX_CHK(down(skey.data(), B.skey.p, 8 * nc)); SLX_CHK(down(sidx.data(), B.sidx.p, 4 * nc)); SLX_CHK(down(cbeg.data(), B.cbeg.p, 8 * nc)); SLX_CHK(down(cend.data(), B.cend.p, 8 * nc));
     }
     if (n_ref) {
         k_bai_fill<<<(unsigned)n_ref, 64, 0, st>>>(d);
-        BAM_HIPCHK(hipGetLastError());
-        BAM_CHK(down(lin.data(), B.lin.p, 8 * n_win)); BAM_CHK(down(first.data(), B.first.p, 8 * R)); BAM_CHK(down(last.data(), B.last.p, 8 * R));
-        BAM_CHK(down(n_map.data(), B.n_map.p, 8 * R)); BAM_CHK(down(n_unmap.data(), B.n_unmap.p, 8 * R)); BAM_CHK(down(n_intv.data(), B.n_intv.p, 4 * R));
+        SLX_HIPCHK(hipGetLastError());
+        SLX_CHK(down(lin.data(), B.lin.p, 8 * n_win)); SLX_CHK(down(first.data(), B.first.p, 8 * R)); SLX_CHK(down(last.data(), B.last.p, 8 * R));
+        SLX_CHK(down(n_map.data(), B.n_map.p, 8 * R)); SLX_CHK(down(n_unmap.data(), B.n_unmap.p, 8 * R)); SLX_CHK(down(n_intv.data(), B.n_intv.p, 4 * R));
     }
-    BAM_CHK(down(&n_no_coor, bst + 2, 8));
-    BAM_HIPCHK(slx_wait_stream(st));
+    SLX_CHK(down(&n_no_coor, bst + 2, 8));
+    SLX_HIPCHK(slx_wait_stream(st));
     // the host only lays the bytes out: per reference its bins in ascending number, the pseudo-bin last, then the windows
     bai.assign("BAI\1", 4);
     put_u32(bai, (uint32_t)n_ref);
@@ -1256,7 +1207,7 @@ static int bai_build_body(slx_bam *rd, int64_t batch_bytes, BaiBuild &B, std::st
 extern "C" int slx_bam_index_build_ex(const char *bam_path, int device, const char *bai_path, int64_t batch_bytes, int64_t chunk_bytes)
 {
     slx_bam *rd = nullptr;
-    BAM_CHK(bam_open_impl(bam_path, device, &rd, false));
+    SLX_CHK(bam_open_impl(bam_path, device, &rd, false));
     if (chunk_bytes >= 64) rd->chunk_bytes = (uint64_t)chunk_bytes;
     std::string bai;
     int rc;
@@ -1281,44 +1232,39 @@ extern "C" int slx_bam_reads_device(slx_bam *rd, const slx_bam_batch *batch, int
 {
     if (!rd || !batch || !d_bases || !d_offs || !n_reads) { slx_set_error("slx_bam_reads_device: null argument"); return SLX_EINVAL; }
     if (!rd->cur_stream || batch->d_stream != rd->cur_stream || batch->d_rec_off != rd->cur_rec) { slx_set_error("slx_bam_reads_device: the batch is not the reader's current one"); return SLX_EINVAL; }
-    BAM_HIPCHK(hipSetDevice(rd->device));
+    SLX_HIPCHK(hipSetDevice(rd->device));
     hipStream_t st = rd->st;
     const uint64_t n = (uint64_t)batch->n_records;
     typedef unsigned long long ull;
     rd->map_stream = nullptr;
-    for (BamDBuf *b : {&rd->d_keep, &rd->d_blen, &rd->d_kidx, &rd->d_boff}) BAM_CHK(b->ensure(8 * (n + 1)));
-    BAM_CHK(rd->d_state.ensure(64)); BAM_CHK(rd->h_state.ensure(64));
+    for (BamDBuf *b : {&rd->d_keep, &rd->d_blen, &rd->d_kidx, &rd->d_boff}) SLX_CHK(b->ensure(8 * (n + 1)));
+    SLX_CHK(rd->d_state.ensure(64)); SLX_CHK(rd->h_state.ensure(64));
     ull *hs = rd->h_state.as<ull>(), *ds = rd->d_state.as<ull>();
     hs[2] = ~0ull;
-    BAM_HIPCHK(hipMemcpyAsync(ds + 2, hs + 2, 8, hipMemcpyHostToDevice, st));
-    BAM_HIPCHK(hipEventRecord(rd->ev[5], st));
+    SLX_HIPCHK(hipMemcpyAsync(ds + 2, hs + 2, 8, hipMemcpyHostToDevice, st));
+    SLX_HIPCHK(hipEventRecord(rd->ev[5], st));
     const uint8_t *s = (const uint8_t *)rd->cur_stream;
     const uint64_t *rec = (const uint64_t *)rd->cur_rec;
     k_bam_keep<<<(unsigned)((n + 1 + 255) / 256), 256, 0, st>>>(s, rec, n, (uint32_t)skip_flags & 0xffffu, rd->d_keep.as<ull>(), rd->d_blen.as<ull>(), ds);
-    BAM_HIPCHK(hipGetLastError());
-    size_t tb = 0, tb2 = 0;
-    BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, rd->d_keep.as<ull>(), rd->d_kidx.as<ull>(), (int)(n + 1), st));
-    BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, rd->d_blen.as<ull>(), rd->d_boff.as<ull>(), (int)(n + 1), st));
-    tb = std::max(tb, tb2);
-    BAM_CHK(rd->d_tmp.ensure(tb + 8));
-    BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(rd->d_tmp.p, tb, rd->d_keep.as<ull>(), rd->d_kidx.as<ull>(), (int)(n + 1), st));
-    BAM_HIPCHK(hipcub::DeviceScan::ExclusiveSum(rd->d_tmp.p, tb, rd->d_blen.as<ull>(), rd->d_boff.as<ull>(), (int)(n + 1), st));
-    BAM_HIPCHK(hipMemcpyAsync(hs, rd->d_kidx.as<ull>() + n, 8, hipMemcpyDeviceToHost, st));
-    BAM_HIPCHK(hipMemcpyAsync(hs + 1, rd->d_boff.as<ull>() + n, 8, hipMemcpyDeviceToHost, st));
-    BAM_HIPCHK(hipMemcpyAsync(hs + 2, ds + 2, 8, hipMemcpyDeviceToHost, st));
-    BAM_HIPCHK(slx_wait_stream(st));
+    SLX_HIPCHK(hipGetLastError());
+    SLX_CHK(slx_exclusive_sum(rd->d_tmp, rd->d_keep.as<ull>(), rd->d_kidx.as<ull>(), n + 1, st, 8));
+    SLX_CHK(slx_exclusive_sum(rd->d_tmp, rd->d_blen.as<ull>(), rd->d_boff.as<ull>(), n + 1, st, 8));
+    SLX_HIPCHK(hipMemcpyAsync(hs, rd->d_kidx.as<ull>() + n, 8, hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(hipMemcpyAsync(hs + 1, rd->d_boff.as<ull>() + n, 8, hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(hipMemcpyAsync(hs + 2, ds + 2, 8, hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(slx_wait_stream(st));
     if (hs[2] != ~0ull) { slx_set_error("BAM: '%s': a record's fields pass its block_size (inflated offset %llu of the batch)", rd->f.path.c_str(), hs[2]); return SLX_EIO; }
     const uint64_t nr = hs[0], nb = hs[1];
-    BAM_CHK(rd->d_bases.ensure(nb + 8)); BAM_CHK(rd->d_offs.ensure(8 * (nr + 1))); BAM_CHK(rd->d_map.ensure(8 * (nr + 1))); BAM_CHK(rd->h_map.ensure(8 * (nr + 1)));
+    SLX_CHK(rd->d_bases.ensure(nb + 8)); SLX_CHK(rd->d_offs.ensure(8 * (nr + 1))); SLX_CHK(rd->d_map.ensure(8 * (nr + 1))); SLX_CHK(rd->h_map.ensure(8 * (nr + 1)));
     if (n) {
         k_bam_unpack<<<(unsigned)((n + 3) / 4), 256, 0, st>>>(s, rec, n, rd->d_kidx.as<ull>(), rd->d_boff.as<ull>(), original_strand, rd->d_bases.as<uint8_t>(), rd->d_offs.as<uint64_t>(),
                                                              rd->d_map.as<int64_t>());
-        BAM_HIPCHK(hipGetLastError());
-    } else BAM_HIPCHK(hipMemsetAsync(rd->d_offs.p, 0, 8, st));
-    BAM_HIPCHK(hipEventRecord(rd->ev[6], st));
-    if (nr) BAM_HIPCHK(hipMemcpyAsync(rd->h_map.p, rd->d_map.p, 8 * nr, hipMemcpyDeviceToHost, st));
-    BAM_HIPCHK(slx_wait_stream(st));
-    rd->us[3] = ev_us(rd->ev[5], rd->ev[6]);
+        SLX_HIPCHK(hipGetLastError());
+    } else SLX_HIPCHK(hipMemsetAsync(rd->d_offs.p, 0, 8, st));
+    SLX_HIPCHK(hipEventRecord(rd->ev[6], st));
+    if (nr) SLX_HIPCHK(hipMemcpyAsync(rd->h_map.p, rd->d_map.p, 8 * nr, hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(slx_wait_stream(st));
+    rd->us[3] = slx_ev_us(rd->ev[5], rd->ev[6]);
     *d_bases = rd->d_bases.p; *d_offs = rd->d_offs.p; *n_reads = (int64_t)nr;
     rd->map_stream = rd->cur_stream; rd->map_reads = (int64_t)nr;
     if (rec_of_read) *rec_of_read = rd->h_map.as<int64_t>();
@@ -1337,10 +1283,10 @@ extern "C" int slx_bam_hits_to_host(slx_bam *rd, slx_aligner *al, const slx_hits
 {
     if (!rd || !al || !dev || !host || !dev->on_device) { slx_set_error("slx_bam_hits_to_host: needs a reader, an aligner and a device-resident result"); return SLX_EINVAL; }
     memset(host, 0, sizeof *host);
-    BAM_HIPCHK(hipSetDevice(rd->device));
+    SLX_HIPCHK(hipSetDevice(rd->device));
     const uint64_t bytes = slx_hits_packed_size(dev);
-    BAM_CHK(rd->d_tmp.ensure(bytes + 8));
-    BAM_CHK(slx_hits_pack(al, dev, rd->d_tmp.p, bytes));
+    SLX_CHK(rd->d_tmp.ensure(bytes + 8));
+    SLX_CHK(slx_hits_pack(al, dev, rd->d_tmp.p, bytes));
     uint8_t *blk = (uint8_t *)malloc(bytes + 8);
     if (!blk) { slx_set_error("out of memory"); return SLX_ENOMEM; }
     if (hipMemcpy(blk, rd->d_tmp.p, bytes, hipMemcpyDeviceToHost) != hipSuccess) { free(blk); slx_set_error("HIP error copying the hits to the host"); return SLX_ENODEVICE; }
@@ -1382,9 +1328,9 @@ extern "C" int slx_bam_inflate_file(const char *path, int device, void *dst, uin
         for (int64_t a = 0; a < nm;) {
             int64_t b = a; uint64_t bytes = 0;
             while (b < nm && (b == a || bytes + rd.f.mem[b].isize <= (256ull << 20))) bytes += rd.f.mem[b++].isize;
-            BAM_CHK(rd.d_out.ensure(bytes + 8));
-            BAM_CHK(bam_inflate_span(&rd, a, b, 0, bytes));
-            if (bytes) { BAM_HIPCHK(hipMemcpyAsync((uint8_t *)dst + pos, rd.d_out.p, bytes, hipMemcpyDeviceToHost, rd.st)); BAM_HIPCHK(hipStreamSynchronize(rd.st)); }
+            SLX_CHK(rd.d_out.ensure(bytes + 8));
+            SLX_CHK(bam_inflate_span(&rd, a, b, 0, bytes));
+            if (bytes) { SLX_HIPCHK(hipMemcpyAsync((uint8_t *)dst + pos, rd.d_out.p, bytes, hipMemcpyDeviceToHost, rd.st)); SLX_HIPCHK(hipStreamSynchronize(rd.st)); }
             pos += bytes; a = b;
         }
         return SLX_OK;

@@ -17,9 +17,8 @@
 #include "slx_internal.h"
 #include "seqlib_amd_bam.h"
 #include "dev_deflate.h"
+#include "slx_hip.h"
 
-#define BGZF_HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { slx_set_error("HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, __LINE__); return SLX_ENODEVICE; } } while (0)
-#define BGZF_CHK(x) do { const int rc_ = (x); if (rc_ != SLX_OK) return rc_; } while (0)
 #define BGZF_SLOT 65536u
 
 typedef unsigned long long ull;
@@ -72,37 +71,9 @@ __global__ __launch_bounds__(256) void k_bgzf_pack(const uint8_t *slots, int n, 
 }
 
 // ------------------------------------------------------------------ host
-namespace {
-struct DBuf {
-    void *p = nullptr; size_t cap = 0;
-    int ensure(size_t n, hipStream_t st = nullptr, size_t keep = 0)
-    {
-        if (n <= cap) return SLX_OK;
-        void *q = nullptr;
-        if (hipMalloc(&q, n) != hipSuccess) { (void)hipGetLastError(); slx_set_error("BGZF writer: cannot allocate %zu bytes of HBM", n); return SLX_ENOMEM; }
-        if (keep && p) { BGZF_HIPCHK(hipMemcpyAsync(q, p, keep, hipMemcpyDeviceToDevice, st)); BGZF_HIPCHK(hipStreamSynchronize(st)); }
-        if (p) (void)hipFree(p);
-        p = q; cap = n;
-        return SLX_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <typename T> T *as() const { return (T *)p; }
-};
-struct HBuf {
-    void *p = nullptr; size_t cap = 0;
-    int ensure(size_t n)
-    {
-        if (n <= cap) return SLX_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; cap = 0;
-        if (hipHostMalloc(&p, n, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); p = nullptr; slx_set_error("BGZF writer: cannot pin %zu bytes", n); return SLX_ENOMEM; }
-        cap = n;
-        return SLX_OK;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-    template <typename T> T *as() const { return (T *)p; }
-};
-}  // namespace
+// no margin: the writer's buffers are computed from batch_bytes (the token arena is four bytes per input byte), so a batch never asks for more than the first did
+typedef SlxDevBuf<SlxExact> DBuf;
+typedef SlxPinBuf<SlxExact> HBuf;
 
 static const unsigned char BGZF_EOF[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
@@ -137,41 +108,36 @@ static int bgzf_fail(slx_bgzf *w, int rc)         // keeps the first error and i
 }
 static int bgzf_sticky(slx_bgzf *w) { slx_set_error("%s", w->err_msg.c_str()); return w->err; }
 
-static float bgzf_ev_us(hipEvent_t a, hipEvent_t b) { float ms = 0; return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms * 1000.f : 0.f; }
-
 // the worker: d_in[set][0, bytes) -> members -> file
 static int bgzf_compress(slx_bgzf *w, int set, uint64_t bytes)
 {
-    BGZF_HIPCHK(hipSetDevice(w->device));
+    SLX_HIPCHK(hipSetDevice(w->device));
     const int n = (int)((bytes + DEF_MEMBER - 1) / DEF_MEMBER);
     hipStream_t st = w->st_work;
-    BGZF_CHK(w->d_slots.ensure((size_t)n * BGZF_SLOT));
-    BGZF_CHK(w->d_tok.ensure((size_t)n * DEF_MEMBER * 4));          // the token arena, computed from the batch: one token per input byte at most
-    BGZF_CHK(w->d_size.ensure(sizeof(ull) * ((size_t)n + 1)));
-    BGZF_CHK(w->d_off.ensure(sizeof(ull) * ((size_t)n + 1)));
-    BGZF_CHK(w->d_flag.ensure(4 * (size_t)n));
-    BGZF_CHK(w->d_pack.ensure((size_t)n * BGZF_SLOT));
-    BGZF_CHK(w->h_pack.ensure((size_t)n * BGZF_SLOT));
-    BGZF_CHK(w->h_flag.ensure(4 * (size_t)n));
-    BGZF_CHK(w->h_total.ensure(sizeof(ull)));
+    SLX_CHK(w->d_slots.ensure((size_t)n * BGZF_SLOT));
+    SLX_CHK(w->d_tok.ensure((size_t)n * DEF_MEMBER * 4));          // the token arena, computed from the batch: one token per input byte at most
+    SLX_CHK(w->d_size.ensure(sizeof(ull) * ((size_t)n + 1)));
+    SLX_CHK(w->d_off.ensure(sizeof(ull) * ((size_t)n + 1)));
+    SLX_CHK(w->d_flag.ensure(4 * (size_t)n));
+    SLX_CHK(w->d_pack.ensure((size_t)n * BGZF_SLOT));
+    SLX_CHK(w->h_pack.ensure((size_t)n * BGZF_SLOT));
+    SLX_CHK(w->h_flag.ensure(4 * (size_t)n));
+    SLX_CHK(w->h_total.ensure(sizeof(ull)));
     const uint8_t *in = w->d_in[set].as<uint8_t>();
-    BGZF_HIPCHK(hipEventRecord(w->ev[0], st));
+    SLX_HIPCHK(hipEventRecord(w->ev[0], st));
     k_bgzf_deflate<<<n, 64, 0, st>>>(in, bytes, n, w->d_slots.as<uint8_t>(), w->d_tok.as<uint32_t>(), w->d_size.as<ull>(), w->d_flag.as<uint32_t>());
-    BGZF_HIPCHK(hipGetLastError());
-    BGZF_HIPCHK(hipEventRecord(w->ev[1], st));
+    SLX_HIPCHK(hipGetLastError());
+    SLX_HIPCHK(hipEventRecord(w->ev[1], st));
     k_bgzf_trailer<<<(n + 3) / 4, 256, 0, st>>>(in, bytes, n, w->d_slots.as<uint8_t>(), w->d_size.as<ull>());
-    BGZF_HIPCHK(hipGetLastError());
-    BGZF_HIPCHK(hipEventRecord(w->ev[2], st));
-    size_t tb = 0;
-    BGZF_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, w->d_size.as<ull>(), w->d_off.as<ull>(), n + 1, st));
-    BGZF_CHK(w->d_tmp.ensure(tb));
-    BGZF_HIPCHK(hipcub::DeviceScan::ExclusiveSum(w->d_tmp.p, tb, w->d_size.as<ull>(), w->d_off.as<ull>(), n + 1, st));
+    SLX_HIPCHK(hipGetLastError());
+    SLX_HIPCHK(hipEventRecord(w->ev[2], st));
+    SLX_CHK(slx_exclusive_sum(w->d_tmp, w->d_size.as<ull>(), w->d_off.as<ull>(), (size_t)n + 1, st));
     k_bgzf_pack<<<n, 256, 0, st>>>(w->d_slots.as<uint8_t>(), n, w->d_size.as<ull>(), w->d_off.as<ull>(), w->d_pack.as<uint8_t>(), (uint64_t)n * BGZF_SLOT);
-    BGZF_HIPCHK(hipGetLastError());
-    BGZF_HIPCHK(hipEventRecord(w->ev[3], st));
-    BGZF_HIPCHK(hipMemcpyAsync(w->h_total.p, w->d_off.as<ull>() + n, sizeof(ull), hipMemcpyDeviceToHost, st));
-    BGZF_HIPCHK(hipMemcpyAsync(w->h_flag.p, w->d_flag.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
-    BGZF_HIPCHK(hipStreamSynchronize(st));
+    SLX_HIPCHK(hipGetLastError());
+    SLX_HIPCHK(hipEventRecord(w->ev[3], st));
+    SLX_HIPCHK(hipMemcpyAsync(w->h_total.p, w->d_off.as<ull>() + n, sizeof(ull), hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(hipMemcpyAsync(w->h_flag.p, w->d_flag.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(hipStreamSynchronize(st));
     const uint32_t *flag = w->h_flag.as<uint32_t>();
     int64_t stored = 0;
     for (int i = 0; i < n; ++i) {
@@ -180,9 +146,9 @@ static int bgzf_compress(slx_bgzf *w, int set, uint64_t bytes)
     }
     const ull total = *w->h_total.as<ull>();
     if (total < 26ull * (ull)n || total > (ull)n * BGZF_SLOT) { slx_set_error("BGZF writer: internal: %llu bytes for %d members", total, n); return SLX_EINTERNAL; }
-    BGZF_HIPCHK(hipMemcpyAsync(w->h_pack.p, w->d_pack.p, total, hipMemcpyDeviceToHost, st));        // one copy of exactly the file bytes
-    BGZF_HIPCHK(hipStreamSynchronize(st));
-    w->us[0] += bgzf_ev_us(w->ev[0], w->ev[1]); w->us[1] += bgzf_ev_us(w->ev[1], w->ev[2]); w->us[2] += bgzf_ev_us(w->ev[2], w->ev[3]);
+    SLX_HIPCHK(hipMemcpyAsync(w->h_pack.p, w->d_pack.p, total, hipMemcpyDeviceToHost, st));        // one copy of exactly the file bytes
+    SLX_HIPCHK(hipStreamSynchronize(st));
+    w->us[0] += slx_ev_us(w->ev[0], w->ev[1]); w->us[1] += slx_ev_us(w->ev[1], w->ev[2]); w->us[2] += slx_ev_us(w->ev[2], w->ev[3]);
     w->c_members += n; w->c_stored += stored; w->c_in += (int64_t)bytes; w->c_out += (int64_t)total;
     if (std::fwrite(w->h_pack.p, 1, total, w->fp) != total) { slx_set_error("BGZF writer: cannot write to '%s': %s", w->path.c_str(), strerror(errno)); return SLX_EIO; }
     return SLX_OK;
@@ -204,12 +170,12 @@ static int bgzf_submit(slx_bgzf *w, bool final)
 {
     const uint64_t take = final ? w->fill : w->fill / DEF_MEMBER * DEF_MEMBER, rest = w->fill - take;
     if (take == 0) return SLX_OK;
-    BGZF_CHK(bgzf_join(w));                  // the other segment is free once the batch before this one is in the file
+    SLX_CHK(bgzf_join(w));                  // the other segment is free once the batch before this one is in the file
     const int set = w->cur, other = set ^ 1;
     if (rest) {
-        BGZF_CHK(w->d_in[other].ensure(std::max<size_t>((size_t)w->batch_bytes, rest)));
-        BGZF_HIPCHK(hipMemcpyAsync(w->d_in[other].p, w->d_in[set].as<uint8_t>() + take, rest, hipMemcpyDeviceToDevice, w->st_stage));
-        BGZF_HIPCHK(hipStreamSynchronize(w->st_stage));
+        SLX_CHK(w->d_in[other].ensure(std::max<size_t>((size_t)w->batch_bytes, rest)));
+        SLX_HIPCHK(hipMemcpyAsync(w->d_in[other].p, w->d_in[set].as<uint8_t>() + take, rest, hipMemcpyDeviceToDevice, w->st_stage));
+        SLX_HIPCHK(hipStreamSynchronize(w->st_stage));
     }
     w->cur = other; w->fill = rest;
     w->worker_rc = SLX_OK;
@@ -240,23 +206,15 @@ static void bgzf_free(slx_bgzf *w)
 
 static int bgzf_open_impl(slx_bgzf *w, const char *path, int device)
 {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        slx_set_error("no HIP device: the BGZF writer compresses on MI355X only (no CPU fallback); '%s' is not created", path);
-        return SLX_ENODEVICE;
-    }
-    if (device < 0) { BGZF_HIPCHK(hipGetDevice(&device)); }
-    if (device >= ndev) { slx_set_error("BGZF writer: device %d is not one of the %d visible", device, ndev); return SLX_EINVAL; }
-    BGZF_HIPCHK(hipSetDevice(device));
-    w->device = device;
+    const std::string no_device = std::string("no HIP device: the BGZF writer compresses on MI355X only (no CPU fallback); '") + path + "' is not created";
+    SLX_CHK(slx_pick_device(device, no_device.c_str(), "BGZF writer", &w->device));
     w->path = path;
     w->is_stdout = w->path == "-";
     w->fp = w->is_stdout ? stdout : std::fopen(path, "wb");
     if (!w->fp) { slx_set_error("BGZF writer: cannot create '%s': %s", path, strerror(errno)); return SLX_EIO; }
-    BGZF_HIPCHK(hipStreamCreateWithFlags(&w->st_stage, hipStreamNonBlocking));
-    BGZF_HIPCHK(hipStreamCreateWithFlags(&w->st_work, hipStreamNonBlocking));
-    for (auto &e : w->ev) BGZF_HIPCHK(hipEventCreate(&e));
+    SLX_HIPCHK(hipStreamCreateWithFlags(&w->st_stage, hipStreamNonBlocking));
+    SLX_HIPCHK(hipStreamCreateWithFlags(&w->st_work, hipStreamNonBlocking));
+    for (auto &e : w->ev) SLX_HIPCHK(hipEventCreate(&e));
     return SLX_OK;
 }
 

@@ -1,7 +1,7 @@
 // slx_fastq.hip -- the FastqReader path of libseqlib_amd.so (include/seqlib_amd_fastq.h): FASTA / FASTQ text parsed on the GPU into the arrays
 // slx_align_batch_device and slx_rec_build take.  DESIGN.md section 9.6 has the argument; the pattern is the BAM reader's (section 9): guess, verify, and walk
 // again what fails.
-//   k_bgzf_inflate / k_bgzf_crc   (slx_bam.hip, through slx_bgzf_inflate_launch) BGZF members straight into the text buffer, one wave per member     dev_inflate.h
+//   k_bgzf_inflate / k_bgzf_crc   (slx_bam.hip, through slx_bgzf_inflate_members) BGZF members straight into the text buffer, one wave per member     dev_inflate.h
 //   k_fq_count / k_fq_lines   line feeds per tile, then (after hipCUB's scan of the counts) the line starts, by a wave prefix per 1 KiB step
 //   k_fq_check                one lane per record taken as four lines: the acceptance test, the fields' places and lengths     dev_fastq.h
 //   k_fq_gather               one launch per stream (bases, qualities, names, comments): one wave per tile of the OUTPUT, through LDS, aligned 16-byte stores
@@ -33,9 +33,6 @@
 #include "dev_fastq.h"
 #include "fq_host.h"
 #include "fq_text.h"
-
-#define FQ_HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { slx_set_error("HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, __LINE__); return SLX_ENODEVICE; } } while (0)
-#define FQ_CHK(x) do { const int rc_ = (x); if (rc_ != SLX_OK) return rc_; } while (0)
 
 typedef uint32_t fq_v4 __attribute__((ext_vector_type(4)));
 
@@ -174,6 +171,7 @@ void fq_text_free(FqText *t)
     if (t->st) { (void)hipSetDevice(t->device); (void)hipStreamSynchronize(t->st); }
     for (FqDBuf *b : t->text_dbufs()) b->release();
     for (FqHBuf *b : t->text_hbufs()) b->release();
+    t->stage.release();
     for (auto &e : t->ev) if (e) (void)hipEventDestroy(e);
     if (t->st) (void)hipStreamDestroy(t->st);
     if (t->map) munmap((void *)t->map, t->fsize);
@@ -196,7 +194,7 @@ int fq_text_start(FqText *t)
 {
     t->have = t->used = 0; t->src_eof = false; t->next_member = 0; t->c_members = 0;
     for (float &u : t->us) u = 0;
-    if (t->source != 1) FQ_CHK(t->prod.start(t->path, t->source == 2));
+    if (t->source != 1) SLX_CHK(t->prod.start(t->path, t->source == 2));
     return SLX_OK;
 }
 
@@ -219,13 +217,9 @@ int fq_text_open(FqText *t, const char *path, int device)
     const ssize_t got = ::pread(fd, h, sizeof h, 0);
     int source = 0;
     if (got >= 2 && h[0] == 0x1f && h[1] == 0x8b) source = (got >= 18 && h[2] == 8 && (h[3] & 4) && h[12] == 'B' && h[13] == 'C') ? 1 : 2;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        ::close(fd);
-        slx_set_error("no HIP device: the %s parses on MI355X only (no CPU fallback)", who);
-        return SLX_ENODEVICE;
-    }
+    const std::string no_device = std::string("no HIP device: the ") + who + " parses on MI355X only (no CPU fallback)";
+    const int rc = slx_pick_device(device, no_device.c_str(), who, &t->device);
+    if (rc != SLX_OK) { ::close(fd); return rc; }
     t->path = path; t->source = source;
     if (source == 1) {
         t->fd = fd; t->fsize = (uint64_t)sb.st_size;
@@ -233,14 +227,11 @@ int fq_text_open(FqText *t, const char *path, int device)
         if (p == MAP_FAILED) { slx_set_error("%s: cannot map '%s'", who, path); return SLX_EIO; }
         t->map = (const uint8_t *)p;
         slx_bam_member *m = nullptr; int64_t nm = 0;
-        FQ_CHK(slx_bam_scan_members(path, &m, &nm, nullptr));
+        SLX_CHK(slx_bam_scan_members(path, &m, &nm, nullptr));
         t->mem.assign(m, m + nm);
         slx_bam_members_free(m);
     } else ::close(fd);
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) { slx_set_error("%s: no current device", who); return SLX_ENODEVICE; }
-    if (device >= ndev) { slx_set_error("%s: device %d is not one of the %d visible", who, device, ndev); return SLX_EINVAL; }
-    t->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&t->st, hipStreamNonBlocking) != hipSuccess) { slx_set_error("%s: cannot create a stream on device %d", who, device); return SLX_ENODEVICE; }
+    if (hipStreamCreateWithFlags(&t->st, hipStreamNonBlocking) != hipSuccess) { slx_set_error("%s: cannot create a stream on device %d", who, t->device); return SLX_ENODEVICE; }
     for (auto &e : t->ev) if (hipEventCreate(&e) != hipSuccess) { slx_set_error("%s: cannot create an event", who); return SLX_ENODEVICE; }
     return SLX_OK;
 }
@@ -262,7 +253,7 @@ extern "C" void slx_fastq_close(slx_fastq *fq) { if (fq) fq_free(fq); }
 extern "C" int slx_fastq_rewind(slx_fastq *fq)
 {
     if (!fq) { slx_set_error("slx_fastq_rewind: null reader"); return SLX_EINVAL; }
-    FQ_HIPCHK(hipSetDevice(fq->device));
+    SLX_HIPCHK(hipSetDevice(fq->device));
     return fq_start(fq);
 }
 
@@ -302,34 +293,13 @@ int fq_pull(FqText *fq, uint64_t want)
     if (fq->source == 1) {
         const int64_t a = fq->next_member, nm = (int64_t)fq->mem.size();
         int64_t b = a;
-        uint64_t out = 0, comp = 0;
-        while (b < nm && (out < want || b == a)) { out += fq->mem[b].isize; comp += fq->mem[b].data_len; ++b; }
-        const int n = (int)(b - a);
-        if (n > 0 && out > 0) {
-            FQ_CHK(T.ensure(fq->have + out + 64, st, fq->have));
-            FQ_CHK(fq->h_comp.ensure(comp + 8)); FQ_CHK(fq->d_comp.ensure(comp + 8));
-            FQ_CHK(fq->h_desc.ensure(sizeof(bam_mdesc) * n)); FQ_CHK(fq->d_desc.ensure(sizeof(bam_mdesc) * n));
-            FQ_CHK(fq->h_err.ensure(4 * (size_t)n)); FQ_CHK(fq->d_err.ensure(4 * (size_t)n));
-            bam_mdesc *d = fq->h_desc.as<bam_mdesc>();
-            uint64_t ci = 0, oo = fq->have;
-            for (int64_t i = a; i < b; ++i) {
-                const slx_bam_member &m = fq->mem[i];
-                memcpy(fq->h_comp.as<uint8_t>() + ci, fq->map + m.file_off + m.data_off, m.data_len);
-                d[i - a] = bam_mdesc{ci, oo, m.data_len, m.isize, m.crc32, 0};
-                ci += m.data_len; oo += m.isize;
-            }
-            const uint64_t out_bytes = fq->have + out;
-            FQ_HIPCHK(hipMemcpyAsync(fq->d_comp.p, fq->h_comp.p, comp, hipMemcpyHostToDevice, st));
-            FQ_HIPCHK(hipMemcpyAsync(fq->d_desc.p, fq->h_desc.p, sizeof(bam_mdesc) * n, hipMemcpyHostToDevice, st));
-            FQ_HIPCHK(hipEventRecord(fq->ev[8], st));
-            FQ_HIPCHK(slx_bgzf_inflate_launch(st, fq->d_comp.as<uint8_t>(), comp, fq->d_desc.as<bam_mdesc>(), n, T.as<uint8_t>(), out_bytes, fq->d_err.as<uint32_t>()));
-            FQ_HIPCHK(hipEventRecord(fq->ev[9], st));
-            FQ_HIPCHK(hipMemcpyAsync(fq->h_err.p, fq->d_err.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
-            FQ_HIPCHK(slx_wait_stream(st));
-            fq->us[3] += fq_ev_us(fq->ev[8], fq->ev[9]); fq->c_members += n;
-            const uint32_t *err = fq->h_err.as<uint32_t>();
-            for (int i = 0; i < n; ++i)
-                if (err[i]) { slx_set_error("BGZF: '%s': the member at file offset %llu does not inflate (code %u)", fq->path.c_str(), (unsigned long long)fq->mem[a + i].file_off, err[i]); return SLX_EIO; }
+        uint64_t out = 0;
+        while (b < nm && (out < want || b == a)) out += fq->mem[b++].isize;
+        if (b > a && out > 0) {
+            SLX_CHK(T.ensure(fq->have + out + 64, st, fq->have));
+            float us[2] = {0, 0};
+            SLX_CHK(slx_bgzf_inflate_members(fq->map, fq->path.c_str(), fq->mem.data(), a, b, fq->stage, T.as<uint8_t>(), fq->have, fq->have + out, st, fq->ev[8], nullptr, fq->ev[9], us));
+            fq->us[3] += us[0]; fq->c_members += b - a;
             fq->have += out;
         }
         fq->next_member = b;
@@ -342,9 +312,9 @@ int fq_pull(FqText *fq, uint64_t want)
         if (s.err) { slx_set_error("%s: reading '%s' failed%s", fq->who, fq->path.c_str(), fq->source == 2 ? " (zlib refuses the stream)" : ""); return SLX_EIO; }
         const uint64_t take = std::min<uint64_t>(want - got, s.n - fq->prod.tail_pos);
         if (take) {
-            FQ_CHK(T.ensure(fq->have + take + 64, st, fq->have));
-            FQ_HIPCHK(hipMemcpyAsync(T.as<uint8_t>() + fq->have, s.p + fq->prod.tail_pos, take, hipMemcpyHostToDevice, st));
-            FQ_HIPCHK(slx_wait_stream(st));          // (the slot goes back to the producer)
+            SLX_CHK(T.ensure(fq->have + take + 64, st, fq->have));
+            SLX_HIPCHK(hipMemcpyAsync(T.as<uint8_t>() + fq->have, s.p + fq->prod.tail_pos, take, hipMemcpyHostToDevice, st));
+            SLX_HIPCHK(slx_wait_stream(st));          // (the slot goes back to the producer)
             fq->have += take; got += take; fq->prod.tail_pos += take;
         }
         if (fq->prod.tail_pos == s.n) {
@@ -355,15 +325,6 @@ int fq_pull(FqText *fq, uint64_t want)
     return SLX_OK;
 }
 
-int fq_scan(FqText *fq, const fq_u64 *in, fq_u64 *out, uint64_t n)
-{
-    size_t tb = 0;
-    FQ_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int64_t)n, fq->st));
-    FQ_CHK(fq->d_tmp.ensure(tb + 16));
-    FQ_HIPCHK(hipcub::DeviceScan::ExclusiveSum(fq->d_tmp.p, tb, in, out, (int64_t)n, fq->st));
-    return SLX_OK;
-}
-
 int fq_line_starts(FqText *fq, uint64_t *n_lines, int *virt_out)
 {
     hipStream_t st = fq->st;
@@ -371,24 +332,24 @@ int fq_line_starts(FqText *fq, uint64_t *n_lines, int *virt_out)
     const uint64_t n = fq->have;
     const uint32_t tile = fq->tile_bytes;
     const uint64_t n_tiles = (n + tile - 1) / tile;
-    FQ_CHK(fq->h_small.ensure(256));
+    SLX_CHK(fq->h_small.ensure(256));
     fq_u64 *hs = fq->h_small.as<fq_u64>();
-    FQ_CHK(fq->d_count.ensure(8 * (n_tiles + 1))); FQ_CHK(fq->d_base.ensure(8 * (n_tiles + 1)));
-    FQ_HIPCHK(hipMemsetAsync(fq->d_count.p, 0, 8 * (n_tiles + 1), st));
-    FQ_HIPCHK(hipEventRecord(fq->ev[0], st));
+    SLX_CHK(fq->d_count.ensure(8 * (n_tiles + 1))); SLX_CHK(fq->d_base.ensure(8 * (n_tiles + 1)));
+    SLX_HIPCHK(hipMemsetAsync(fq->d_count.p, 0, 8 * (n_tiles + 1), st));
+    SLX_HIPCHK(hipEventRecord(fq->ev[0], st));
     k_fq_count<<<(unsigned)((n_tiles + 3) / 4), 256, 0, st>>>(text, n, tile, n_tiles, fq->d_count.as<fq_u64>());
-    FQ_HIPCHK(hipGetLastError());
-    FQ_CHK(fq_scan(fq, fq->d_count.as<fq_u64>(), fq->d_base.as<fq_u64>(), n_tiles + 1));
-    FQ_HIPCHK(hipMemcpyAsync(hs, fq->d_base.as<fq_u64>() + n_tiles, 8, hipMemcpyDeviceToHost, st));
-    FQ_HIPCHK(hipMemcpyAsync(hs + 1, text + n - 1, 1, hipMemcpyDeviceToHost, st));
-    FQ_HIPCHK(slx_wait_stream(st));
+    SLX_HIPCHK(hipGetLastError());
+    SLX_CHK(fq_scan(fq, fq->d_count.as<fq_u64>(), fq->d_base.as<fq_u64>(), n_tiles + 1));
+    SLX_HIPCHK(hipMemcpyAsync(hs, fq->d_base.as<fq_u64>() + n_tiles, 8, hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(hipMemcpyAsync(hs + 1, text + n - 1, 1, hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(slx_wait_stream(st));
     const uint64_t n_nl = hs[0];
     const int virt = fq->src_eof && *(const uint8_t *)(hs + 1) != '\n' ? 1 : 0;
     const uint64_t L = n_nl + (uint64_t)virt;
-    FQ_CHK(fq->d_line.ensure(8 * (L + 2)));
+    SLX_CHK(fq->d_line.ensure(8 * (L + 2)));
     k_fq_lines<<<(unsigned)((n_tiles + 3) / 4), 256, 0, st>>>(text, n, tile, n_tiles, fq->d_base.as<fq_u64>(), virt, fq->d_line.as<fq_u64>());
-    FQ_HIPCHK(hipGetLastError());
-    FQ_HIPCHK(hipEventRecord(fq->ev[1], st));
+    SLX_HIPCHK(hipGetLastError());
+    SLX_HIPCHK(hipEventRecord(fq->ev[1], st));
     *n_lines = L; *virt_out = virt;
     return SLX_OK;
 }
@@ -397,9 +358,9 @@ int fq_shift(FqText *fq, uint64_t room)
 {
     const uint64_t left = fq->have - fq->used;
     FqDBuf &O = fq->d_text[fq->cur ^ 1];
-    FQ_CHK(O.ensure(left + room + 64));
-    if (left) FQ_HIPCHK(hipMemcpyAsync(O.p, fq->d_text[fq->cur].as<uint8_t>() + fq->used, left, hipMemcpyDeviceToDevice, fq->st));
-    FQ_HIPCHK(slx_wait_stream(fq->st));
+    SLX_CHK(O.ensure(left + room + 64));
+    if (left) SLX_HIPCHK(hipMemcpyAsync(O.p, fq->d_text[fq->cur].as<uint8_t>() + fq->used, left, hipMemcpyDeviceToDevice, fq->st));
+    SLX_HIPCHK(slx_wait_stream(fq->st));
     fq->cur ^= 1; fq->have = left; fq->used = 0;
     return SLX_OK;
 }
@@ -413,29 +374,29 @@ static int fq_parse(slx_fastq *fq, int64_t *n_reads, int64_t *n_slow, uint64_t *
     const bool eof = fq->src_eof;
     uint64_t L = 0;
     int virt = 0;
-    FQ_CHK(fq_line_starts(fq, &L, &virt));          // ---- line starts
+    SLX_CHK(fq_line_starts(fq, &L, &virt));          // ---- line starts
     fq_u64 *hs = fq->h_small.as<fq_u64>();
     // ---- the records taken as four lines each
     const uint64_t n_cand = L / 4 + 1;
     FqDBuf *per8[7] = {&fq->d_len_b, &fq->d_len_n, &fq->d_len_c, &fq->d_src_b, &fq->d_src_q, &fq->d_src_n, &fq->d_src_c};
-    for (FqDBuf *b : per8) FQ_CHK(b->ensure(8 * (n_cand + 1)));
-    FQ_CHK(fq->d_flags.ensure(n_cand + 1));
-    FQ_CHK(fq->d_first.ensure(8));
-    FQ_HIPCHK(hipMemsetAsync(fq->d_first.p, 0xff, 8, st));
+    for (FqDBuf *b : per8) SLX_CHK(b->ensure(8 * (n_cand + 1)));
+    SLX_CHK(fq->d_flags.ensure(n_cand + 1));
+    SLX_CHK(fq->d_first.ensure(8));
+    SLX_HIPCHK(hipMemsetAsync(fq->d_first.p, 0xff, 8, st));
     fq_arrays A{fq->d_len_b.as<fq_u64>(), fq->d_len_n.as<fq_u64>(), fq->d_len_c.as<fq_u64>(), fq->d_src_b.as<fq_u64>(), fq->d_src_q.as<fq_u64>(), fq->d_src_n.as<fq_u64>(),
                 fq->d_src_c.as<fq_u64>(), fq->d_flags.as<uint8_t>()};
-    FQ_HIPCHK(hipEventRecord(fq->ev[2], st));
+    SLX_HIPCHK(hipEventRecord(fq->ev[2], st));
     k_fq_check<<<(unsigned)((n_cand + 255) / 256), 256, 0, st>>>(text, n, fq->d_line.as<fq_u64>(), L, eof ? 1 : 0, fq->fast_fail, n_cand, A, fq->d_first.as<fq_u64>());
-    FQ_HIPCHK(hipGetLastError());
-    FQ_HIPCHK(hipEventRecord(fq->ev[3], st));
-    FQ_HIPCHK(hipMemcpyAsync(hs, fq->d_first.p, 8, hipMemcpyDeviceToHost, st));
-    FQ_HIPCHK(slx_wait_stream(st));
-    fq->us[0] += fq_ev_us(fq->ev[0], fq->ev[1]); fq->us[1] += fq_ev_us(fq->ev[2], fq->ev[3]);
+    SLX_HIPCHK(hipGetLastError());
+    SLX_HIPCHK(hipEventRecord(fq->ev[3], st));
+    SLX_HIPCHK(hipMemcpyAsync(hs, fq->d_first.p, 8, hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(slx_wait_stream(st));
+    fq->us[0] += slx_ev_us(fq->ev[0], fq->ev[1]); fq->us[1] += slx_ev_us(fq->ev[2], fq->ev[3]);
     if (hs[0] == ~0ull) { slx_set_error("FASTQ reader: internal: no record ends the fast path"); return SLX_EINTERNAL; }          // (the last candidate is never FQ_OK)
     const uint64_t F = hs[0] >> 2;
     const int status = (int)(hs[0] & 3);
-    FQ_HIPCHK(hipMemcpyAsync(hs, fq->d_line.as<fq_u64>() + 4 * F, 8, hipMemcpyDeviceToHost, st));
-    FQ_HIPCHK(slx_wait_stream(st));
+    SLX_HIPCHK(hipMemcpyAsync(hs, fq->d_line.as<fq_u64>() + 4 * F, 8, hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(slx_wait_stream(st));
     const uint64_t fast_end = status == FQ_NONE ? n : std::min<uint64_t>(hs[0], n);
     // ---- the serial parser from the first record that failed
     uint64_t S = 0, pos = 0;
@@ -443,9 +404,9 @@ static int fq_parse(slx_fastq *fq, int64_t *n_reads, int64_t *n_slow, uint64_t *
     std::string sb, sq, sn, sc, sf;
     if (status == FQ_FAIL) {
         const uint64_t m = n - fast_end;
-        FQ_CHK(fq->h_tail.ensure(m + 1));
-        FQ_HIPCHK(hipMemcpyAsync(fq->h_tail.p, text + fast_end, m, hipMemcpyDeviceToHost, st));
-        FQ_HIPCHK(slx_wait_stream(st));
+        SLX_CHK(fq->h_tail.ensure(m + 1));
+        SLX_HIPCHK(hipMemcpyAsync(fq->h_tail.p, text + fast_end, m, hipMemcpyDeviceToHost, st));
+        SLX_HIPCHK(slx_wait_stream(st));
         const uint8_t *p = fq->h_tail.as<uint8_t>();
         fqh_rec r;
         for (;;) {
@@ -467,13 +428,13 @@ static int fq_parse(slx_fastq *fq, int64_t *n_reads, int64_t *n_slow, uint64_t *
     if (N == 0) return SLX_OK;
     if (N >= 0xffffffffull) { slx_set_error("FASTQ reader: 2^32 reads or more in one batch; ask for fewer bytes"); return SLX_EUNSUPPORTED; }
     // ---- the slow reads' bytes and per-record entries go up behind the fast ones
-    for (FqDBuf *b : per8) FQ_CHK(b->ensure(8 * (N + 1), st, 8 * F));
-    FQ_CHK(fq->d_flags.ensure(N + 1, st, F));
+    for (FqDBuf *b : per8) SLX_CHK(b->ensure(8 * (N + 1), st, 8 * F));
+    SLX_CHK(fq->d_flags.ensure(N + 1, st, F));
     {
         const uint64_t nb = sb.size(), nn = sn.size(), nc = sc.size();
         const uint64_t bytes = 2 * nb + nn + nc;
         const uint64_t arr = 8 * (3 * (S + 1) + 4 * S);
-        FQ_CHK(fq->h_slow.ensure(bytes + arr + S + 64)); FQ_CHK(fq->d_slow.ensure(bytes + 64));
+        SLX_CHK(fq->h_slow.ensure(bytes + arr + S + 64)); SLX_CHK(fq->d_slow.ensure(bytes + 64));
         uint8_t *h = fq->h_slow.as<uint8_t>();
         memcpy(h, sb.data(), nb); memcpy(h + nb, sq.data(), nb); memcpy(h + 2 * nb, sn.data(), nn); memcpy(h + 2 * nb + nn, sc.data(), nc);
         const uint64_t a0 = (bytes + 15) & ~15ull;
@@ -490,41 +451,41 @@ static int fq_parse(slx_fastq *fq, int64_t *n_reads, int64_t *n_slow, uint64_t *
             hf[i] = (uint8_t)sf[i];
         }
         len[0][S] = len[1][S] = len[2][S] = 0;
-        if (bytes) FQ_HIPCHK(hipMemcpyAsync(fq->d_slow.p, h, bytes, hipMemcpyHostToDevice, st));
-        for (int i = 0; i < 3; ++i) FQ_HIPCHK(hipMemcpyAsync(per8[i]->as<fq_u64>() + F, len[i], 8 * (S + 1), hipMemcpyHostToDevice, st));
+        if (bytes) SLX_HIPCHK(hipMemcpyAsync(fq->d_slow.p, h, bytes, hipMemcpyHostToDevice, st));
+        for (int i = 0; i < 3; ++i) SLX_HIPCHK(hipMemcpyAsync(per8[i]->as<fq_u64>() + F, len[i], 8 * (S + 1), hipMemcpyHostToDevice, st));
         if (S) {
-            for (int i = 0; i < 4; ++i) FQ_HIPCHK(hipMemcpyAsync(per8[3 + i]->as<fq_u64>() + F, src[i], 8 * S, hipMemcpyHostToDevice, st));
-            FQ_HIPCHK(hipMemcpyAsync(fq->d_flags.as<uint8_t>() + F, hf, S, hipMemcpyHostToDevice, st));
+            for (int i = 0; i < 4; ++i) SLX_HIPCHK(hipMemcpyAsync(per8[3 + i]->as<fq_u64>() + F, src[i], 8 * S, hipMemcpyHostToDevice, st));
+            SLX_HIPCHK(hipMemcpyAsync(fq->d_flags.as<uint8_t>() + F, hf, S, hipMemcpyHostToDevice, st));
         }
     }
     // ---- offsets, then the four streams
     FqDBuf *offs[3] = {&fq->d_off_b, &fq->d_off_n, &fq->d_off_c};
-    FQ_HIPCHK(hipEventRecord(fq->ev[4], st));
+    SLX_HIPCHK(hipEventRecord(fq->ev[4], st));
     for (int i = 0; i < 3; ++i) {
-        FQ_CHK(offs[i]->ensure(8 * (N + 1)));
-        FQ_CHK(fq_scan(fq, per8[i]->as<fq_u64>(), offs[i]->as<fq_u64>(), N + 1));
-        FQ_HIPCHK(hipMemcpyAsync(hs + i, offs[i]->as<fq_u64>() + N, 8, hipMemcpyDeviceToHost, st));
+        SLX_CHK(offs[i]->ensure(8 * (N + 1)));
+        SLX_CHK(fq_scan(fq, per8[i]->as<fq_u64>(), offs[i]->as<fq_u64>(), N + 1));
+        SLX_HIPCHK(hipMemcpyAsync(hs + i, offs[i]->as<fq_u64>() + N, 8, hipMemcpyDeviceToHost, st));
     }
-    FQ_HIPCHK(hipEventRecord(fq->ev[5], st));
-    FQ_HIPCHK(slx_wait_stream(st));
-    fq->us[1] += fq_ev_us(fq->ev[4], fq->ev[5]);
+    SLX_HIPCHK(hipEventRecord(fq->ev[5], st));
+    SLX_HIPCHK(slx_wait_stream(st));
+    fq->us[1] += slx_ev_us(fq->ev[4], fq->ev[5]);
     fq->tot_b = hs[0]; fq->tot_n = hs[1]; fq->tot_c = hs[2];
-    FQ_CHK(fq->d_bases.ensure(fq->tot_b + 64)); FQ_CHK(fq->d_quals.ensure(fq->tot_b + 64)); FQ_CHK(fq->d_names.ensure(fq->tot_n + 64)); FQ_CHK(fq->d_coms.ensure(fq->tot_c + 64));
+    SLX_CHK(fq->d_bases.ensure(fq->tot_b + 64)); SLX_CHK(fq->d_quals.ensure(fq->tot_b + 64)); SLX_CHK(fq->d_names.ensure(fq->tot_n + 64)); SLX_CHK(fq->d_coms.ensure(fq->tot_c + 64));
     const uint32_t gt = fq->gather_tile;
     auto gather = [&](FqDBuf &src, FqDBuf &off, uint64_t total, FqDBuf &dst) {
         if (!total) return;
         const uint64_t tiles = (total + gt - 1) / gt;
         k_fq_gather<<<(unsigned)((tiles + 3) / 4), 256, 0, st>>>(src.as<fq_u64>(), off.as<fq_u64>(), N, total, gt, dst.as<uint8_t>());
     };
-    FQ_HIPCHK(hipEventRecord(fq->ev[6], st));
+    SLX_HIPCHK(hipEventRecord(fq->ev[6], st));
     gather(fq->d_src_b, fq->d_off_b, fq->tot_b, fq->d_bases);
     gather(fq->d_src_q, fq->d_off_b, fq->tot_b, fq->d_quals);
     gather(fq->d_src_n, fq->d_off_n, fq->tot_n, fq->d_names);
     gather(fq->d_src_c, fq->d_off_c, fq->tot_c, fq->d_coms);
-    FQ_HIPCHK(hipGetLastError());
-    FQ_HIPCHK(hipEventRecord(fq->ev[7], st));
-    FQ_HIPCHK(slx_wait_stream(st));
-    fq->us[2] += fq_ev_us(fq->ev[6], fq->ev[7]);
+    SLX_HIPCHK(hipGetLastError());
+    SLX_HIPCHK(hipEventRecord(fq->ev[7], st));
+    SLX_HIPCHK(slx_wait_stream(st));
+    fq->us[2] += slx_ev_us(fq->ev[6], fq->ev[7]);
     return SLX_OK;
 }
 
@@ -535,19 +496,19 @@ extern "C" int slx_fastq_next(slx_fastq *fq, int64_t max_bytes, slx_fastq_batch 
     fq->last = *b;
     if (fq->done) return SLX_OK;
     if (max_bytes <= 0) max_bytes = 64ll << 20;
-    FQ_HIPCHK(hipSetDevice(fq->device));
+    SLX_HIPCHK(hipSetDevice(fq->device));
     hipStream_t st = fq->st;
     uint64_t target = (uint64_t)max_bytes, text_bytes = 0;
     for (;;) {
-        if (fq->used) FQ_CHK(fq_shift(fq, target));          // the cut tail moves to the front of the other buffer
-        if (fq->have < target && !fq->src_eof) FQ_CHK(fq_pull(fq, target - fq->have));
+        if (fq->used) SLX_CHK(fq_shift(fq, target));          // the cut tail moves to the front of the other buffer
+        if (fq->have < target && !fq->src_eof) SLX_CHK(fq_pull(fq, target - fq->have));
         if (fq->have == 0) {
             if (fq->src_eof) { fq->done = true; return SLX_OK; }
             continue;
         }
         int64_t n = 0, n_slow = 0;
         uint64_t consumed = 0;
-        FQ_CHK(fq_parse(fq, &n, &n_slow, &consumed));
+        SLX_CHK(fq_parse(fq, &n, &n_slow, &consumed));
         fq->used = consumed; text_bytes += consumed;
         if (n > 0) {
             b->n_reads = n; b->n_slow_reads = n_slow; b->n_text_bytes = (int64_t)text_bytes;
@@ -569,14 +530,14 @@ extern "C" int slx_fastq_to_host(slx_fastq *fq, const slx_fastq_batch *b, void *
 {
     if (!fq || !b) { slx_set_error("slx_fastq_to_host: null argument"); return SLX_EINVAL; }
     if (b->n_reads <= 0 || b->n_reads != fq->last.n_reads || b->d_bases != fq->last.d_bases || b->d_offs != fq->last.d_offs) { slx_set_error("slx_fastq_to_host: not the reader's last batch"); return SLX_EINVAL; }
-    FQ_HIPCHK(hipSetDevice(fq->device));
+    SLX_HIPCHK(hipSetDevice(fq->device));
     hipStream_t st = fq->st;
     const size_t n = (size_t)b->n_reads;
     auto down = [&](void *dst, const void *src, size_t bytes) { return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess; };
-    FQ_HIPCHK(down(offs, b->d_offs, 8 * (n + 1))); FQ_HIPCHK(down(name_offs, b->d_name_offs, 8 * (n + 1))); FQ_HIPCHK(down(com_offs, b->d_com_offs, 8 * (n + 1)));
-    FQ_HIPCHK(down(flags, b->d_flags, n));
-    FQ_HIPCHK(down(bases, b->d_bases, fq->tot_b)); FQ_HIPCHK(down(quals, b->d_quals, fq->tot_b));
-    FQ_HIPCHK(down(names, b->d_names, fq->tot_n)); FQ_HIPCHK(down(coms, b->d_coms, fq->tot_c));
-    FQ_HIPCHK(slx_wait_stream(st));
+    SLX_HIPCHK(down(offs, b->d_offs, 8 * (n + 1))); SLX_HIPCHK(down(name_offs, b->d_name_offs, 8 * (n + 1))); SLX_HIPCHK(down(com_offs, b->d_com_offs, 8 * (n + 1)));
+    SLX_HIPCHK(down(flags, b->d_flags, n));
+    SLX_HIPCHK(down(bases, b->d_bases, fq->tot_b)); SLX_HIPCHK(down(quals, b->d_quals, fq->tot_b));
+    SLX_HIPCHK(down(names, b->d_names, fq->tot_n)); SLX_HIPCHK(down(coms, b->d_coms, fq->tot_c));
+    SLX_HIPCHK(slx_wait_stream(st));
     return SLX_OK;
 }

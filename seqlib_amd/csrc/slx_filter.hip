@@ -16,9 +16,8 @@
 #include "slx_internal.h"
 #include "seqlib_amd_filter.h"
 #include "rfilter_host.h"
+#include "slx_hip.h"
 
-#define FLT_HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { slx_set_error("HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, __LINE__); return SLX_ENODEVICE; } } while (0)
-#define FLT_CHK(x) do { const int rc_ = (x); if (rc_ != SLX_OK) return rc_; } while (0)
 #define FLT_LDS_MAX 65536u
 
 // st: [0] records on the long list, [1] error bits, [2] kept records
@@ -70,22 +69,8 @@ __global__ __launch_bounds__(256) void k_flt_eval_long(const uint8_t *s, const u
 }
 
 // ------------------------------------------------------------------ host
-namespace {
-struct FltDBuf {
-    void *p = nullptr; size_t cap = 0;
-    int ensure(size_t n)
-    {
-        if (n <= cap) return SLX_OK;
-        const size_t want = n + n / 4 + 256;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        if (hipMalloc(&p, want) != hipSuccess) { (void)hipGetLastError(); p = nullptr; slx_set_error("read filter: cannot allocate %zu bytes of HBM", want); return SLX_ENOMEM; }
-        cap = want;
-        return SLX_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-}
+// a margin of 1/4 + 256 bytes on every growth: kept as found
+typedef SlxDevBuf<SlxMargin<4, 256>> FltDBuf;
 
 struct slx_filter {
     std::vector<RfHostFilter> filters;
@@ -194,7 +179,7 @@ static int flt_record_error(uint32_t bits)
 extern "C" int slx_filter_test_record(slx_filter *f, const uint8_t *rec, int64_t n)
 {
     if (!f || !rec || n < 0) { slx_set_error("slx_filter_test_record: null argument"); return SLX_EINVAL; }
-    FLT_CHK(flt_compile(f));
+    SLX_CHK(flt_compile(f));
     rf_feat F;
     const uint32_t er = n < 4 ? RF_E_FIELDS : rf_features(rec, (uint64_t)n, &f->C.tab, &F);
     if (er) return flt_record_error(er);
@@ -222,32 +207,26 @@ extern "C" int slx_filter_features(const uint8_t *rec, int64_t n, slx_filter_fea
     return SLX_OK;
 }
 
-static int flt_no_device()
-{
-    slx_set_error("no HIP device: the read filter evaluates batches on MI355X only (no CPU fallback)");
-    return SLX_ENODEVICE;
-}
-
 static int flt_upload(slx_filter *f, int device, hipStream_t st)
 {
-    FLT_CHK(flt_compile(f));
+    SLX_CHK(flt_compile(f));
     if (f->up_device == device) return SLX_OK;
     if (f->buf_device >= 0 && f->buf_device != device) {          // the buffers of another device go
-        FLT_HIPCHK(hipSetDevice(f->buf_device));
+        SLX_HIPCHK(hipSetDevice(f->buf_device));
         for (FltDBuf *b : {&f->d_flt, &f->d_rules, &f->d_regs, &f->d_strs, &f->d_dfa, &f->d_st, &f->d_long}) b->release();
-        FLT_HIPCHK(hipSetDevice(device));
+        SLX_HIPCHK(hipSetDevice(device));
     }
     f->up_device = -1; f->buf_device = device;
     const RfCompiled &C = f->C;
     auto up = [&](FltDBuf &b, const void *src, size_t bytes) -> int {
-        FLT_CHK(b.ensure(bytes + 16));
-        if (bytes) FLT_HIPCHK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st));
+        SLX_CHK(b.ensure(bytes + 16));
+        if (bytes) SLX_HIPCHK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st));
         return SLX_OK;
     };
-    FLT_CHK(up(f->d_flt, C.flt.data(), sizeof(rf_filter) * C.flt.size())); FLT_CHK(up(f->d_rules, C.rules.data(), sizeof(rf_rule) * C.rules.size()));
-    FLT_CHK(up(f->d_regs, C.regs.data(), sizeof(rf_reg) * C.regs.size())); FLT_CHK(up(f->d_strs, C.strs.data(), C.strs.size()));
-    FLT_CHK(up(f->d_dfa, C.dfa.data(), 4 * C.dfa.size())); FLT_CHK(f->d_st.ensure(16));
-    FLT_HIPCHK(hipStreamSynchronize(st));
+    SLX_CHK(up(f->d_flt, C.flt.data(), sizeof(rf_filter) * C.flt.size())); SLX_CHK(up(f->d_rules, C.rules.data(), sizeof(rf_rule) * C.rules.size()));
+    SLX_CHK(up(f->d_regs, C.regs.data(), sizeof(rf_reg) * C.regs.size())); SLX_CHK(up(f->d_strs, C.strs.data(), C.strs.size()));
+    SLX_CHK(up(f->d_dfa, C.dfa.data(), 4 * C.dfa.size())); SLX_CHK(f->d_st.ensure(16));
+    SLX_HIPCHK(hipStreamSynchronize(st));
     f->dtab = C.tab;
     f->dtab.flt = (const rf_filter *)f->d_flt.p; f->dtab.rules = (const rf_rule *)f->d_rules.p; f->dtab.regs = (const rf_reg *)f->d_regs.p;
     f->dtab.strs = (const uint8_t *)f->d_strs.p; f->dtab.dfa = (const uint32_t *)f->d_dfa.p;
@@ -260,35 +239,34 @@ int slx_filter_eval_device(slx_filter *f, int device, void *stream, const uint8_
     hipStream_t st = (hipStream_t)stream;
     if (n_kept) *n_kept = 0;
     if (n_rec >= 0xffffffffull) { slx_set_error("read filter: %llu records in one batch", (unsigned long long)n_rec); return SLX_EUNSUPPORTED; }
-    FLT_CHK(flt_upload(f, device, st));
+    SLX_CHK(flt_upload(f, device, st));
     if (n_rec == 0) return SLX_OK;
     if (n_bytes < 36 * n_rec) return flt_record_error(RF_E_FIELDS);
     if (f->ev_device != device) {
         for (auto &e : f->ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-        for (auto &e : f->ev) FLT_HIPCHK(hipEventCreate(&e));
+        for (auto &e : f->ev) SLX_HIPCHK(hipEventCreate(&e));
         f->ev_device = device;
     }
-    FLT_CHK(f->d_long.ensure(4 * (size_t)n_rec));
+    SLX_CHK(f->d_long.ensure(4 * (size_t)n_rec));
     uint32_t *d_st = (uint32_t *)f->d_st.p;
     const uint32_t W = f->window, V = f->overhang, stage = W + V + 16;
     const size_t dfa_bytes = 4 * f->C.dfa.size();
     const bool in_lds = dfa_bytes && stage + dfa_bytes <= FLT_LDS_MAX;
     const uint64_t n_win = (n_bytes + W - 1) / W;
     if (n_win >= 0x7fffffffull) { slx_set_error("read filter: %llu windows in one batch", (unsigned long long)n_win); return SLX_EUNSUPPORTED; }
-    FLT_HIPCHK(hipMemsetAsync(d_st, 0, 16, st));
-    FLT_HIPCHK(hipMemsetAsync(d_keep, 0, n_rec, st));
-    FLT_HIPCHK(hipEventRecord(f->ev[0], st));
+    SLX_HIPCHK(hipMemsetAsync(d_st, 0, 16, st));
+    SLX_HIPCHK(hipMemsetAsync(d_keep, 0, n_rec, st));
+    SLX_HIPCHK(hipEventRecord(f->ev[0], st));
     k_flt_eval<<<(unsigned)n_win, 256, stage + (in_lds ? dfa_bytes : 0), st>>>(s, rec, n_rec, n_bytes, W, V, f->dtab, in_lds ? (uint32_t)f->C.dfa.size() : 0u, d_keep, (uint32_t *)f->d_long.p, d_st);
-    FLT_HIPCHK(hipGetLastError());
+    SLX_HIPCHK(hipGetLastError());
     const uint64_t long_blocks = std::min<uint64_t>((n_rec + 3) / 4, 1024);
     k_flt_eval_long<<<(unsigned)long_blocks, 256, 0, st>>>(s, rec, n_rec, f->dtab, f->chunk_bases, d_keep, (const uint32_t *)f->d_long.p, d_st);
-    FLT_HIPCHK(hipGetLastError());
-    FLT_HIPCHK(hipEventRecord(f->ev[1], st));
+    SLX_HIPCHK(hipGetLastError());
+    SLX_HIPCHK(hipEventRecord(f->ev[1], st));
     uint32_t h[4] = {0, 0, 0, 0};
-    FLT_HIPCHK(hipMemcpyAsync(h, d_st, 16, hipMemcpyDeviceToHost, st));
-    FLT_HIPCHK(slx_wait_stream(st));
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, f->ev[0], f->ev[1]) == hipSuccess) f->us += ms * 1000.0;
+    SLX_HIPCHK(hipMemcpyAsync(h, d_st, 16, hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(slx_wait_stream(st));
+    f->us += slx_ev_us(f->ev[0], f->ev[1]);
     f->c_in_lds = in_lds; f->c_long += h[0];
     if (h[1]) return flt_record_error(h[1]);
     f->c_seen += (int64_t)n_rec; f->c_passed += h[2];
@@ -300,24 +278,20 @@ extern "C" int slx_filter_apply_device(slx_filter *f, int device, const void *d_
 {
     if (!f || n_records < 0 || (n_records && (!d_stream || !d_rec_off || !d_keep))) { slx_set_error("slx_filter_apply_device: null argument"); return SLX_EINVAL; }
     if (n_kept) *n_kept = 0;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return flt_no_device(); }
-    if (device < 0) { FLT_HIPCHK(hipGetDevice(&device)); }
-    if (device >= ndev) { slx_set_error("read filter: device %d is not one of the %d visible", device, ndev); return SLX_EINVAL; }
-    FLT_HIPCHK(hipSetDevice(device));
+    SLX_CHK(slx_pick_device(device, "no HIP device: the read filter evaluates batches on MI355X only (no CPU fallback)", "read filter", &device));
     if (f->own_device != device) {
         if (f->own) (void)hipStreamDestroy(f->own);
         f->own = nullptr;
-        FLT_HIPCHK(hipStreamCreateWithFlags(&f->own, hipStreamNonBlocking));
+        SLX_HIPCHK(hipStreamCreateWithFlags(&f->own, hipStreamNonBlocking));
         f->own_device = device;
     }
     uint64_t n_bytes = 0;
     if (n_records) {
-        FLT_HIPCHK(hipMemcpyAsync(&n_bytes, (const uint64_t *)d_rec_off + n_records, 8, hipMemcpyDeviceToHost, f->own));
-        FLT_HIPCHK(hipStreamSynchronize(f->own));
+        SLX_HIPCHK(hipMemcpyAsync(&n_bytes, (const uint64_t *)d_rec_off + n_records, 8, hipMemcpyDeviceToHost, f->own));
+        SLX_HIPCHK(hipStreamSynchronize(f->own));
     }
     uint64_t k = 0;
-    FLT_CHK(slx_filter_eval_device(f, device, f->own, (const uint8_t *)d_stream, (const uint64_t *)d_rec_off, (uint64_t)n_records, n_bytes, (uint8_t *)d_keep, &k));
+    SLX_CHK(slx_filter_eval_device(f, device, f->own, (const uint8_t *)d_stream, (const uint64_t *)d_rec_off, (uint64_t)n_records, n_bytes, (uint8_t *)d_keep, &k));
     if (n_kept) *n_kept = (int64_t)k;
     return SLX_OK;
 }
@@ -325,7 +299,7 @@ extern "C" int slx_filter_apply_device(slx_filter *f, int device, const void *d_
 extern "C" int slx_filter_attach(slx_filter *f, slx_bam *rd)
 {
     if (!rd) { slx_set_error("slx_filter_attach: reader is null"); return SLX_EINVAL; }
-    if (f) FLT_CHK(flt_compile(f));
+    if (f) SLX_CHK(flt_compile(f));
     slx_reader_set_filter(rd, f);
     return SLX_OK;
 }

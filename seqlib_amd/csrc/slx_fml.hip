@@ -64,15 +64,7 @@ void slx_fml_opt_adjust_window(slx_fml_opt *opt, int64_t n, uint64_t tot_len) { 
 extern "C" int slx_fml_create(int device, slx_fml **out)
 {
     if (!out) { slx_set_error("slx_fml_create: out is null"); return SLX_EINVAL; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        slx_set_error("no HIP device: the FermiAssembler / BFC path runs on MI355X only (no CPU fallback)");
-        return SLX_ENODEVICE;
-    }
-    if (device < 0) { FML_HIPCHK(hipGetDevice(&device)); }
-    if (device >= ndev) { slx_set_error("slx_fml_create: device %d is not one of the %d visible", device, ndev); return SLX_EINVAL; }
-    FML_HIPCHK(hipSetDevice(device));
+    SLX_CHK(slx_pick_device(device, "no HIP device: the FermiAssembler / BFC path runs on MI355X only (no CPU fallback)", "slx_fml_create", &device));
     slx_fml *f = new slx_fml();
     f->device = device;
     if (const char *e = getenv("SLX_FML_PART_MIN")) f->part_min_bases = atoll(e);       // test hook: batches of at least this many bases count by partitions
@@ -92,9 +84,8 @@ extern "C" void slx_fml_free(slx_fml *f)
 {
     if (!f) return;
     (void)hipSetDevice(f->device);
-    for (FmlDevBuf *b : f->all_bufs()) b->release();
-    if (f->h_text_pin) (void)hipHostFree(f->h_text_pin);
-    f->h_asm.release(); f->h_asm2.release();
+    for (FmlDBuf *b : f->all_bufs()) b->release();
+    f->h_text.release(); f->h_asm.release(); f->h_asm2.release();
     if (f->ev0) (void)hipEventDestroy(f->ev0);
     if (f->ev1) (void)hipEventDestroy(f->ev1);
     if (f->st_copy) (void)hipStreamDestroy(f->st_copy);
@@ -131,14 +122,12 @@ extern "C" int64_t slx_fml_counter(const slx_fml *f, const char *key)
     return -1;
 }
 
-int fml_probe_begin(slx_fml *f) { FML_HIPCHK(hipEventRecord(f->ev0, f->st)); return SLX_OK; }
+int fml_probe_begin(slx_fml *f) { SLX_HIPCHK(hipEventRecord(f->ev0, f->st)); return SLX_OK; }
 int fml_probe_end(slx_fml *f, int which)
 {
-    float ms = 0;
-    FML_HIPCHK(hipEventRecord(f->ev1, f->st));
-    FML_HIPCHK(hipEventSynchronize(f->ev1));
-    FML_HIPCHK(hipEventElapsedTime(&ms, f->ev0, f->ev1));
-    f->probe[which] += ms;
+    SLX_HIPCHK(hipEventRecord(f->ev1, f->st));
+    SLX_HIPCHK(hipEventSynchronize(f->ev1));
+    f->probe[which] += slx_ev_ms(f->ev0, f->ev1);
     return SLX_OK;
 }
 
@@ -163,10 +152,10 @@ int fml_upload(slx_fml *f, const char *bases, const char *quals, const uint64_t 
     int rc;
     if ((rc = f->d_bases.ensure((size_t)total + 64)) || (rc = f->d_offs.ensure(((size_t)n_reads + 1) * 8))) return rc;
     if (quals && (rc = f->d_quals.ensure((size_t)total + 64))) return rc;
-    if (total) FML_HIPCHK(hipMemcpyAsync(f->d_bases.p, bases + base0, total, hipMemcpyHostToDevice, f->st));
-    if (total && quals) FML_HIPCHK(hipMemcpyAsync(f->d_quals.p, quals + base0, total, hipMemcpyHostToDevice, f->st));
-    FML_HIPCHK(hipMemcpyAsync(f->d_offs.p, f->h_offs.data(), ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, f->st));
-    FML_HIPCHK(slx_wait_stream(f->st));          // h_offs may be rebuilt by the caller's next step
+    if (total) SLX_HIPCHK(hipMemcpyAsync(f->d_bases.p, bases + base0, total, hipMemcpyHostToDevice, f->st));
+    if (total && quals) SLX_HIPCHK(hipMemcpyAsync(f->d_quals.p, quals + base0, total, hipMemcpyHostToDevice, f->st));
+    SLX_HIPCHK(hipMemcpyAsync(f->d_offs.p, f->h_offs.data(), ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, f->st));
+    SLX_HIPCHK(slx_wait_stream(f->st));          // h_offs may be rebuilt by the caller's next step
     return SLX_OK;
 }
 
@@ -212,7 +201,7 @@ int fml_setup_windows(slx_fml *f, const slx_fml_opt *opt, const int64_t *win_off
     f->n_win = n_win; f->n_slots = slots; f->n_parts = parts;
     int rc;
     if ((rc = f->d_tab.ensure((size_t)std::max<uint64_t>(slots, 1) * sizeof(FmlSlot))) || (rc = f->d_wins.ensure(f->wins.size() * sizeof(FmlWin)))) return rc;
-    FML_HIPCHK(hipMemcpyAsync(f->d_wins.p, f->wins.data(), f->wins.size() * sizeof(FmlWin), hipMemcpyHostToDevice, f->st));
+    SLX_HIPCHK(hipMemcpyAsync(f->d_wins.p, f->wins.data(), f->wins.size() * sizeof(FmlWin), hipMemcpyHostToDevice, f->st));
     return SLX_OK;
 }
 
@@ -224,13 +213,13 @@ static int launch_hist(slx_fml *f)          // bfc_ch_hist of every window's tab
     if ((rc = f->d_hist.ensure((size_t)nw * 320 * 8))) return rc;
     f->h_hist.assign((size_t)nw * 320, 0);
     if ((rc = fml_probe_begin(f))) return rc;
-    FML_HIPCHK(hipMemsetAsync(f->d_hist.p, 0, (size_t)nw * 320 * 8, f->st));
+    SLX_HIPCHK(hipMemsetAsync(f->d_hist.p, 0, (size_t)nw * 320 * 8, f->st));
     if (f->n_slots) {
         hipLaunchKernelGGL(k_fml_hist, dim3((unsigned)((f->n_slots + 1023) / 1024)), dim3(256), 0, f->st, f->d_tab.as<FmlSlot>(), (unsigned long long)f->n_slots,
                            f->d_wins.as<FmlWin>(), f->n_win, f->d_hist.as<unsigned long long>());
-        FML_HIPCHK(hipGetLastError());
+        SLX_HIPCHK(hipGetLastError());
     }
-    FML_HIPCHK(hipMemcpyAsync(f->h_hist.data(), f->d_hist.p, (size_t)nw * 320 * 8, hipMemcpyDeviceToHost, f->st));
+    SLX_HIPCHK(hipMemcpyAsync(f->h_hist.data(), f->d_hist.p, (size_t)nw * 320 * 8, hipMemcpyDeviceToHost, f->st));
     return fml_probe_end(f, 1);
 }
 
@@ -245,13 +234,13 @@ static int pack_planes(slx_fml *f, int q, FmlPlanes *P)
     unsigned long long *p0 = pl, *p1 = pl + words, *pn = pl + 2 * words, *pq = pl + 3 * words, *ps = pl + 4 * words;
     *P = FmlPlanes{p0, p1, pn, pq, ps};
     if (f->planes_ok && f->planes_q == q) return SLX_OK;
-    FML_HIPCHK(hipMemsetAsync(pl, 0, words * 8 * 5, f->st));
-    FML_HIPCHK(hipMemsetAsync(pn, 0xff, 8, f->st));          // the guard block before the text: all N
+    SLX_HIPCHK(hipMemsetAsync(pl, 0, words * 8 * 5, f->st));
+    SLX_HIPCHK(hipMemsetAsync(pn, 0xff, 8, f->st));          // the guard block before the text: all N
     if (total > 0) {
         hipLaunchKernelGGL(k_fml_starts, dim3((unsigned)((f->n_reads + 255) / 256)), dim3(256), 0, f->st, f->d_offs.as<unsigned long long>(), (long long)f->n_reads, ps);
         hipLaunchKernelGGL(k_fml_pack, dim3((unsigned)((nblk + 3) / 4)), dim3(256), 0, f->st, f->d_bases.as<char>(), f->has_qual ? f->d_quals.as<char>() : nullptr,
                            (long long)total, q, p0, p1, pn, pq);
-        FML_HIPCHK(hipGetLastError());
+        SLX_HIPCHK(hipGetLastError());
     }
     f->planes_ok = true; f->planes_q = q;
     return SLX_OK;
@@ -265,28 +254,28 @@ static int run_count_once(slx_fml *f, int q, bool *too_small)
     if ((rc = fml_probe_begin(f))) return rc;
     FmlPlanes P;
     if ((rc = pack_planes(f, q, &P))) return rc;
-    FML_HIPCHK(hipMemsetAsync(f->d_tab.p, 0, (size_t)std::max<uint64_t>(f->n_slots, 1) * sizeof(FmlSlot), f->st));
-    FML_HIPCHK(hipMemsetAsync(f->d_stats.p, 0, 256, f->st));
+    SLX_HIPCHK(hipMemsetAsync(f->d_tab.p, 0, (size_t)std::max<uint64_t>(f->n_slots, 1) * sizeof(FmlSlot), f->st));
+    SLX_HIPCHK(hipMemsetAsync(f->d_stats.p, 0, 256, f->st));
     if (total > 0) {
         // large batches: bin the k-mers into partitions, count each partition in LDS, insert every distinct k-mer once (dev_fml.h: overflowing items spill
         // straight into the table); small batches: one contended atomic per k-mer
         bool by_parts = f->part_ok && f->n_parts > 0 && total >= f->part_min_bases &&
                         f->d_cursor.ensure((size_t)f->n_parts * 4 + 64) == SLX_OK && f->d_items.ensure((size_t)f->n_parts * FML_PART_CAP * 8 + 64) == SLX_OK;
         if (by_parts) {
-            FML_HIPCHK(hipMemsetAsync(f->d_cursor.p, 0, (size_t)f->n_parts * 4 + 64, f->st));
+            SLX_HIPCHK(hipMemsetAsync(f->d_cursor.p, 0, (size_t)f->n_parts * 4 + 64, f->st));
             hipLaunchKernelGGL(k_fml_bin, dim3((unsigned)((total + FML_BIN_TILE - 1) / FML_BIN_TILE)), dim3(256), 0, f->st, P, (long long)total, f->d_wins.as<FmlWin>(), f->n_win,
                                f->d_cursor.as<unsigned int>(), f->d_items.as<unsigned long long>(), f->d_tab.as<FmlSlot>(), f->d_stats.as<unsigned long long>());
             hipLaunchKernelGGL(k_fml_part, dim3(f->n_parts), dim3(256), 0, f->st, (const unsigned int *)f->d_cursor.as<unsigned int>(), (const unsigned long long *)f->d_items.as<unsigned long long>(),
                                f->d_wins.as<FmlWin>(), f->n_win, f->d_tab.as<FmlSlot>(), f->d_stats.as<unsigned long long>());
-            FML_HIPCHK(hipGetLastError());
+            SLX_HIPCHK(hipGetLastError());
         }
         if (!by_parts)
         hipLaunchKernelGGL(k_fml_count, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, f->st, P, (long long)total, f->d_offs.as<unsigned long long>(), (long long)f->n_reads,
                            f->d_wins.as<FmlWin>(), f->n_win, f->d_tab.as<FmlSlot>(), f->d_stats.as<unsigned long long>());
-        FML_HIPCHK(hipGetLastError());
+        SLX_HIPCHK(hipGetLastError());
     }
     unsigned long long st[2] = {0, 0};
-    FML_HIPCHK(hipMemcpyAsync(st, f->d_stats.p, 16, hipMemcpyDeviceToHost, f->st));
+    SLX_HIPCHK(hipMemcpyAsync(st, f->d_stats.p, 16, hipMemcpyDeviceToHost, f->st));
     if ((rc = fml_probe_end(f, 0))) return rc;
     *too_small = st[1] != 0;
     if (*too_small) return SLX_OK;
@@ -327,7 +316,7 @@ int fml_run_count(slx_fml *f, int q)
         }
         f->n_slots = slots;
         if ((rc = f->d_tab.ensure((size_t)std::max<uint64_t>(slots, 1) * sizeof(FmlSlot)))) return rc;
-        FML_HIPCHK(hipMemcpyAsync(f->d_wins.p, f->wins.data(), f->wins.size() * sizeof(FmlWin), hipMemcpyHostToDevice, f->st));
+        SLX_HIPCHK(hipMemcpyAsync(f->d_wins.p, f->wins.data(), f->wins.size() * sizeof(FmlWin), hipMemcpyHostToDevice, f->st));
     }
 }
 
@@ -354,7 +343,7 @@ int fml_run_hist(slx_fml *f, bool bfc_class)
         f->wins[(size_t)w].mode = mode; f->wins[(size_t)w].min_cov = min_cov;
         f->kcov[(size_t)w] = kcov;
     }
-    FML_HIPCHK(hipMemcpyAsync(f->d_wins.p, f->wins.data(), f->wins.size() * sizeof(FmlWin), hipMemcpyHostToDevice, f->st));
+    SLX_HIPCHK(hipMemcpyAsync(f->d_wins.p, f->wins.data(), f->wins.size() * sizeof(FmlWin), hipMemcpyHostToDevice, f->st));
     return SLX_OK;
 }
 
@@ -385,11 +374,11 @@ int fml_run_ec(slx_fml *f)
     if ((rc = pack_planes(f, f->last_q, &P))) return rc;
     hipLaunchKernelGGL(k_fml_occ, dim3((unsigned)((f->total + 255) / 256)), dim3(256), 0, f->st, P, (long long)f->total, f->d_wins.as<FmlWin>(), f->n_win,
                        (const FmlSlot *)f->d_tab.as<FmlSlot>(), f->d_occ.as<unsigned short>());
-    FML_HIPCHK(hipMemsetAsync(f->d_misc.p, 0, 256, f->st));
+    SLX_HIPCHK(hipMemsetAsync(f->d_misc.p, 0, 256, f->st));
     hipLaunchKernelGGL(k_fml_ec, dim3((unsigned)(lanes / 256)), dim3(256), 0, f->st, f->d_tab.as<FmlSlot>(), f->d_wins.as<FmlWin>(), f->n_win, ec_opt(f->last_q),
                        f->d_bases.as<char>(), f->has_qual ? f->d_quals.as<char>() : nullptr, f->d_offs.as<unsigned long long>(), (long long)f->n_reads,
                        (const unsigned short *)f->d_occ.as<unsigned short>(), f->d_scratch.as<unsigned char>(), lane_bytes, f->max_len, f->d_misc.as<unsigned long long>(), (int *)nullptr);
-    FML_HIPCHK(hipGetLastError());
+    SLX_HIPCHK(hipGetLastError());
     f->planes_ok = false;          // (the text has changed under the planes)
     return fml_probe_end(f, 2);
 }
@@ -406,29 +395,29 @@ int fml_run_streak(slx_fml *f)
     FmlPlanes P;
     if ((rc = pack_planes(f, f->last_q, &P))) return rc;
     unsigned long long *pm = f->d_occ.as<unsigned long long>();
-    FML_HIPCHK(hipMemsetAsync(pm, 0, 8, f->st));          // (the guard word before the text)
+    SLX_HIPCHK(hipMemsetAsync(pm, 0, 8, f->st));          // (the guard word before the text)
     hipLaunchKernelGGL(k_fml_multi, dim3((unsigned)((nblk + 3) / 4)), dim3(256), 0, f->st, P, (long long)f->total, f->d_wins.as<FmlWin>(), f->n_win, (const FmlSlot *)f->d_tab.as<FmlSlot>(), pm);
     hipLaunchKernelGGL(k_fml_streak, dim3((unsigned)((f->n_reads + 255) / 256)), dim3(256), 0, f->st, (const unsigned long long *)pm, f->d_wins.as<FmlWin>(), f->n_win,
                        f->d_offs.as<unsigned long long>(), (long long)f->n_reads, .8f, f->d_ns.as<int>(), f->d_nl.as<int>());
-    FML_HIPCHK(hipGetLastError());
+    SLX_HIPCHK(hipGetLastError());
     return fml_probe_end(f, 3);
 }
 
 static int download_text(slx_fml *f, char *bases, char *quals, const uint64_t *offs)
 {
     if (!f->total) return SLX_OK;
-    FML_HIPCHK(hipMemcpyAsync(bases + offs[0], f->d_bases.p, (size_t)f->total, hipMemcpyDeviceToHost, f->st));
-    if (quals && f->has_qual) FML_HIPCHK(hipMemcpyAsync(quals + offs[0], f->d_quals.p, (size_t)f->total, hipMemcpyDeviceToHost, f->st));
-    FML_HIPCHK(slx_wait_stream(f->st));
+    SLX_HIPCHK(hipMemcpyAsync(bases + offs[0], f->d_bases.p, (size_t)f->total, hipMemcpyDeviceToHost, f->st));
+    if (quals && f->has_qual) SLX_HIPCHK(hipMemcpyAsync(quals + offs[0], f->d_quals.p, (size_t)f->total, hipMemcpyDeviceToHost, f->st));
+    SLX_HIPCHK(slx_wait_stream(f->st));
     return SLX_OK;
 }
 
 static int download_trim(slx_fml *f, int32_t *new_start, int32_t *new_len)
 {
     if (!f->n_reads) return SLX_OK;
-    FML_HIPCHK(hipMemcpyAsync(new_start, f->d_ns.p, (size_t)f->n_reads * 4, hipMemcpyDeviceToHost, f->st));
-    FML_HIPCHK(hipMemcpyAsync(new_len, f->d_nl.p, (size_t)f->n_reads * 4, hipMemcpyDeviceToHost, f->st));
-    FML_HIPCHK(slx_wait_stream(f->st));
+    SLX_HIPCHK(hipMemcpyAsync(new_start, f->d_ns.p, (size_t)f->n_reads * 4, hipMemcpyDeviceToHost, f->st));
+    SLX_HIPCHK(hipMemcpyAsync(new_len, f->d_nl.p, (size_t)f->n_reads * 4, hipMemcpyDeviceToHost, f->st));
+    SLX_HIPCHK(slx_wait_stream(f->st));
     return SLX_OK;
 }
 
@@ -448,7 +437,7 @@ extern "C" int slx_fml_correct(slx_fml *f, const slx_fml_opt *opt, char *bases, 
     if (!f || !opt) { slx_set_error("slx_fml_correct: bad argument"); return SLX_EINVAL; }
     if (flt_uniq && (!new_start || !new_len)) { slx_set_error("slx_fml_correct: flt_uniq needs new_start / new_len"); return SLX_EINVAL; }
     std::lock_guard<std::mutex> g(f->mu);
-    FML_HIPCHK(hipSetDevice(f->device));
+    SLX_HIPCHK(hipSetDevice(f->device));
     f->reset_probes();
     int rc;
     if ((rc = fml_upload(f, bases, quals, offs, n_reads)) || (rc = fml_setup_windows(f, opt, win_off, n_win, 0))) return rc;
@@ -458,7 +447,7 @@ extern "C" int slx_fml_correct(slx_fml *f, const slx_fml_opt *opt, char *bases, 
     if ((rc = fml_correct_core_device(f, flt_uniq))) return rc;
     if (flt_uniq) { if ((rc = download_trim(f, new_start, new_len))) return rc; }
     else if ((rc = download_text(f, bases, quals, offs))) return rc;
-    FML_HIPCHK(slx_wait_stream(f->st));
+    SLX_HIPCHK(slx_wait_stream(f->st));
     for (int w = 0; w < n_win; ++w) {
         if (kcov) kcov[w] = f->kcov[(size_t)w];
         if (ec_k) ec_k[w] = f->wins[(size_t)w].k;
@@ -471,7 +460,7 @@ extern "C" int slx_fml_count(slx_fml *f, const char *bases, const char *quals, c
     if (!f) { slx_set_error("slx_fml_count: bad argument"); return SLX_EINVAL; }
     if (k < 1 || k > SLX_FML_MAX_K) { slx_set_error("slx_fml_count: k = %d: the k-mer tables take 1 <= k <= %d", k, SLX_FML_MAX_K); return k < 1 ? SLX_EINVAL : SLX_EUNSUPPORTED; }
     std::lock_guard<std::mutex> g(f->mu);
-    FML_HIPCHK(hipSetDevice(f->device));
+    SLX_HIPCHK(hipSetDevice(f->device));
     f->reset_probes();
     slx_fml_opt o;
     slx_fml_opt_init(&o);
@@ -479,7 +468,7 @@ extern "C" int slx_fml_count(slx_fml *f, const char *bases, const char *quals, c
     int rc;
     f->have_count = false;
     if ((rc = fml_upload(f, bases, quals, offs, n_reads)) || (rc = fml_setup_windows(f, &o, win_off, 1, k)) || (rc = fml_run_count(f, q))) return rc;
-    FML_HIPCHK(slx_wait_stream(f->st));
+    SLX_HIPCHK(slx_wait_stream(f->st));
     f->have_count = true;
     f->count_win = f->wins[0];
     return SLX_OK;
@@ -489,10 +478,10 @@ extern "C" int slx_fml_count_hist(slx_fml *f, uint64_t cnt[256], uint64_t high[6
 {
     if (!f || !f->have_count) { slx_set_error("slx_fml_count_hist: no count table (call slx_fml_count first)"); return SLX_EINVAL; }
     std::lock_guard<std::mutex> g(f->mu);
-    FML_HIPCHK(hipSetDevice(f->device));
+    SLX_HIPCHK(hipSetDevice(f->device));
     int rc;
     if ((rc = fml_run_hist(f))) return rc;
-    FML_HIPCHK(slx_wait_stream(f->st));
+    SLX_HIPCHK(slx_wait_stream(f->st));
     for (int i = 0; i < 256; ++i) cnt[i] = f->h_hist[(size_t)i];
     for (int i = 0; i < 64; ++i) high[i] = f->h_hist[(size_t)256 + i];
     if (mode) *mode = f->wins[0].mode;
@@ -503,9 +492,9 @@ extern "C" int slx_fml_count_dump(slx_fml *f, uint64_t *keys, uint16_t *vals, ui
 {
     if (!f || !f->have_count || !n) { slx_set_error("slx_fml_count_dump: no count table"); return SLX_EINVAL; }
     std::lock_guard<std::mutex> g(f->mu);
-    FML_HIPCHK(hipSetDevice(f->device));
+    SLX_HIPCHK(hipSetDevice(f->device));
     const FmlWin w = f->wins[0];
-    FmlDevBuf dk, dv;
+    FmlDBuf dk, dv;
     int rc;
     if ((rc = dk.ensure((size_t)std::max<uint64_t>(cap, 1) * 8)) || (rc = dv.ensure((size_t)std::max<uint64_t>(cap, 1) * 2)) || (rc = f->d_misc.ensure(256))) { dk.release(); dv.release(); return rc; }
     hipError_t e = hipMemsetAsync(f->d_misc.p, 0, 256, f->st);
@@ -537,7 +526,7 @@ extern "C" int slx_fml_error_correct(slx_fml *f, const slx_fml_opt *opt, char *b
     if (!f || !opt || !f->have_count) { slx_set_error("slx_fml_error_correct: no count table (call slx_fml_count first)"); return SLX_EINVAL; }
     if (flt_uniq && (!new_start || !new_len)) { slx_set_error("slx_fml_error_correct: flt_uniq needs new_start / new_len"); return SLX_EINVAL; }
     std::lock_guard<std::mutex> g(f->mu);
-    FML_HIPCHK(hipSetDevice(f->device));
+    SLX_HIPCHK(hipSetDevice(f->device));
     f->reset_probes();
     int rc;
     // the table stays; the reads to correct replace the reads it was counted from
@@ -546,13 +535,13 @@ extern "C" int slx_fml_error_correct(slx_fml *f, const slx_fml_opt *opt, char *b
     f->wins[0].read0 = 0; f->wins[0].read1 = n_reads; f->wins[0].pos0 = 0;
     f->wopt.assign(1, *opt);
     f->n_win = 1;
-    FML_HIPCHK(hipMemcpyAsync(f->d_wins.p, f->wins.data(), sizeof(FmlWin), hipMemcpyHostToDevice, f->st));
+    SLX_HIPCHK(hipMemcpyAsync(f->d_wins.p, f->wins.data(), sizeof(FmlWin), hipMemcpyHostToDevice, f->st));
     if ((rc = fml_run_hist(f, true))) return rc;
     f->count_win.mode = f->wins[0].mode; f->count_win.min_cov = f->wins[0].min_cov;
     if ((rc = flt_uniq ? fml_run_streak(f) : fml_run_ec(f))) return rc;
     if (flt_uniq) { if ((rc = download_trim(f, new_start, new_len))) return rc; }
     else if ((rc = download_text(f, bases, quals, offs))) return rc;
-    FML_HIPCHK(slx_wait_stream(f->st));
+    SLX_HIPCHK(slx_wait_stream(f->st));
     if (kcov) *kcov = f->kcov[0];
     if (min_cov) *min_cov = f->wins[0].min_cov;
     return SLX_OK;

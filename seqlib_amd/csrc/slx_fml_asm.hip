@@ -95,7 +95,7 @@ int build_and_assemble(slx_fml *f, const std::vector<int> &h_ns, const std::vect
     const long long n_str = (long long)w_strs[(size_t)n_win];
     // one pinned stretch: strings | irr_off | rep | cnt | n_irr | contained
     const size_t ns_h = (size_t)n_str + 2;
-    if (f->h_asm.ensure(ns_h * (sizeof(FmlStr) + 8 + 4 + 4 + 4 + 1) + 256)) { slx_set_error("fml: out of pinned host memory (%lld strings)", n_str); return SLX_ENOMEM; }
+    SLX_CHK(f->h_asm.ensure(ns_h * (sizeof(FmlStr) + 8 + 4 + 4 + 4 + 1) + 256));
     FmlStr *const strs = (FmlStr *)f->h_asm.p;
     unsigned long long *const h_irroff = (unsigned long long *)(strs + ns_h);
     int *const h_rep = (int *)(h_irroff + ns_h);
@@ -121,22 +121,13 @@ int build_and_assemble(slx_fml *f, const std::vector<int> &h_ns, const std::vect
     const int min_match = n_win ? aw[0].min_match : 1;
     // the text comes back into a pinned buffer the context keeps (a fresh std::vector would be zero-filled and pageable: 240 MB of both for
     // eight 100 000-read windows)
-    if (f->h_text_cap < (size_t)text_len + 1) {
-        if (f->h_text_pin) { (void)hipHostFree(f->h_text_pin); f->h_text_pin = nullptr; f->h_text_cap = 0; }
-        const size_t want = (size_t)text_len + (size_t)text_len / 8 + 4096;
-        if (hipHostMalloc((void **)&f->h_text_pin, want, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            slx_set_error("fml: out of pinned host memory (%llu bytes)", (unsigned long long)want);
-            return SLX_ENOMEM;
-        }
-        f->h_text_cap = want;
-    }
-    unsigned char *const h_text = f->h_text_pin;
+    SLX_CHK(f->h_text.ensure((size_t)text_len));          // (an assembly without strings pins nothing: h_text stays null and nothing below reads it)
+    unsigned char *const h_text = f->h_text.as<unsigned char>();
     const FmlEdge *h_out = nullptr;
     unsigned long long n_out = 0;
     if (n_str > 0) {
         int rc;
-        FmlDevBuf &d_strs = f->d_tmp0, &d_text = f->d_tmp1, &d_keys = f->d_tmp2, &d_vals = f->d_tmp3, &d_sort = f->d_tmp4, &d_graph = f->d_tmp5;
+        FmlDBuf &d_strs = f->d_tmp0, &d_text = f->d_tmp1, &d_keys = f->d_tmp2, &d_vals = f->d_tmp3, &d_sort = f->d_tmp4, &d_graph = f->d_tmp5;
         // d_graph: rep | cnt | cur | n_irr | irr_off | str_off | eoff | contained, one allocation
         const size_t ns = (size_t)n_str + 2;
         const size_t g_bytes = ns * (4 + 4 + 4 + 4 + 8 + 8 + 8 + 1) + 256;
@@ -149,21 +140,21 @@ int build_and_assemble(slx_fml *f, const std::vector<int> &h_ns, const std::vect
         unsigned long long *keys_in = d_keys.as<unsigned long long>(), *keys_out = keys_in + ns;
         unsigned int *vals_in = d_vals.as<unsigned int>(), *vals_out = vals_in + ns;
         if ((rc = fml_probe_begin(f))) return rc;
-        FML_HIPCHK(hipMemcpyAsync(d_strs.p, strs, (size_t)n_str * sizeof(FmlStr), hipMemcpyHostToDevice, f->st));
-        FML_HIPCHK(hipMemsetAsync(d_cnt, 0, ns * 4 * 3, f->st));          // cnt, cur, n_irr
-        FML_HIPCHK(hipMemsetAsync(f->d_misc.p, 0, 256, f->st));
+        SLX_HIPCHK(hipMemcpyAsync(d_strs.p, strs, (size_t)n_str * sizeof(FmlStr), hipMemcpyHostToDevice, f->st));
+        SLX_HIPCHK(hipMemsetAsync(d_cnt, 0, ns * 4 * 3, f->st));          // cnt, cur, n_irr
+        SLX_HIPCHK(hipMemsetAsync(f->d_misc.p, 0, 256, f->st));
         hipLaunchKernelGGL(k_asm_strings, dim3((unsigned)((n_str + 3) / 4)), dim3(256), 0, f->st, f->d_bases.as<char>(), d_strs.as<FmlStr>(), n_str, d_text.as<unsigned char>());
         // the text is final here and the graph stage on the host wants all of it (1.9 GB for 64 windows): it leaves on a stream of its own, under the sort, the join
         // and the reduction, instead of after them
-        FML_HIPCHK(hipEventRecord(f->ev_copy, f->st));
-        FML_HIPCHK(hipStreamWaitEvent(f->st_copy, f->ev_copy, 0));
-        FML_HIPCHK(hipMemcpyAsync(h_text, d_text.p, (size_t)text_len, hipMemcpyDeviceToHost, f->st_copy));
+        SLX_HIPCHK(hipEventRecord(f->ev_copy, f->st));
+        SLX_HIPCHK(hipStreamWaitEvent(f->st_copy, f->ev_copy, 0));
+        SLX_HIPCHK(hipMemcpyAsync(h_text, d_text.p, (size_t)text_len, hipMemcpyDeviceToHost, f->st_copy));
         hipLaunchKernelGGL(k_asm_keys, dim3((unsigned)((n_str + 255) / 256)), dim3(256), 0, f->st, d_text.as<unsigned char>(), d_strs.as<FmlStr>(), n_str, kk, keys_in, vals_in, d_rep, d_cont);
-        FML_HIPCHK(hipGetLastError());
+        SLX_HIPCHK(hipGetLastError());
         size_t tmp_bytes = 0;
-        FML_HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys_in, keys_out, vals_in, vals_out, (int)n_str, 0, 64, f->st));
+        SLX_HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys_in, keys_out, vals_in, vals_out, (int)n_str, 0, 64, f->st));
         if ((rc = d_sort.ensure(tmp_bytes + 256))) return rc;
-        FML_HIPCHK(hipcub::DeviceRadixSort::SortPairs(d_sort.p, tmp_bytes, keys_in, keys_out, vals_in, vals_out, (int)n_str, 0, 64, f->st));
+        SLX_HIPCHK(hipcub::DeviceRadixSort::SortPairs(d_sort.p, tmp_bytes, keys_in, keys_out, vals_in, vals_out, (int)n_str, 0, 64, f->st));
         // an index over the sorted keys (key -> first position), then
         // the join: overlaps as (u, v, length) triples; room for 40 per string at first (about the coverage), more when they do not fit
         unsigned long long *d_trin = f->d_misc.as<unsigned long long>(), *d_outn = d_trin + 1;
@@ -173,7 +164,7 @@ int build_and_assemble(slx_fml *f, const std::vector<int> &h_ns, const std::vect
         if ((rc = f->d_index.ensure(((size_t)hmask + 1) * 12))) return rc;
         unsigned long long *d_hkey = f->d_index.as<unsigned long long>();
         unsigned int *d_hval = (unsigned int *)(d_hkey + (size_t)hmask + 1);
-        FML_HIPCHK(hipMemsetAsync(d_hkey, 0, ((size_t)hmask + 1) * 8, f->st));
+        SLX_HIPCHK(hipMemsetAsync(d_hkey, 0, ((size_t)hmask + 1) * 8, f->st));
         hipLaunchKernelGGL(k_asm_index, dim3((unsigned)((n_str + 255) / 256)), dim3(256), 0, f->st, (const unsigned long long *)keys_out, n_str, d_hkey, d_hval, hmask);
         unsigned long long tri_cap = std::max<unsigned long long>(f->tri_per_str * (unsigned long long)n_str + (1u << 20), 1u << 20), n_tri = 0;
         int asm_cus = 256;
@@ -181,12 +172,12 @@ int build_and_assemble(slx_fml *f, const std::vector<int> &h_ns, const std::vect
         const unsigned grid_str = (unsigned)std::min<long long>((n_str + 3) / 4, (long long)asm_cus * 16);          // persistent waves: each keeps its own stretch of the output (dev_fml_asm.h)
         while (true) {
             if ((rc = f->d_tri.ensure((size_t)tri_cap * sizeof(FmlTriple)))) return rc;
-            FML_HIPCHK(hipMemsetAsync(f->d_misc.p, 0, 256, f->st));
+            SLX_HIPCHK(hipMemsetAsync(f->d_misc.p, 0, 256, f->st));
             hipLaunchKernelGGL(k_asm_join, dim3(grid_str), dim3(256), 0, f->st, d_text.as<unsigned char>(), d_strs.as<FmlStr>(), n_str, kk, min_match, keys_out, vals_out,
                                (const unsigned long long *)d_hkey, (const unsigned int *)d_hval, hmask, d_rep, d_cont, d_cnt, f->d_tri.as<FmlTriple>(), tri_cap, d_trin);
-            FML_HIPCHK(hipGetLastError());
-            FML_HIPCHK(hipMemcpyAsync(&n_tri, d_trin, 8, hipMemcpyDeviceToHost, f->st));
-            FML_HIPCHK(slx_wait_stream(f->st));
+            SLX_HIPCHK(hipGetLastError());
+            SLX_HIPCHK(hipMemcpyAsync(&n_tri, d_trin, 8, hipMemcpyDeviceToHost, f->st));
+            SLX_HIPCHK(slx_wait_stream(f->st));
             if (n_tri <= tri_cap) break;
             tri_cap = n_tri + n_tri / 8;          // (the marks of containment and the counts are idempotent: the join simply runs again)
             f->tri_per_str = std::max<unsigned long long>(f->tri_per_str, tri_cap / (unsigned long long)n_str + 1);
@@ -194,17 +185,14 @@ int build_and_assemble(slx_fml *f, const std::vector<int> &h_ns, const std::vect
         // where a vertex's overlaps start: the exclusive sum of the counts, on the device (cnt[n_str] = 0: entry n_str of the sum is the number of edges)
         unsigned long long n_edges = 0;
         {
-            size_t sb = 0;
             hipcub::TransformInputIterator<unsigned long long, FmlWiden, const unsigned int *> cnt64((const unsigned int *)d_cnt, FmlWiden());          // (sums in 64 bits)
-            FML_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, cnt64, d_eoff, (int)(n_str + 1), f->st));
-            if ((rc = d_sort.ensure(sb + 256))) return rc;
-            FML_HIPCHK(hipcub::DeviceScan::ExclusiveSum(d_sort.p, sb, cnt64, d_eoff, (int)(n_str + 1), f->st));
-            FML_HIPCHK(hipMemcpyAsync(&n_edges, d_eoff + n_str, 8, hipMemcpyDeviceToHost, f->st));
-            FML_HIPCHK(hipMemcpyAsync(h_cnt, d_cnt, (size_t)n_str * 4, hipMemcpyDeviceToHost, f->st));          // (for the counters, read at the end)
-            FML_HIPCHK(slx_wait_stream(f->st));
+            SLX_CHK(slx_exclusive_sum(d_sort, cnt64, d_eoff, (size_t)n_str + 1, f->st, 256));
+            SLX_HIPCHK(hipMemcpyAsync(&n_edges, d_eoff + n_str, 8, hipMemcpyDeviceToHost, f->st));
+            SLX_HIPCHK(hipMemcpyAsync(h_cnt, d_cnt, (size_t)n_str * 4, hipMemcpyDeviceToHost, f->st));          // (for the counters, read at the end)
+            SLX_HIPCHK(slx_wait_stream(f->st));
         }
         // edges grouped by source | sorted copy (vertices with > 64 overlaps) | irreducible edges | flags | list of those vertices
-        FmlDevBuf &d_edges = f->d_scratch;
+        FmlDBuf &d_edges = f->d_scratch;
         // (e_out: a wave of k_asm_reduce that meets a vertex with more kept edges than its stretch has left abandons the rest of it -- up to 63 of FML_OUT_CHUNK = 128
         // slots per stretch, so reserved slots stay below 128 / 65 x kept edges --, and leaves most of its last stretch unused; n_out is checked after the launches)
         const unsigned long long out_cap = 2 * (n_edges + 1) + (unsigned long long)grid_str * 4 * FML_OUT_CHUNK;
@@ -217,18 +205,18 @@ int build_and_assemble(slx_fml *f, const std::vector<int> &h_ns, const std::vect
                                (const unsigned long long *)d_eoff, d_cur, e_raw);
         hipLaunchKernelGGL(k_asm_reduce, dim3(grid_str), dim3(256), 0, f->st, d_text.as<unsigned char>(), d_strs.as<FmlStr>(), n_str, (const unsigned long long *)d_eoff,
                            (const unsigned int *)d_cur, (const FmlEdge *)e_raw, d_nirr, d_irroff, e_out, d_outn, big_list, d_nbig);
-        FML_HIPCHK(hipGetLastError());
+        SLX_HIPCHK(hipGetLastError());
         int big_cap = FML_BIG_CAP;          // SLX_FML_BIG_CAP: test hook, sends smaller lists down the through-memory path
         if (const char *e = getenv("SLX_FML_BIG_CAP")) { const int v = atoi(e); if (v >= 64 && v < FML_BIG_CAP) big_cap = v; }
         unsigned int n_big = 0, n_huge = 0;
-        FML_HIPCHK(hipMemcpyAsync(&n_big, d_nbig, 4, hipMemcpyDeviceToHost, f->st));
-        FML_HIPCHK(slx_wait_stream(f->st));
+        SLX_HIPCHK(hipMemcpyAsync(&n_big, d_nbig, 4, hipMemcpyDeviceToHost, f->st));
+        SLX_HIPCHK(slx_wait_stream(f->st));
         if (n_big) {
             hipLaunchKernelGGL(k_asm_reduce_big, dim3(n_big), dim3(256), 0, f->st, d_text.as<unsigned char>(), d_strs.as<FmlStr>(), (const int *)big_list, (const unsigned int *)d_nbig,
                                (const unsigned long long *)d_eoff, (const unsigned int *)d_cur, (const FmlEdge *)e_raw, d_nirr, d_irroff, e_out, d_outn, huge_list, d_nhuge, big_cap);
-            FML_HIPCHK(hipGetLastError());
-            FML_HIPCHK(hipMemcpyAsync(&n_huge, d_nhuge, 4, hipMemcpyDeviceToHost, f->st));
-            FML_HIPCHK(slx_wait_stream(f->st));
+            SLX_HIPCHK(hipGetLastError());
+            SLX_HIPCHK(hipMemcpyAsync(&n_huge, d_nhuge, 4, hipMemcpyDeviceToHost, f->st));
+            SLX_HIPCHK(slx_wait_stream(f->st));
             if (n_huge) {
                 const dim3 hg(n_huge, FML_HUGE_SLICES);
                 hipLaunchKernelGGL(k_asm_huge_rank, hg, dim3(256), 0, f->st, (const int *)huge_list, (const unsigned long long *)d_eoff, (const unsigned int *)d_cur, (const FmlEdge *)e_raw, e_sorted);
@@ -237,22 +225,22 @@ int build_and_assemble(slx_fml *f, const std::vector<int> &h_ns, const std::vect
                                    (const unsigned int *)d_cur, (const FmlEdge *)e_sorted, e_flags);
                 hipLaunchKernelGGL(k_asm_huge_emit, dim3((n_huge + 3) / 4), dim3(256), 0, f->st, (const int *)huge_list, (const unsigned int *)d_nhuge, (const unsigned long long *)d_eoff,
                                    (const unsigned int *)d_cur, (const FmlEdge *)e_sorted, (const unsigned char *)e_flags, d_nirr, d_irroff, e_out, d_outn);
-                FML_HIPCHK(hipGetLastError());
+                SLX_HIPCHK(hipGetLastError());
             }
         }
         if (times) { (void)slx_wait_stream(f->st); tm_gpu = ms_since(tm0); }
-        FML_HIPCHK(hipMemcpyAsync(&n_out, d_outn, 8, hipMemcpyDeviceToHost, f->st));
-        FML_HIPCHK(hipMemcpyAsync(h_rep, d_rep, (size_t)n_str * 4, hipMemcpyDeviceToHost, f->st));
-        FML_HIPCHK(hipMemcpyAsync(h_cont, d_cont, (size_t)n_str, hipMemcpyDeviceToHost, f->st));
-        FML_HIPCHK(hipMemcpyAsync(h_nirr, d_nirr, (size_t)n_str * 4, hipMemcpyDeviceToHost, f->st));
-        FML_HIPCHK(hipMemcpyAsync(h_irroff, d_irroff, (size_t)n_str * 8, hipMemcpyDeviceToHost, f->st));
+        SLX_HIPCHK(hipMemcpyAsync(&n_out, d_outn, 8, hipMemcpyDeviceToHost, f->st));
+        SLX_HIPCHK(hipMemcpyAsync(h_rep, d_rep, (size_t)n_str * 4, hipMemcpyDeviceToHost, f->st));
+        SLX_HIPCHK(hipMemcpyAsync(h_cont, d_cont, (size_t)n_str, hipMemcpyDeviceToHost, f->st));
+        SLX_HIPCHK(hipMemcpyAsync(h_nirr, d_nirr, (size_t)n_str * 4, hipMemcpyDeviceToHost, f->st));
+        SLX_HIPCHK(hipMemcpyAsync(h_irroff, d_irroff, (size_t)n_str * 8, hipMemcpyDeviceToHost, f->st));
         if ((rc = fml_probe_end(f, 4))) return rc;          // synchronises
-        FML_HIPCHK(slx_wait_stream(f->st_copy));
+        SLX_HIPCHK(slx_wait_stream(f->st_copy));
         if (n_out > out_cap) { slx_set_error("fml: the reduction reserved %llu edge slots, %llu were sized (internal)", n_out, out_cap); return SLX_EINTERNAL; }
         // the edges, then (filled per window below) their targets and lengths as the graph stage wants them: edges | edge_v | edge_len
-        if (f->h_asm2.ensure(((size_t)n_out + 1) * (sizeof(FmlEdge) + 8) + 256)) { slx_set_error("fml: out of pinned host memory (%llu edges)", n_out); return SLX_ENOMEM; }
+        SLX_CHK(f->h_asm2.ensure(((size_t)n_out + 1) * (sizeof(FmlEdge) + 8) + 256));
         h_out = (const FmlEdge *)f->h_asm2.p;
-        if (n_out) FML_HIPCHK(hipMemcpy(f->h_asm2.p, e_out, (size_t)n_out * sizeof(FmlEdge), hipMemcpyDeviceToHost));
+        if (n_out) SLX_HIPCHK(hipMemcpy(f->h_asm2.p, e_out, (size_t)n_out * sizeof(FmlEdge), hipMemcpyDeviceToHost));
         {   // (n_tri and n_out count reserved slots, some unused: the counters are the sums of the per-string counts)
             std::vector<unsigned long long> po((size_t)n_win, 0), pi((size_t)n_win, 0);
             over_windows([&](int w) {
@@ -269,7 +257,7 @@ int build_and_assemble(slx_fml *f, const std::vector<int> &h_ns, const std::vect
     tm_down = ms_since(tm0);
     // ---- per window on the host: chains, cleaning, records -- the windows are independent, so they go over the host's CPUs
     const auto t0 = std::chrono::steady_clock::now();
-    if (!h_out) { if (f->h_asm2.ensure(256)) { slx_set_error("fml: out of pinned host memory"); return SLX_ENOMEM; } h_out = (const FmlEdge *)f->h_asm2.p; }
+    if (!h_out) { SLX_CHK(f->h_asm2.ensure(256)); h_out = (const FmlEdge *)f->h_asm2.p; }
     int *const ev = (int *)((FmlEdge *)f->h_asm2.p + n_out + 1), *const el = ev + n_out + 1;
     std::atomic<int> next_win(0);
     auto work = [&]() {
@@ -328,10 +316,10 @@ static int assemble_resident(slx_fml *f, const slx_fml_opt *opt, const int64_t *
     if (getenv("SLX_FML_TIMES")) { (void)slx_wait_stream(f->st); fprintf(stderr, "[fml times] correct + filter on the device: %.1f ms wall\n", std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - tm0).count()); }
     std::vector<int> ns((size_t)n_reads + 1), nl((size_t)n_reads + 1);
     if (n_reads) {
-        FML_HIPCHK(hipMemcpyAsync(ns.data(), f->d_ns.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, f->st));
-        FML_HIPCHK(hipMemcpyAsync(nl.data(), f->d_nl.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, f->st));
+        SLX_HIPCHK(hipMemcpyAsync(ns.data(), f->d_ns.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, f->st));
+        SLX_HIPCHK(hipMemcpyAsync(nl.data(), f->d_nl.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, f->st));
     }
-    FML_HIPCHK(slx_wait_stream(f->st));
+    SLX_HIPCHK(slx_wait_stream(f->st));
     std::vector<slx_fml_opt> wopt(f->wopt);
     for (int w = 0; w < n_win; ++w) {
         slx_magopt &m = wopt[(size_t)w].mag_opt;
@@ -360,7 +348,7 @@ extern "C" int slx_fml_assemble(slx_fml *f, const slx_fml_opt *opt, const char *
     int rc;
     if ((rc = check_assemble_args(f, opt, utgs, n_utg, n_win))) return rc;
     std::lock_guard<std::mutex> g(f->mu);
-    FML_HIPCHK(hipSetDevice(f->device));
+    SLX_HIPCHK(hipSetDevice(f->device));
     f->reset_probes();
     f->have_count = false; f->staged = false;
     if ((rc = fml_upload(f, bases, quals, offs, n_reads))) return rc;
@@ -371,16 +359,16 @@ extern "C" int slx_fml_stage(slx_fml *f, const char *bases, const char *quals, c
 {
     if (!f) { slx_set_error("slx_fml_stage: bad argument"); return SLX_EINVAL; }
     std::lock_guard<std::mutex> g(f->mu);
-    FML_HIPCHK(hipSetDevice(f->device));
+    SLX_HIPCHK(hipSetDevice(f->device));
     f->have_count = false; f->staged = false;
     int rc;
     if ((rc = fml_upload(f, bases, quals, offs, n_reads))) return rc;
     if ((rc = f->d_bases0.ensure((size_t)f->total + 64)) || (f->has_qual && (rc = f->d_quals0.ensure((size_t)f->total + 64)))) return rc;
     if (f->total) {
-        FML_HIPCHK(hipMemcpyAsync(f->d_bases0.p, f->d_bases.p, (size_t)f->total, hipMemcpyDeviceToDevice, f->st));
-        if (f->has_qual) FML_HIPCHK(hipMemcpyAsync(f->d_quals0.p, f->d_quals.p, (size_t)f->total, hipMemcpyDeviceToDevice, f->st));
+        SLX_HIPCHK(hipMemcpyAsync(f->d_bases0.p, f->d_bases.p, (size_t)f->total, hipMemcpyDeviceToDevice, f->st));
+        if (f->has_qual) SLX_HIPCHK(hipMemcpyAsync(f->d_quals0.p, f->d_quals.p, (size_t)f->total, hipMemcpyDeviceToDevice, f->st));
     }
-    FML_HIPCHK(slx_wait_stream(f->st));
+    SLX_HIPCHK(slx_wait_stream(f->st));
     f->staged = true;
     return SLX_OK;
 }
@@ -391,12 +379,12 @@ extern "C" int slx_fml_assemble_staged(slx_fml *f, const slx_fml_opt *opt, const
     if ((rc = check_assemble_args(f, opt, utgs, n_utg, n_win))) return rc;
     std::lock_guard<std::mutex> g(f->mu);
     if (!f->staged) { slx_set_error("slx_fml_assemble_staged: no staged reads (slx_fml_stage first)"); return SLX_EINVAL; }
-    FML_HIPCHK(hipSetDevice(f->device));
+    SLX_HIPCHK(hipSetDevice(f->device));
     f->reset_probes();
     f->have_count = false; f->planes_ok = false;
     if (f->total) {          // the correction rewrites the working copy: start from the staged reads every time
-        FML_HIPCHK(hipMemcpyAsync(f->d_bases.p, f->d_bases0.p, (size_t)f->total, hipMemcpyDeviceToDevice, f->st));
-        if (f->has_qual) FML_HIPCHK(hipMemcpyAsync(f->d_quals.p, f->d_quals0.p, (size_t)f->total, hipMemcpyDeviceToDevice, f->st));
+        SLX_HIPCHK(hipMemcpyAsync(f->d_bases.p, f->d_bases0.p, (size_t)f->total, hipMemcpyDeviceToDevice, f->st));
+        if (f->has_qual) SLX_HIPCHK(hipMemcpyAsync(f->d_quals.p, f->d_quals0.p, (size_t)f->total, hipMemcpyDeviceToDevice, f->st));
     }
     return assemble_resident(f, opt, win_off, n_win, utgs, n_utg);
 }
@@ -407,7 +395,7 @@ extern "C" int slx_fml_direct_assemble(slx_fml *f, slx_fml_opt *opt, float kcov,
     int rc;
     if ((rc = check_assemble_opt(opt))) return rc;
     std::lock_guard<std::mutex> g(f->mu);
-    FML_HIPCHK(hipSetDevice(f->device));
+    SLX_HIPCHK(hipSetDevice(f->device));
     f->reset_probes();
     f->have_count = false;
     *utgs = nullptr; *n_utg = 0;

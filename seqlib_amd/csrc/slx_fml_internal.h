@@ -6,53 +6,15 @@
 #include <mutex>
 #include <vector>
 #include "slx_internal.h"
+#include "slx_hip.h"
 #include "seqlib_amd_fml.h"
 #include "dev_fml.h"
 
-void slx_set_error(const char *fmt, ...);
-
-#define FML_HIPCHK(x)                                                                               \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) {                                                                     \
-            slx_set_error("HIP error %s at %s:%d (%s)", hipGetErrorString(e_), __FILE__, __LINE__, #x); \
-            return e_ == hipErrorOutOfMemory ? SLX_ENOMEM : SLX_ENODEVICE;                          \
-        }                                                                                           \
-    } while (0)
-
-struct FmlDevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes)
-    {
-        if (bytes <= cap) return SLX_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        const size_t want = bytes + bytes / 8 + 256;
-        FML_HIPCHK(hipMalloc(&p, want));
-        cap = want;
-        return SLX_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <typename T> T *as() const { return (T *)p; }
-};
-
+// the context's work areas in HBM: a margin of 1/8 + 256 bytes on every growth, as the aligner's (kept as found)
+typedef SlxDevBuf<SlxMargin<8, 256>> FmlDBuf;
 // host memory the context keeps between calls, pinned: what an assembly call hands to and takes from the device (a fresh std::vector per call is zero-filled
-// and pageable -- half a gigabyte of both for 64 windows -- and every copy into it goes through a staging buffer)
-struct FmlPinned {
-    void *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t n)
-    {
-        if (n <= cap) return 0;
-        if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
-        const size_t want = n + n / 8 + 4096;
-        if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return -1; }
-        cap = want;
-        return 0;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-};
+// and pageable -- half a gigabyte of both for 64 windows -- and every copy into it goes through a staging buffer).  1/8 + 4096: kept as found
+typedef SlxPinBuf<SlxMargin<8, 4096>> FmlHBuf;
 
 struct slx_fml {
     int device = 0;
@@ -68,9 +30,8 @@ struct slx_fml {
     int planes_q = -1;
     uint64_t n_slots = 0;
     std::vector<uint64_t> h_offs;          // rebased to 0
-    unsigned char *h_text_pin = nullptr;   // the assembly text on the host (pinned, kept between calls: 1 byte per base of both strands)
-    size_t h_text_cap = 0;
-    FmlPinned h_asm, h_asm2;                 // the string list and the per-string results of an assembly call; its edges
+    FmlHBuf h_text;                        // the assembly text on the host (kept between calls: 1 byte per base of both strands)
+    FmlHBuf h_asm, h_asm2;                 // the string list and the per-string results of an assembly call; its edges
     std::vector<FmlWin> wins;
     std::vector<slx_fml_opt> wopt;         // per window: the caller's options after fml_opt_adjust on the window's reads
     std::vector<float> kcov;
@@ -78,7 +39,7 @@ struct slx_fml {
     // BFC::Train's table, kept between calls
     bool have_count = false, staged = false;
     FmlWin count_win;
-    FmlDevBuf d_bases0, d_quals0, d_bases, d_quals, d_offs, d_planes, d_tab, d_wins, d_hist, d_scratch, d_misc, d_stats, d_tri, d_index, d_ns, d_nl, d_tmp0, d_tmp1, d_tmp2, d_tmp3, d_tmp4, d_tmp5, d_cursor, d_items, d_occ;
+    FmlDBuf d_bases0, d_quals0, d_bases, d_quals, d_offs, d_planes, d_tab, d_wins, d_hist, d_scratch, d_misc, d_stats, d_tri, d_index, d_ns, d_nl, d_tmp0, d_tmp1, d_tmp2, d_tmp3, d_tmp4, d_tmp5, d_cursor, d_items, d_occ;
     float probe[SLX_FML_N_PROBES] = {0, 0, 0, 0, 0, 0};
     int64_t n_inserted = 0, n_bases = 0, n_distinct = 0;
     bool use_part = true;                   // fml_count by partitions (k_fml_bin + k_fml_part) when the batch is large enough; SLX_FML_PART=0 turns it off
@@ -88,7 +49,7 @@ struct slx_fml {
     int tab_div = 8, tab_grow = 1;          // table slots = 2 x bases x tab_grow / tab_div, a power of two (adapts when a table fills up)
     int64_t n_overlaps = 0, n_irreducible = 0, asm_text_len = 0, n_big_vertices = 0, n_huge_vertices = 0, n_strings = 0;
     unsigned long long tri_per_str = 40;          // of the last assemble call
-    std::vector<FmlDevBuf *> all_bufs()
+    std::vector<FmlDBuf *> all_bufs()
     {
         return {&d_bases0, &d_quals0, &d_bases, &d_quals, &d_offs, &d_planes, &d_tab, &d_wins, &d_hist, &d_scratch, &d_misc, &d_stats, &d_tri, &d_index, &d_ns, &d_nl, &d_tmp0, &d_tmp1, &d_tmp2, &d_tmp3, &d_tmp4, &d_tmp5, &d_cursor, &d_items, &d_occ};
     }

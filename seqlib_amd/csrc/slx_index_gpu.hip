@@ -10,15 +10,9 @@
 #include <cstdio>
 #include <vector>
 #include "slx_internal.h"
+#include "slx_hip.h"
 
-#define HIPCHK(x)                                                                                   \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) {                                                                     \
-            slx_set_error("HIP error %s at %s:%d (%s)", hipGetErrorString(e_), __FILE__, __LINE__, #x); \
-            return SLX_ENODEVICE;                                                                   \
-        }                                                                                           \
-    } while (0)
+#define HIPCHK(x) SLX_HIPCHK(x)
 
 namespace {
 

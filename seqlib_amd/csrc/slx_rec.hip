@@ -16,9 +16,7 @@
 #include "seqlib_amd_rec.h"
 #include "dev_wave.h"
 #include "dev_rec.h"
-
-#define REC_HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { slx_set_error("HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, __LINE__); return SLX_ENODEVICE; } } while (0)
-#define REC_CHK(x) do { const int rc_ = (x); if (rc_ != SLX_OK) return rc_; } while (0)
+#include "slx_hip.h"
 
 typedef unsigned long long ull;
 
@@ -74,23 +72,9 @@ __global__ __launch_bounds__(256) void k_rec_fill(rec_in in, const rec_meta *met
 }
 
 // ------------------------------------------------------------------ host
-namespace {
-struct RDBuf {
-    void *p = nullptr; size_t cap = 0;
-    int ensure(size_t n)
-    {
-        if (n <= cap) return SLX_OK;
-        const size_t want = n + n / 4 + 256;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        if (hipMalloc(&p, want) != hipSuccess) { (void)hipGetLastError(); p = nullptr; slx_set_error("record builder: cannot allocate %zu bytes of HBM", want); return SLX_ENOMEM; }
-        cap = want;
-        return SLX_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <typename T> T *as() const { return (T *)p; }
-};
-}  // namespace
+// a margin of 1/4 + 256 bytes on every growth: kept as found.  The two pinned words are as large as what they hold
+typedef SlxDevBuf<SlxMargin<4, 256>> RDBuf;
+typedef SlxPinBuf<SlxExact> RHBuf;
 
 struct slx_rec {
     slx_aligner *al = nullptr;
@@ -99,8 +83,8 @@ struct slx_rec {
     hipEvent_t ev[3] = {};
     RDBuf d_owner, d_meta, d_len, d_off, d_wide, d_state, d_tmp, d_stream;
     RDBuf u_bases, u_offs, u_names, u_name_offs;      // slx_rec_upload's copies
-    rec_state *h_state = nullptr;       // pinned: [0] goes up, [1] comes down
-    ull *h_total = nullptr;             // pinned
+    RHBuf h_state;                      // two rec_state: [0] goes up, [1] comes down
+    RHBuf h_total;                      // one ull
     const void *last_stream = nullptr;  // of the batch handed out last
     int64_t last_records = 0, last_bytes = 0;
     int64_t c_records = 0, c_bytes = 0, c_batches = 0, c_wide = 0;
@@ -115,8 +99,7 @@ extern "C" void slx_rec_free(slx_rec *rb)
         (void)hipStreamSynchronize(rb->st);
     }
     for (RDBuf *b : {&rb->d_owner, &rb->d_meta, &rb->d_len, &rb->d_off, &rb->d_wide, &rb->d_state, &rb->d_tmp, &rb->d_stream, &rb->u_bases, &rb->u_offs, &rb->u_names, &rb->u_name_offs}) b->release();
-    if (rb->h_state) (void)hipHostFree(rb->h_state);
-    if (rb->h_total) (void)hipHostFree(rb->h_total);
+    rb->h_state.release(); rb->h_total.release();
     for (auto &e : rb->ev) if (e) (void)hipEventDestroy(e);
     if (rb->st) (void)hipStreamDestroy(rb->st);
     delete rb;
@@ -127,11 +110,10 @@ static int rec_init(slx_rec *rb, slx_aligner *al)
     const int device = slx_aligner_device_of(al);
     if (device < 0) { slx_set_error("slx_rec_create: single-device aligners only (the hits of a multi-device aligner are merged on the host)"); return SLX_EINVAL; }
     rb->al = al; rb->device = device;
-    REC_HIPCHK(hipSetDevice(device));
-    REC_HIPCHK(hipStreamCreateWithFlags(&rb->st, hipStreamNonBlocking));
-    for (auto &e : rb->ev) REC_HIPCHK(hipEventCreate(&e));
-    REC_HIPCHK(hipHostMalloc((void **)&rb->h_state, 2 * sizeof(rec_state), hipHostMallocDefault));
-    REC_HIPCHK(hipHostMalloc((void **)&rb->h_total, sizeof(ull), hipHostMallocDefault));
+    SLX_HIPCHK(hipSetDevice(device));
+    SLX_HIPCHK(hipStreamCreateWithFlags(&rb->st, hipStreamNonBlocking));
+    for (auto &e : rb->ev) SLX_HIPCHK(hipEventCreate(&e));
+    SLX_CHK(rb->h_state.ensure(2 * sizeof(rec_state))); SLX_CHK(rb->h_total.ensure(sizeof(ull)));
     return SLX_OK;
 }
 
@@ -139,12 +121,8 @@ extern "C" int slx_rec_create(slx_aligner *al, slx_rec **out)
 {
     if (!out) { slx_set_error("slx_rec_create: null argument"); return SLX_EINVAL; }
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {          // (before the aligner is looked at: without a GPU there is none to give)
-        (void)hipGetLastError();
-        slx_set_error("no HIP device: BAM records are built on MI355X only (no CPU fallback)");
-        return SLX_ENODEVICE;
-    }
+    int ndev = 0;          // (before the aligner is looked at: without a GPU there is none to give)
+    SLX_CHK(slx_count_devices("no HIP device: BAM records are built on MI355X only (no CPU fallback)", &ndev));
     if (!al) { slx_set_error("slx_rec_create: null aligner"); return SLX_EINVAL; }
     slx_rec *rb = new slx_rec();
     const int rc = rec_init(rb, al);
@@ -152,8 +130,6 @@ extern "C" int slx_rec_create(slx_aligner *al, slx_rec **out)
     *out = rb;
     return SLX_OK;
 }
-
-static float rec_ev_us(hipEvent_t a, hipEvent_t b) { float ms = 0; return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms * 1000.f : 0.f; }
 
 static int rec_build_impl(slx_rec *rb, const slx_hits *dev, rec_in in, slx_rec_batch *out)
 {
@@ -163,12 +139,12 @@ static int rec_build_impl(slx_rec *rb, const slx_hits *dev, rec_in in, slx_rec_b
     if (pre == REC_E_HOST) { slx_set_error("slx_rec_build: the result is host-resident; records are built from a result of slx_align_batch_device"); return rec_slx_code(pre); }
     if (pre == REC_E_REG2SAM) { slx_set_error("slx_rec_build: a SLX_F_REG2SAM result (UseBwaMemRecords): its XA / SA / MD strings are built on the host"); return rec_slx_code(pre); }
     if (dev->n_reads < 0 || dev->n_hits < 0 || dev->n_hits > 0xffffffffll) { slx_set_error("slx_rec_build: %lld reads, %lld hits", (long long)dev->n_reads, (long long)dev->n_hits); return SLX_EINVAL; }
-    REC_HIPCHK(hipSetDevice(rb->device));
+    SLX_HIPCHK(hipSetDevice(rb->device));
     const int64_t N = dev->n_reads, H = dev->n_hits;
-    REC_CHK(rb->d_off.ensure(8 * ((size_t)H + 1)));
+    SLX_CHK(rb->d_off.ensure(8 * ((size_t)H + 1)));
     if (H == 0) {          // reads without hits produce nothing
-        REC_HIPCHK(hipMemsetAsync(rb->d_off.p, 0, 8, rb->st));
-        REC_HIPCHK(slx_wait_stream(rb->st));
+        SLX_HIPCHK(hipMemsetAsync(rb->d_off.p, 0, 8, rb->st));
+        SLX_HIPCHK(slx_wait_stream(rb->st));
         out->d_rec_off = rb->d_off.p; out->d_stream = rb->d_off.p;
         rb->last_stream = out->d_stream;
         ++rb->c_batches;
@@ -178,28 +154,26 @@ static int rec_build_impl(slx_rec *rb, const slx_hits *dev, rec_in in, slx_rec_b
     in.hit_off = dev->hit_off; in.rid = dev->rid; in.pos = dev->pos; in.flag = dev->flag; in.mapq = dev->mapq; in.score = dev->score; in.nm = dev->nm; in.na = dev->na;
     in.n_cigar_ops = dev->n_cigar_ops; in.cig_off = dev->cig_off; in.cigar = dev->cigar;
     hipStream_t st = rb->st;
-    REC_CHK(rb->d_owner.ensure(8 * (size_t)H)); REC_CHK(rb->d_meta.ensure(sizeof(rec_meta) * (size_t)H)); REC_CHK(rb->d_len.ensure(8 * ((size_t)H + 1)));
-    REC_CHK(rb->d_wide.ensure(4 * (size_t)H)); REC_CHK(rb->d_state.ensure(sizeof(rec_state)));
-    rb->h_state[0].refusal = REC_NO_REFUSAL; rb->h_state[0].n_wide = 0; rb->h_state[0].pad = 0;
-    REC_HIPCHK(hipMemcpyAsync(rb->d_state.p, &rb->h_state[0], sizeof(rec_state), hipMemcpyHostToDevice, st));
-    REC_HIPCHK(hipEventRecord(rb->ev[0], st));
+    SLX_CHK(rb->d_owner.ensure(8 * (size_t)H)); SLX_CHK(rb->d_meta.ensure(sizeof(rec_meta) * (size_t)H)); SLX_CHK(rb->d_len.ensure(8 * ((size_t)H + 1)));
+    SLX_CHK(rb->d_wide.ensure(4 * (size_t)H)); SLX_CHK(rb->d_state.ensure(sizeof(rec_state)));
+    rec_state *const h_state = rb->h_state.as<rec_state>();
+    h_state[0].refusal = REC_NO_REFUSAL; h_state[0].n_wide = 0; h_state[0].pad = 0;
+    SLX_HIPCHK(hipMemcpyAsync(rb->d_state.p, &h_state[0], sizeof(rec_state), hipMemcpyHostToDevice, st));
+    SLX_HIPCHK(hipEventRecord(rb->ev[0], st));
     k_rec_owner<<<(unsigned)((N + 255) / 256), 256, 0, st>>>(in.hit_off, N, H, rb->d_owner.as<int64_t>());
-    REC_HIPCHK(hipGetLastError());
+    SLX_HIPCHK(hipGetLastError());
     k_rec_size<<<(unsigned)((H + 255) / 256), 256, 0, st>>>(in, rb->d_owner.as<int64_t>(), rb->d_meta.as<rec_meta>(), rb->d_len.as<ull>(), rb->d_wide.as<uint32_t>(), rb->d_state.as<rec_state>());
-    REC_HIPCHK(hipGetLastError());
+    SLX_HIPCHK(hipGetLastError());
     k_rec_size_wide<<<(unsigned)std::min<int64_t>((H + 3) / 4, 2048), 256, 0, st>>>(in, rb->d_owner.as<int64_t>(), rb->d_meta.as<rec_meta>(), rb->d_len.as<ull>(), rb->d_wide.as<uint32_t>(),
                                                                                    rb->d_state.as<rec_state>());
-    REC_HIPCHK(hipGetLastError());
-    size_t tb = 0;
-    REC_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, rb->d_len.as<ull>(), rb->d_off.as<ull>(), (int)(H + 1), st));
-    REC_CHK(rb->d_tmp.ensure(tb + 8));
-    REC_HIPCHK(hipcub::DeviceScan::ExclusiveSum(rb->d_tmp.p, tb, rb->d_len.as<ull>(), rb->d_off.as<ull>(), (int)(H + 1), st));
-    REC_HIPCHK(hipEventRecord(rb->ev[1], st));
-    REC_HIPCHK(hipMemcpyAsync(rb->h_total, rb->d_off.as<ull>() + H, sizeof(ull), hipMemcpyDeviceToHost, st));
-    REC_HIPCHK(hipMemcpyAsync(&rb->h_state[1], rb->d_state.p, sizeof(rec_state), hipMemcpyDeviceToHost, st));
-    REC_HIPCHK(slx_wait_stream(st));
-    rb->us_size += rec_ev_us(rb->ev[0], rb->ev[1]);
-    const rec_state got = rb->h_state[1];
+    SLX_HIPCHK(hipGetLastError());
+    SLX_CHK(slx_exclusive_sum(rb->d_tmp, rb->d_len.as<ull>(), rb->d_off.as<ull>(), (size_t)H + 1, st, 8));
+    SLX_HIPCHK(hipEventRecord(rb->ev[1], st));
+    SLX_HIPCHK(hipMemcpyAsync(rb->h_total.p, rb->d_off.as<ull>() + H, sizeof(ull), hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(hipMemcpyAsync(&h_state[1], rb->d_state.p, sizeof(rec_state), hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(slx_wait_stream(st));
+    rb->us_size += slx_ev_us(rb->ev[0], rb->ev[1]);
+    const rec_state got = h_state[1];
     if (got.refusal != REC_NO_REFUSAL) {
         const long long read = (long long)(got.refusal >> 8);
         const int code = (int)(got.refusal & 0xff);
@@ -208,15 +182,15 @@ static int rec_build_impl(slx_rec *rb, const slx_hits *dev, rec_in in, slx_rec_b
         else slx_set_error("slx_rec_build: read %lld of the batch has a hit whose hard-clip window is empty or passes the read (was the alignment made with the same hardclip?); nothing of the batch was built", read);
         return rec_slx_code(code);
     }
-    const ull total = *rb->h_total;
+    const ull total = *rb->h_total.as<ull>();
     if (total < 58ull * (ull)H) { slx_set_error("slx_rec_build: internal: %llu bytes for %lld records", total, (long long)H); return SLX_EINTERNAL; }
-    REC_CHK(rb->d_stream.ensure((size_t)total + 16));
+    SLX_CHK(rb->d_stream.ensure((size_t)total + 16));
     const ull n_tiles = (total + REC_TILE - 1) / REC_TILE;
     k_rec_fill<<<(unsigned)((n_tiles + 3) / 4), 256, 0, st>>>(in, rb->d_meta.as<rec_meta>(), rb->d_owner.as<int64_t>(), rb->d_off.as<ull>(), total, rb->d_stream.as<uint8_t>());
-    REC_HIPCHK(hipGetLastError());
-    REC_HIPCHK(hipEventRecord(rb->ev[2], st));
-    REC_HIPCHK(slx_wait_stream(st));
-    rb->us_fill += rec_ev_us(rb->ev[1], rb->ev[2]);
+    SLX_HIPCHK(hipGetLastError());
+    SLX_HIPCHK(hipEventRecord(rb->ev[2], st));
+    SLX_HIPCHK(slx_wait_stream(st));
+    rb->us_fill += slx_ev_us(rb->ev[1], rb->ev[2]);
     out->n_records = H; out->n_bytes = (int64_t)total; out->d_stream = rb->d_stream.p; out->d_rec_off = rb->d_off.p;
     rb->last_stream = out->d_stream; rb->last_records = H; rb->last_bytes = (int64_t)total;
     rb->c_records += H; rb->c_bytes += (int64_t)total; ++rb->c_batches; rb->c_wide += got.n_wide;
@@ -261,13 +235,13 @@ extern "C" int slx_rec_upload(slx_rec *rb, const void *bases, const uint64_t *of
     if (!rb || !offs || !name_offs || n_reads < 0 || !d_bases || !d_offs || !d_names || !d_name_offs) { slx_set_error("slx_rec_upload: null argument"); return SLX_EINVAL; }
     const uint64_t nb = offs[n_reads] - offs[0], nn = name_offs[n_reads] - name_offs[0];
     if (offs[0] != 0 || name_offs[0] != 0 || (nb && !bases) || (nn && !names)) { slx_set_error("slx_rec_upload: offsets start at 0 and the arrays they index are given"); return SLX_EINVAL; }
-    REC_HIPCHK(hipSetDevice(rb->device));
-    REC_CHK(rb->u_bases.ensure(nb + 16)); REC_CHK(rb->u_names.ensure(nn + 16)); REC_CHK(rb->u_offs.ensure(8 * ((size_t)n_reads + 1))); REC_CHK(rb->u_name_offs.ensure(8 * ((size_t)n_reads + 1)));
-    if (nb) REC_HIPCHK(hipMemcpyAsync(rb->u_bases.p, bases, nb, hipMemcpyHostToDevice, rb->st));
-    if (nn) REC_HIPCHK(hipMemcpyAsync(rb->u_names.p, names, nn, hipMemcpyHostToDevice, rb->st));
-    REC_HIPCHK(hipMemcpyAsync(rb->u_offs.p, offs, 8 * ((size_t)n_reads + 1), hipMemcpyHostToDevice, rb->st));
-    REC_HIPCHK(hipMemcpyAsync(rb->u_name_offs.p, name_offs, 8 * ((size_t)n_reads + 1), hipMemcpyHostToDevice, rb->st));
-    REC_HIPCHK(slx_wait_stream(rb->st));
+    SLX_HIPCHK(hipSetDevice(rb->device));
+    SLX_CHK(rb->u_bases.ensure(nb + 16)); SLX_CHK(rb->u_names.ensure(nn + 16)); SLX_CHK(rb->u_offs.ensure(8 * ((size_t)n_reads + 1))); SLX_CHK(rb->u_name_offs.ensure(8 * ((size_t)n_reads + 1)));
+    if (nb) SLX_HIPCHK(hipMemcpyAsync(rb->u_bases.p, bases, nb, hipMemcpyHostToDevice, rb->st));
+    if (nn) SLX_HIPCHK(hipMemcpyAsync(rb->u_names.p, names, nn, hipMemcpyHostToDevice, rb->st));
+    SLX_HIPCHK(hipMemcpyAsync(rb->u_offs.p, offs, 8 * ((size_t)n_reads + 1), hipMemcpyHostToDevice, rb->st));
+    SLX_HIPCHK(hipMemcpyAsync(rb->u_name_offs.p, name_offs, 8 * ((size_t)n_reads + 1), hipMemcpyHostToDevice, rb->st));
+    SLX_HIPCHK(slx_wait_stream(rb->st));
     *d_bases = rb->u_bases.p; *d_offs = rb->u_offs.p; *d_names = rb->u_names.p; *d_name_offs = rb->u_name_offs.p;
     return SLX_OK;
 }
@@ -277,10 +251,10 @@ extern "C" int slx_rec_to_host(slx_rec *rb, const slx_rec_batch *b, void *dst, u
     if (!rb || !b) { slx_set_error("slx_rec_to_host: null argument"); return SLX_EINVAL; }
     if (!rb->last_stream || b->d_stream != rb->last_stream || b->n_records != rb->last_records || b->n_bytes != rb->last_bytes) { slx_set_error("slx_rec_to_host: not the builder's last batch"); return SLX_EINVAL; }
     if ((uint64_t)b->n_bytes > cap || (b->n_bytes && !dst)) { slx_set_error("slx_rec_to_host: %lld bytes do not fit the %llu given", (long long)b->n_bytes, (unsigned long long)cap); return SLX_EINVAL; }
-    REC_HIPCHK(hipSetDevice(rb->device));
-    if (b->n_bytes) REC_HIPCHK(hipMemcpyAsync(dst, b->d_stream, (size_t)b->n_bytes, hipMemcpyDeviceToHost, rb->st));
-    if (rec_off_dst) REC_HIPCHK(hipMemcpyAsync(rec_off_dst, b->d_rec_off, 8 * ((size_t)b->n_records + 1), hipMemcpyDeviceToHost, rb->st));
-    REC_HIPCHK(hipStreamSynchronize(rb->st));
+    SLX_HIPCHK(hipSetDevice(rb->device));
+    if (b->n_bytes) SLX_HIPCHK(hipMemcpyAsync(dst, b->d_stream, (size_t)b->n_bytes, hipMemcpyDeviceToHost, rb->st));
+    if (rec_off_dst) SLX_HIPCHK(hipMemcpyAsync(rec_off_dst, b->d_rec_off, 8 * ((size_t)b->n_records + 1), hipMemcpyDeviceToHost, rb->st));
+    SLX_HIPCHK(hipStreamSynchronize(rb->st));
     return SLX_OK;
 }
 

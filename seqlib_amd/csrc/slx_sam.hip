@@ -25,9 +25,6 @@
 #include "sam_host.h"
 #include "sam_reader.h"
 
-#define SAM_HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { slx_set_error("HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, __LINE__); return SLX_ENODEVICE; } } while (0)
-#define SAM_CHK(x) do { const int rc_ = (x); if (rc_ != SLX_OK) return rc_; } while (0)
-
 // ------------------------------------------------------------------ kernels
 // sam_fields for one wave: lane i tests byte 64 j + i, the ballot gives the tabs in order.  s[0, n), n <= SAM_MAX_LINE; F is written by lane 0.
 __device__ __forceinline__ void sam_fields_wave(const uint8_t *s, uint32_t n, uint32_t lane, sam_fld *F)
@@ -139,10 +136,10 @@ static int sam_read_header(slx_samsrc *S)
     uint64_t want = 1u << 16;
     std::string msg;
     for (;;) {
-        if (!S->src_eof) SAM_CHK(fq_pull(S, want));
-        SAM_CHK(S->h_text.ensure(S->have + 1));
-        if (S->have) SAM_HIPCHK(hipMemcpyAsync(S->h_text.p, S->d_text[S->cur].p, S->have, hipMemcpyDeviceToHost, S->st));
-        SAM_HIPCHK(slx_wait_stream(S->st));
+        if (!S->src_eof) SLX_CHK(fq_pull(S, want));
+        SLX_CHK(S->h_text.ensure(S->have + 1));
+        if (S->have) SLX_HIPCHK(hipMemcpyAsync(S->h_text.p, S->d_text[S->cur].p, S->have, hipMemcpyDeviceToHost, S->st));
+        SLX_HIPCHK(slx_wait_stream(S->st));
         const int r = samh_header(S->h_text.as<uint8_t>(), S->have, S->src_eof, S->text, S->ref_names, S->ref_lens, &S->body_off, &S->header_lines, msg);
         if (r < 0) { slx_set_error("SAM: '%s': %s", S->path.c_str(), msg.c_str()); return SLX_EIO; }
         if (r == 1) break;
@@ -154,11 +151,11 @@ static int sam_read_header(slx_samsrc *S)
 
 int slx_samsrc_rewind(slx_samsrc *S)
 {
-    SAM_HIPCHK(hipSetDevice(S->device));
-    SAM_CHK(fq_text_start(S));
+    SLX_HIPCHK(hipSetDevice(S->device));
+    SLX_CHK(fq_text_start(S));
     S->done = S->bad = false; S->c_fast = S->c_slow = 0;
     for (float &u : S->us_sam) u = 0;
-    while (S->have < S->body_off && !S->src_eof) SAM_CHK(fq_pull(S, S->body_off - S->have));
+    while (S->have < S->body_off && !S->src_eof) SLX_CHK(fq_pull(S, S->body_off - S->have));
     S->used = S->body_off; S->line_base = S->header_lines;
     return SLX_OK;
 }
@@ -228,39 +225,39 @@ static int sam_parse(slx_samsrc *S, uint64_t *n_rec, uint64_t *n_bytes, uint64_t
     uint64_t L = 0;
     int virt = 0;
     *n_rec = *n_bytes = *consumed = 0;
-    SAM_CHK(fq_line_starts(S, &L, &virt));
+    SLX_CHK(fq_line_starts(S, &L, &virt));
     if (L == 0) return SLX_OK;
     if (L >= 0xffffffffull) { slx_set_error("SAM reader: 2^32 lines or more in one batch; ask for fewer bytes"); return SLX_EUNSUPPORTED; }
     const fq_u64 *line_off = S->d_line.as<fq_u64>();
-    SAM_CHK(S->d_fld.ensure(sizeof(sam_fld) * L)); SAM_CHK(S->d_size.ensure(8 * (L + 1))); SAM_CHK(S->d_verdict.ensure(L + 8)); SAM_CHK(S->d_rec.ensure(8 * (L + 1)));
-    SAM_CHK(S->d_cnt.ensure(8)); SAM_CHK(S->h_size.ensure(8 * (L + 1) + 64));
+    SLX_CHK(S->d_fld.ensure(sizeof(sam_fld) * L)); SLX_CHK(S->d_size.ensure(8 * (L + 1))); SLX_CHK(S->d_verdict.ensure(L + 8)); SLX_CHK(S->d_rec.ensure(8 * (L + 1)));
+    SLX_CHK(S->d_cnt.ensure(8)); SLX_CHK(S->h_size.ensure(8 * (L + 1) + 64));
     fq_u64 *hs = S->h_small.as<fq_u64>();
-    SAM_HIPCHK(hipMemsetAsync(S->d_cnt.p, 0, 8, st));
-    SAM_HIPCHK(hipMemsetAsync(S->d_fld.p, 0, sizeof(sam_fld) * L, st));
+    SLX_HIPCHK(hipMemsetAsync(S->d_cnt.p, 0, 8, st));
+    SLX_HIPCHK(hipMemsetAsync(S->d_fld.p, 0, sizeof(sam_fld) * L, st));
     const sam_refs R = S->dev_refs();
-    SAM_HIPCHK(hipEventRecord(S->ev[2], st));
+    SLX_HIPCHK(hipEventRecord(S->ev[2], st));
     k_sam_fields<<<(unsigned)((L + 3) / 4), 256, 0, st>>>(text, line_off, L, virt, S->d_fld.as<sam_fld>());
-    SAM_HIPCHK(hipGetLastError());
-    SAM_HIPCHK(hipEventRecord(S->ev[3], st));
+    SLX_HIPCHK(hipGetLastError());
+    SLX_HIPCHK(hipEventRecord(S->ev[3], st));
     k_sam_size<<<(unsigned)((L + 1 + 255) / 256), 256, 0, st>>>(text, line_off, L, virt, S->d_fld.as<sam_fld>(), R, S->fast_fail, S->d_size.as<fq_u64>(), S->d_verdict.as<uint8_t>(), S->d_cnt.as<fq_u64>());
-    SAM_HIPCHK(hipGetLastError());
-    SAM_HIPCHK(hipEventRecord(S->ev[4], st));
-    SAM_HIPCHK(hipMemcpyAsync(hs, S->d_cnt.p, 8, hipMemcpyDeviceToHost, st));
-    SAM_HIPCHK(hipMemcpyAsync(hs + 1, line_off + L, 8, hipMemcpyDeviceToHost, st));
-    SAM_HIPCHK(slx_wait_stream(st));
-    S->us[0] += fq_ev_us(S->ev[0], S->ev[1]); S->us_sam[0] += fq_ev_us(S->ev[2], S->ev[3]); S->us_sam[1] += fq_ev_us(S->ev[3], S->ev[4]);
+    SLX_HIPCHK(hipGetLastError());
+    SLX_HIPCHK(hipEventRecord(S->ev[4], st));
+    SLX_HIPCHK(hipMemcpyAsync(hs, S->d_cnt.p, 8, hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(hipMemcpyAsync(hs + 1, line_off + L, 8, hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(slx_wait_stream(st));
+    S->us[0] += slx_ev_us(S->ev[0], S->ev[1]); S->us_sam[0] += slx_ev_us(S->ev[2], S->ev[3]); S->us_sam[1] += slx_ev_us(S->ev[3], S->ev[4]);
     const uint64_t n_other = hs[0];
     *consumed = hs[1] < n ? hs[1] : n;
     // ---- the lines that are not FAST, one by one through the host parser
     uint64_t L_eff = L, n_slow = 0;
     const fq_u64 *d_src = nullptr;
     if (n_other) {
-        SAM_CHK(S->h_text.ensure(n + 1)); SAM_CHK(S->h_verdict.ensure(L + 8)); SAM_CHK(S->h_line.ensure(8 * (L + 2))); SAM_CHK(S->h_src.ensure(8 * (L + 1)));
-        SAM_HIPCHK(hipMemcpyAsync(S->h_text.p, text, n, hipMemcpyDeviceToHost, st));
-        SAM_HIPCHK(hipMemcpyAsync(S->h_verdict.p, S->d_verdict.p, L, hipMemcpyDeviceToHost, st));
-        SAM_HIPCHK(hipMemcpyAsync(S->h_line.p, line_off, 8 * (L + 1), hipMemcpyDeviceToHost, st));
-        SAM_HIPCHK(hipMemcpyAsync(S->h_size.p, S->d_size.p, 8 * (L + 1), hipMemcpyDeviceToHost, st));
-        SAM_HIPCHK(slx_wait_stream(st));
+        SLX_CHK(S->h_text.ensure(n + 1)); SLX_CHK(S->h_verdict.ensure(L + 8)); SLX_CHK(S->h_line.ensure(8 * (L + 2))); SLX_CHK(S->h_src.ensure(8 * (L + 1)));
+        SLX_HIPCHK(hipMemcpyAsync(S->h_text.p, text, n, hipMemcpyDeviceToHost, st));
+        SLX_HIPCHK(hipMemcpyAsync(S->h_verdict.p, S->d_verdict.p, L, hipMemcpyDeviceToHost, st));
+        SLX_HIPCHK(hipMemcpyAsync(S->h_line.p, line_off, 8 * (L + 1), hipMemcpyDeviceToHost, st));
+        SLX_HIPCHK(hipMemcpyAsync(S->h_size.p, S->d_size.p, 8 * (L + 1), hipMemcpyDeviceToHost, st));
+        SLX_HIPCHK(slx_wait_stream(st));
         const uint8_t *ht = S->h_text.as<uint8_t>(), *hv = S->h_verdict.as<uint8_t>();
         const fq_u64 *hl = S->h_line.as<fq_u64>();
         fq_u64 *hsz = S->h_size.as<fq_u64>(), *hsrc = S->h_src.as<fq_u64>();
@@ -291,26 +288,26 @@ static int sam_parse(slx_samsrc *S, uint64_t *n_rec, uint64_t *n_bytes, uint64_t
         }
         hsz[L_eff] = 0;
         if (L_eff == 0) return SLX_OK;          // (S->bad: the caller reports it)
-        SAM_CHK(S->d_slow.ensure(stage.size() + 16)); SAM_CHK(S->h_slow.ensure(stage.size() + 16)); SAM_CHK(S->d_src.ensure(8 * (L + 1)));
+        SLX_CHK(S->d_slow.ensure(stage.size() + 16)); SLX_CHK(S->h_slow.ensure(stage.size() + 16)); SLX_CHK(S->d_src.ensure(8 * (L + 1)));
         if (!stage.empty()) memcpy(S->h_slow.p, stage.data(), stage.size());
         for (uint64_t k : at) hsrc[k] += (fq_u64)(uintptr_t)S->d_slow.p;
-        if (!stage.empty()) SAM_HIPCHK(hipMemcpyAsync(S->d_slow.p, S->h_slow.p, stage.size(), hipMemcpyHostToDevice, st));
-        SAM_HIPCHK(hipMemcpyAsync(S->d_src.p, hsrc, 8 * (L_eff + 1), hipMemcpyHostToDevice, st));
-        SAM_HIPCHK(hipMemcpyAsync(S->d_size.p, hsz, 8 * (L_eff + 1), hipMemcpyHostToDevice, st));
+        if (!stage.empty()) SLX_HIPCHK(hipMemcpyAsync(S->d_slow.p, S->h_slow.p, stage.size(), hipMemcpyHostToDevice, st));
+        SLX_HIPCHK(hipMemcpyAsync(S->d_src.p, hsrc, 8 * (L_eff + 1), hipMemcpyHostToDevice, st));
+        SLX_HIPCHK(hipMemcpyAsync(S->d_size.p, hsz, 8 * (L_eff + 1), hipMemcpyHostToDevice, st));
         d_src = S->d_src.as<fq_u64>();
     }
     // ---- offsets, then the records
-    SAM_CHK(fq_scan(S, S->d_size.as<fq_u64>(), S->d_rec.as<fq_u64>(), L_eff + 1));
-    SAM_HIPCHK(hipMemcpyAsync(hs, S->d_rec.as<fq_u64>() + L_eff, 8, hipMemcpyDeviceToHost, st));
-    SAM_HIPCHK(slx_wait_stream(st));
+    SLX_CHK(fq_scan(S, S->d_size.as<fq_u64>(), S->d_rec.as<fq_u64>(), L_eff + 1));
+    SLX_HIPCHK(hipMemcpyAsync(hs, S->d_rec.as<fq_u64>() + L_eff, 8, hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(slx_wait_stream(st));
     const uint64_t total = hs[0];
-    SAM_CHK(S->d_out.ensure(total + 64));
-    SAM_HIPCHK(hipEventRecord(S->ev[5], st));
+    SLX_CHK(S->d_out.ensure(total + 64));
+    SLX_HIPCHK(hipEventRecord(S->ev[5], st));
     k_sam_fill<<<(unsigned)((L_eff + 3) / 4), 256, 0, st>>>(text, line_off, L_eff, L, virt, S->d_fld.as<sam_fld>(), R, S->d_verdict.as<uint8_t>(), d_src, S->d_rec.as<fq_u64>(), S->d_out.as<uint8_t>());
-    SAM_HIPCHK(hipGetLastError());
-    SAM_HIPCHK(hipEventRecord(S->ev[6], st));
-    SAM_HIPCHK(slx_wait_stream(st));
-    S->us_sam[2] += fq_ev_us(S->ev[5], S->ev[6]);
+    SLX_HIPCHK(hipGetLastError());
+    SLX_HIPCHK(hipEventRecord(S->ev[6], st));
+    SLX_HIPCHK(slx_wait_stream(st));
+    S->us_sam[2] += slx_ev_us(S->ev[5], S->ev[6]);
     *n_rec = L_eff; *n_bytes = total;
     S->c_slow += (int64_t)n_slow; S->c_fast += (int64_t)(L_eff - n_slow);
     S->line_base += L_eff;
@@ -323,18 +320,18 @@ int slx_samsrc_next(slx_samsrc *S, int64_t max_bytes, const void **d_stream, con
     if (S->bad) { slx_set_error("%s", S->bad_msg.c_str()); return SLX_EIO; }
     if (S->done) return SLX_OK;
     if (max_bytes <= 0) max_bytes = 64ll << 20;
-    SAM_HIPCHK(hipSetDevice(S->device));
+    SLX_HIPCHK(hipSetDevice(S->device));
     const int64_t members0 = S->c_members;
     uint64_t target = (uint64_t)max_bytes;
     for (;;) {
-        if (S->used) SAM_CHK(fq_shift(S, target));          // the cut tail moves to the front of the other buffer
-        if (S->have < target && !S->src_eof) SAM_CHK(fq_pull(S, target - S->have));
+        if (S->used) SLX_CHK(fq_shift(S, target));          // the cut tail moves to the front of the other buffer
+        if (S->have < target && !S->src_eof) SLX_CHK(fq_pull(S, target - S->have));
         if (S->have == 0) {
             if (S->src_eof) { S->done = true; return SLX_OK; }
             continue;
         }
         uint64_t consumed = 0;
-        SAM_CHK(sam_parse(S, n_rec, n_bytes, &consumed));
+        SLX_CHK(sam_parse(S, n_rec, n_bytes, &consumed));
         S->used = consumed;
         *n_members = S->c_members - members0;
         if (*n_rec) { *d_stream = S->d_out.p; *d_rec = S->d_rec.p; return SLX_OK; }

@@ -22,9 +22,7 @@
 #include "dev_wave.h"
 #include "dev_recsort.h"
 #include "recsort_host.h"
-
-#define SORT_HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { slx_set_error("HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, __LINE__); return SLX_ENODEVICE; } } while (0)
-#define SORT_CHK(x) do { const int rc_ = (x); if (rc_ != SLX_OK) return rc_; } while (0)
+#include "slx_hip.h"
 
 typedef unsigned long long ull;
 static const int64_t SORT_MAX_SLAB = 1ll << 40;          // 2^29 tiles, 2^27 blocks of k_sort_gather: well inside a grid
@@ -78,20 +76,9 @@ __global__ __launch_bounds__(256) void k_sort_gather(const ull *dst_off, const u
 
 // ------------------------------------------------------------------ host
 namespace {
-struct SBuf {
-    void *p = nullptr; size_t cap = 0;
-    int ensure(size_t n)
-    {
-        if (n <= cap) return SLX_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        if (hipMalloc(&p, n) != hipSuccess) { (void)hipGetLastError(); p = nullptr; slx_set_error("sorter: cannot allocate %zu bytes of HBM", n); return SLX_ENOMEM; }
-        cap = n;
-        return SLX_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <typename T> T *as() const { return (T *)p; }
-};
+// no margin: the tables are sized by the held records, which max_bytes bounds -- HBM a margin took would be HBM the budget cannot give to records
+typedef SlxDevBuf<SlxExact> SBuf;
+typedef SlxPinBuf<SlxExact> SHBuf;
 
 // one add: the bytes and, behind them in the same allocation, the offsets and the three per-record tables
 struct Segment {
@@ -111,12 +98,10 @@ struct slx_sort {
     ull max_key = 0;
     int64_t max_bytes = 0, slab_bytes = 64ll << 20, batch_bytes = 64ll << 20;
     SBuf d_state, d_key_in, d_key_out, d_ord_in, d_ord_out, d_len, d_src, d_slen, d_ssrc, d_doff, d_tmp, d_slab;
-    sort_state *h_state = nullptr;          // pinned: [0] goes up, [1] comes down
+    SHBuf h_state;                          // two sort_state: [0] goes up, [1] comes down
     int64_t c_records = 0, c_bytes = 0, c_segments = 0, c_slabs = 0;
     double us_key = 0, us_sort = 0, us_gather = 0;
 };
-
-static float sort_ev_us(hipEvent_t a, hipEvent_t b) { float ms = 0; return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms * 1000.f : 0.f; }
 
 static void sort_clear(slx_sort *s)
 {
@@ -131,38 +116,24 @@ extern "C" void slx_sort_free(slx_sort *s)
     if (s->st) { (void)hipSetDevice(s->device); (void)hipStreamSynchronize(s->st); }
     sort_clear(s);
     for (SBuf *b : {&s->d_state, &s->d_key_in, &s->d_key_out, &s->d_ord_in, &s->d_ord_out, &s->d_len, &s->d_src, &s->d_slen, &s->d_ssrc, &s->d_doff, &s->d_tmp, &s->d_slab}) b->release();
-    if (s->h_state) (void)hipHostFree(s->h_state);
+    s->h_state.release();
     for (auto &e : s->ev) if (e) (void)hipEventDestroy(e);
     if (s->st) (void)hipStreamDestroy(s->st);
     delete s;
 }
 
-static int sort_no_device(const char *who)
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        slx_set_error("%s: no HIP device: BAM records are sorted on MI355X only (no CPU fallback)", who);
-        return SLX_ENODEVICE;
-    }
-    return SLX_OK;
-}
+static std::string sort_no_device(const char *who) { return std::string(who) + ": no HIP device: BAM records are sorted on MI355X only (no CPU fallback)"; }
 
 static int sort_init(slx_sort *s, int device)
 {
-    int ndev = 0;
-    SORT_HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0) SORT_HIPCHK(hipGetDevice(&device));
-    if (device >= ndev) { slx_set_error("slx_sort_create: device %d is not one of the %d visible", device, ndev); return SLX_EINVAL; }
-    SORT_HIPCHK(hipSetDevice(device));
-    s->device = device;
+    SLX_CHK(slx_pick_device(device, sort_no_device("slx_sort_create").c_str(), "slx_sort_create", &s->device));
     size_t free_b = 0, total_b = 0;
-    SORT_HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    SLX_HIPCHK(hipMemGetInfo(&free_b, &total_b));
     s->max_bytes = std::max<int64_t>((int64_t)(free_b / 2), 1);
-    SORT_HIPCHK(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
-    for (auto &e : s->ev) SORT_HIPCHK(hipEventCreate(&e));
-    SORT_HIPCHK(hipHostMalloc((void **)&s->h_state, 2 * sizeof(sort_state), hipHostMallocDefault));
-    SORT_CHK(s->d_state.ensure(sizeof(sort_state)));
+    SLX_HIPCHK(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
+    for (auto &e : s->ev) SLX_HIPCHK(hipEventCreate(&e));
+    SLX_CHK(s->h_state.ensure(2 * sizeof(sort_state)));
+    SLX_CHK(s->d_state.ensure(sizeof(sort_state)));
     return SLX_OK;
 }
 
@@ -170,7 +141,6 @@ extern "C" int slx_sort_create(int device, slx_sort **out)
 {
     if (!out) { slx_set_error("slx_sort_create: null argument"); return SLX_EINVAL; }
     *out = nullptr;
-    SORT_CHK(sort_no_device("slx_sort_create"));
     slx_sort *s = new slx_sort();
     const int rc = sort_init(s, device);
     if (rc != SLX_OK) { slx_sort_free(s); return rc; }
@@ -194,7 +164,7 @@ static int sort_add(slx_sort *s, const void *stream, int64_t n_bytes, const void
         slx_set_error("%s: %llu records: the sorter's ordinals are 32 bits", who, (ull)(s->held_records + (uint64_t)n_records));
         return SLX_EUNSUPPORTED;
     }
-    SORT_HIPCHK(hipSetDevice(s->device));
+    SLX_HIPCHK(hipSetDevice(s->device));
     const size_t n = (size_t)n_records, nb = (size_t)n_bytes;
     const size_t o_off = up16(nb), o_key = o_off + up16(8 * (n + 1)), o_src = o_key + up16(8 * n), o_len = o_src + up16(8 * n), total = o_len + up16(4 * n);
     Segment g;
@@ -202,22 +172,23 @@ static int sort_add(slx_sort *s, const void *stream, int64_t n_bytes, const void
     g.n_bytes = nb; g.n = n;
     g.off = (uint64_t *)(g.base + o_off); g.key = (ull *)(g.base + o_key); g.src = (ull *)(g.base + o_src); g.len = (uint32_t *)(g.base + o_len);
     hipStream_t st = s->st;
+    sort_state *const h_state = s->h_state.as<sort_state>();
     auto run = [&]() -> int {
         const hipMemcpyKind kind = from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-        SORT_HIPCHK(hipMemcpyAsync(g.base, stream, nb, kind, st));
-        SORT_HIPCHK(hipMemcpyAsync(g.off, rec_off, 8 * (n + 1), kind, st));
-        s->h_state[0].bad = RS_NO_BAD; s->h_state[0].max_key = 0;
-        SORT_HIPCHK(hipMemcpyAsync(s->d_state.p, &s->h_state[0], sizeof(sort_state), hipMemcpyHostToDevice, st));
-        SORT_HIPCHK(hipEventRecord(s->ev[0], st));
+        SLX_HIPCHK(hipMemcpyAsync(g.base, stream, nb, kind, st));
+        SLX_HIPCHK(hipMemcpyAsync(g.off, rec_off, 8 * (n + 1), kind, st));
+        h_state[0].bad = RS_NO_BAD; h_state[0].max_key = 0;
+        SLX_HIPCHK(hipMemcpyAsync(s->d_state.p, &h_state[0], sizeof(sort_state), hipMemcpyHostToDevice, st));
+        SLX_HIPCHK(hipEventRecord(s->ev[0], st));
         k_sort_key<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(g.base, nb, g.off, n, g.key, g.len, g.src, s->d_state.as<sort_state>());
-        SORT_HIPCHK(hipGetLastError());
-        SORT_HIPCHK(hipEventRecord(s->ev[1], st));
-        SORT_HIPCHK(hipMemcpyAsync(&s->h_state[1], s->d_state.p, sizeof(sort_state), hipMemcpyDeviceToHost, st));
-        SORT_HIPCHK(slx_wait_stream(st));
-        s->us_key += sort_ev_us(s->ev[0], s->ev[1]);
-        if (s->h_state[1].bad != RS_NO_BAD) {
+        SLX_HIPCHK(hipGetLastError());
+        SLX_HIPCHK(hipEventRecord(s->ev[1], st));
+        SLX_HIPCHK(hipMemcpyAsync(&h_state[1], s->d_state.p, sizeof(sort_state), hipMemcpyDeviceToHost, st));
+        SLX_HIPCHK(slx_wait_stream(st));
+        s->us_key += slx_ev_us(s->ev[0], s->ev[1]);
+        if (h_state[1].bad != RS_NO_BAD) {
             slx_set_error("%s: record %llu of the call does not start where the block_size before it ends, or its offsets do not rise inside the %lld bytes, or (the last) its block_size does not end there; nothing of the call was added",
-                          who, s->h_state[1].bad, (long long)n_bytes);
+                          who, h_state[1].bad, (long long)n_bytes);
             return SLX_EINVAL;
         }
         return SLX_OK;
@@ -226,7 +197,7 @@ static int sort_add(slx_sort *s, const void *stream, int64_t n_bytes, const void
     if (rc != SLX_OK) { (void)hipStreamSynchronize(st); (void)hipFree(g.base); return rc; }
     s->segs.push_back(g);
     s->held_records += n; s->held_bytes += nb;
-    s->max_key = std::max(s->max_key, s->h_state[1].max_key);
+    s->max_key = std::max(s->max_key, h_state[1].max_key);
     s->c_records += (int64_t)n; s->c_bytes += (int64_t)nb; ++s->c_segments;
     return SLX_OK;
 }
@@ -245,32 +216,32 @@ static int sort_tables(slx_sort *s)
 {
     const size_t N = (size_t)s->held_records;
     hipStream_t st = s->st;
-    SORT_CHK(s->d_key_in.ensure(8 * N)); SORT_CHK(s->d_key_out.ensure(8 * N)); SORT_CHK(s->d_ord_in.ensure(4 * N)); SORT_CHK(s->d_ord_out.ensure(4 * N));
-    SORT_CHK(s->d_len.ensure(4 * N)); SORT_CHK(s->d_src.ensure(8 * N)); SORT_CHK(s->d_slen.ensure(8 * (N + 1))); SORT_CHK(s->d_ssrc.ensure(8 * N)); SORT_CHK(s->d_doff.ensure(8 * (N + 1)));
-    SORT_HIPCHK(hipEventRecord(s->ev[0], st));
+    SLX_CHK(s->d_key_in.ensure(8 * N)); SLX_CHK(s->d_key_out.ensure(8 * N)); SLX_CHK(s->d_ord_in.ensure(4 * N)); SLX_CHK(s->d_ord_out.ensure(4 * N));
+    SLX_CHK(s->d_len.ensure(4 * N)); SLX_CHK(s->d_src.ensure(8 * N)); SLX_CHK(s->d_slen.ensure(8 * (N + 1))); SLX_CHK(s->d_ssrc.ensure(8 * N)); SLX_CHK(s->d_doff.ensure(8 * (N + 1)));
+    SLX_HIPCHK(hipEventRecord(s->ev[0], st));
     size_t at = 0;
     for (const Segment &g : s->segs) {          // the per-record tables of the segments side by side (the records themselves stay where they are)
-        SORT_HIPCHK(hipMemcpyAsync(s->d_key_in.as<ull>() + at, g.key, 8 * g.n, hipMemcpyDeviceToDevice, st));
-        SORT_HIPCHK(hipMemcpyAsync(s->d_src.as<ull>() + at, g.src, 8 * g.n, hipMemcpyDeviceToDevice, st));
-        SORT_HIPCHK(hipMemcpyAsync(s->d_len.as<uint32_t>() + at, g.len, 4 * g.n, hipMemcpyDeviceToDevice, st));
+        SLX_HIPCHK(hipMemcpyAsync(s->d_key_in.as<ull>() + at, g.key, 8 * g.n, hipMemcpyDeviceToDevice, st));
+        SLX_HIPCHK(hipMemcpyAsync(s->d_src.as<ull>() + at, g.src, 8 * g.n, hipMemcpyDeviceToDevice, st));
+        SLX_HIPCHK(hipMemcpyAsync(s->d_len.as<uint32_t>() + at, g.len, 4 * g.n, hipMemcpyDeviceToDevice, st));
         at += (size_t)g.n;
     }
     const unsigned grid = (unsigned)((N + 256) / 256);
     k_sort_iota<<<grid, 256, 0, st>>>(s->d_ord_in.as<uint32_t>(), N);
-    SORT_HIPCHK(hipGetLastError());
+    SLX_HIPCHK(hipGetLastError());
     int end_bit = 1;          // the bits in use: the highest key of the adds is known
     while (end_bit < 64 && (s->max_key >> end_bit)) ++end_bit;
-    size_t tb_sort = 0, tb_scan = 0;
-    SORT_HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, s->d_key_in.as<ull>(), s->d_key_out.as<ull>(), s->d_ord_in.as<uint32_t>(), s->d_ord_out.as<uint32_t>(), N, 0, end_bit, st));
-    SORT_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb_scan, s->d_slen.as<ull>(), s->d_doff.as<ull>(), N + 1, st));
-    SORT_CHK(s->d_tmp.ensure(std::max(tb_sort, tb_scan) + 8));
-    SORT_HIPCHK(hipcub::DeviceRadixSort::SortPairs(s->d_tmp.p, tb_sort, s->d_key_in.as<ull>(), s->d_key_out.as<ull>(), s->d_ord_in.as<uint32_t>(), s->d_ord_out.as<uint32_t>(), N, 0, end_bit, st));
+    size_t tb_sort = 0, tb_scan = 0;          // one block for both: the sum finds it large enough and allocates nothing
+    SLX_HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, s->d_key_in.as<ull>(), s->d_key_out.as<ull>(), s->d_ord_in.as<uint32_t>(), s->d_ord_out.as<uint32_t>(), N, 0, end_bit, st));
+    SLX_CHK(slx_exclusive_sum_bytes(s->d_slen.as<ull>(), s->d_doff.as<ull>(), N + 1, st, &tb_scan));
+    SLX_CHK(s->d_tmp.ensure(std::max(tb_sort, tb_scan) + 8));
+    SLX_HIPCHK(hipcub::DeviceRadixSort::SortPairs(s->d_tmp.p, tb_sort, s->d_key_in.as<ull>(), s->d_key_out.as<ull>(), s->d_ord_in.as<uint32_t>(), s->d_ord_out.as<uint32_t>(), N, 0, end_bit, st));
     k_sort_perm<<<grid, 256, 0, st>>>(s->d_ord_out.as<uint32_t>(), s->d_len.as<uint32_t>(), s->d_src.as<ull>(), N, s->d_slen.as<ull>(), s->d_ssrc.as<ull>());
-    SORT_HIPCHK(hipGetLastError());
-    SORT_HIPCHK(hipcub::DeviceScan::ExclusiveSum(s->d_tmp.p, tb_scan, s->d_slen.as<ull>(), s->d_doff.as<ull>(), N + 1, st));
-    SORT_HIPCHK(hipEventRecord(s->ev[1], st));
-    SORT_HIPCHK(slx_wait_stream(st));
-    s->us_sort += sort_ev_us(s->ev[0], s->ev[1]);
+    SLX_HIPCHK(hipGetLastError());
+    SLX_CHK(slx_exclusive_sum(s->d_tmp, s->d_slen.as<ull>(), s->d_doff.as<ull>(), N + 1, st, 8));
+    SLX_HIPCHK(hipEventRecord(s->ev[1], st));
+    SLX_HIPCHK(slx_wait_stream(st));
+    s->us_sort += slx_ev_us(s->ev[0], s->ev[1]);
     return SLX_OK;
 }
 
@@ -280,27 +251,27 @@ static int sort_gather(slx_sort *s, uint64_t tile0, uint64_t tile_end, uint8_t *
     hipStream_t st = s->st;
     const uint64_t grid = (tile_end - tile0 + 3) / 4;
     if (grid > 0x7fffffffull) { slx_set_error("sorter: %llu tiles in one gather are more than a grid holds", (ull)(tile_end - tile0)); return SLX_EUNSUPPORTED; }
-    SORT_HIPCHK(hipSetDevice(s->device));          // (the writer selects its own device in every call between two gathers)
-    SORT_HIPCHK(hipEventRecord(s->ev[0], st));
+    SLX_HIPCHK(hipSetDevice(s->device));          // (the writer selects its own device in every call between two gathers)
+    SLX_HIPCHK(hipEventRecord(s->ev[0], st));
     k_sort_gather<<<(unsigned)grid, 256, 0, st>>>(s->d_doff.as<ull>(), s->d_ssrc.as<ull>(), (int64_t)s->held_records, s->held_bytes, tile0, tile_end, out);
-    SORT_HIPCHK(hipGetLastError());
-    SORT_HIPCHK(hipEventRecord(s->ev[1], st));
-    SORT_HIPCHK(slx_wait_stream(st));
-    s->us_gather += sort_ev_us(s->ev[0], s->ev[1]);
+    SLX_HIPCHK(hipGetLastError());
+    SLX_HIPCHK(hipEventRecord(s->ev[1], st));
+    SLX_HIPCHK(slx_wait_stream(st));
+    s->us_gather += slx_ev_us(s->ev[0], s->ev[1]);
     return SLX_OK;
 }
 
 static int sort_finish_impl(slx_sort *s, slx_bgzf *w)
 {
     if (s->held_records == 0) return SLX_OK;
-    SORT_HIPCHK(hipSetDevice(s->device));
-    SORT_CHK(sort_tables(s));
+    SLX_HIPCHK(hipSetDevice(s->device));
+    SLX_CHK(sort_tables(s));
     const uint64_t B = s->held_bytes, n_tiles = (B + RS_TILE - 1) / RS_TILE, slab_tiles = (uint64_t)s->slab_bytes / RS_TILE;
-    SORT_CHK(s->d_slab.ensure((size_t)std::min<uint64_t>(n_tiles, slab_tiles) * RS_TILE));
+    SLX_CHK(s->d_slab.ensure((size_t)std::min<uint64_t>(n_tiles, slab_tiles) * RS_TILE));
     for (uint64_t t = 0; t < n_tiles; t += slab_tiles) {
         const uint64_t te = std::min(n_tiles, t + slab_tiles), bytes = std::min(B, te * RS_TILE) - t * RS_TILE;
-        SORT_CHK(sort_gather(s, t, te, s->d_slab.as<uint8_t>()));
-        SORT_CHK(slx_bgzf_write_device(w, s->d_slab.p, (int64_t)bytes));          // staged when it returns: the slab is free for the next range of tiles
+        SLX_CHK(sort_gather(s, t, te, s->d_slab.as<uint8_t>()));
+        SLX_CHK(slx_bgzf_write_device(w, s->d_slab.p, (int64_t)bytes));          // staged when it returns: the slab is free for the next range of tiles
         ++s->c_slabs;
     }
     return SLX_OK;
@@ -330,17 +301,17 @@ extern "C" int slx_sort_to_host(slx_sort *s, void *dst, uint64_t cap, uint64_t *
     const uint64_t B = s->held_bytes, N = s->held_records;
     if (B > cap || (B && !dst)) { slx_set_error("slx_sort_to_host: %llu bytes do not fit the %llu given", (ull)B, (ull)cap); return SLX_EINVAL; }
     if (N == 0) { if (rec_off_dst) rec_off_dst[0] = 0; return SLX_OK; }
-    SORT_HIPCHK(hipSetDevice(s->device));
+    SLX_HIPCHK(hipSetDevice(s->device));
     auto run = [&]() -> int {
-        SORT_CHK(sort_tables(s));
+        SLX_CHK(sort_tables(s));
         const uint64_t n_tiles = (B + RS_TILE - 1) / RS_TILE;
-        SORT_CHK(s->d_slab.ensure((size_t)n_tiles * RS_TILE));
-        SORT_CHK(sort_gather(s, 0, n_tiles, s->d_slab.as<uint8_t>()));
+        SLX_CHK(s->d_slab.ensure((size_t)n_tiles * RS_TILE));
+        SLX_CHK(sort_gather(s, 0, n_tiles, s->d_slab.as<uint8_t>()));
         ++s->c_slabs;
-        SORT_HIPCHK(hipMemcpyAsync(dst, s->d_slab.p, B, hipMemcpyDeviceToHost, s->st));
-        if (rec_off_dst) SORT_HIPCHK(hipMemcpyAsync(rec_off_dst, s->d_doff.p, 8 * (N + 1), hipMemcpyDeviceToHost, s->st));
-        if (perm_dst) SORT_HIPCHK(hipMemcpyAsync(perm_dst, s->d_ord_out.p, 4 * N, hipMemcpyDeviceToHost, s->st));
-        SORT_HIPCHK(hipStreamSynchronize(s->st));
+        SLX_HIPCHK(hipMemcpyAsync(dst, s->d_slab.p, B, hipMemcpyDeviceToHost, s->st));
+        if (rec_off_dst) SLX_HIPCHK(hipMemcpyAsync(rec_off_dst, s->d_doff.p, 8 * (N + 1), hipMemcpyDeviceToHost, s->st));
+        if (perm_dst) SLX_HIPCHK(hipMemcpyAsync(perm_dst, s->d_ord_out.p, 4 * N, hipMemcpyDeviceToHost, s->st));
+        SLX_HIPCHK(hipStreamSynchronize(s->st));
         return SLX_OK;
     };
     const int rc = run();
@@ -364,12 +335,12 @@ static int sort_file_impl(slx_sort *s, slx_bam *rd, const char *out_path, bool *
 {
     for (;;) {
         slx_bam_batch b;
-        SORT_CHK(slx_bam_next(rd, s->batch_bytes, &b));
+        SLX_CHK(slx_bam_next(rd, s->batch_bytes, &b));
         if (b.n_records == 0) break;
-        SORT_CHK(slx_sort_add_device(s, b.d_stream, b.n_bytes, b.d_rec_off, b.n_records));
+        SLX_CHK(slx_sort_add_device(s, b.d_stream, b.n_bytes, b.d_rec_off, b.n_records));
     }
     const char *text = nullptr; int64_t l_text = 0; int n_ref = 0;
-    SORT_CHK(slx_bam_header(rd, &text, &l_text, &n_ref));
+    SLX_CHK(slx_bam_header(rd, &text, &l_text, &n_ref));
     const std::string so = recsort_header_so(std::string(text, (size_t)l_text));
     std::string h("BAM\1", 4);
     sort_put32(h, (uint32_t)so.size());
@@ -382,7 +353,7 @@ static int sort_file_impl(slx_sort *s, slx_bam *rd, const char *out_path, bool *
         sort_put32(h, (uint32_t)slx_bam_ref_len(rd, i));
     }
     slx_bgzf *w = nullptr;
-    SORT_CHK(slx_bgzf_open(out_path, s->device, &w));
+    SLX_CHK(slx_bgzf_open(out_path, s->device, &w));
     *created = true;
     int rc = slx_bgzf_write(w, h.data(), (int64_t)h.size());
     if (rc == SLX_OK) rc = slx_bgzf_flush(w);          // the records start in a member of their own, as BamWriter::WriteHeader leaves them
@@ -401,9 +372,9 @@ extern "C" int slx_sort_file_ex(slx_sort *s, const char *in_path, const char *ou
         return SLX_EINVAL;
     }
     if (s->held_records) { slx_set_error("slx_sort_file_ex: the sorter holds %llu records; it must be empty", (ull)s->held_records); return SLX_EINVAL; }
-    SORT_HIPCHK(hipSetDevice(s->device));
+    SLX_HIPCHK(hipSetDevice(s->device));
     slx_bam *rd = nullptr;
-    SORT_CHK(slx_bam_open(in_path, s->device, &rd));
+    SLX_CHK(slx_bam_open(in_path, s->device, &rd));
     bool created = false;
     const int rc = sort_file_impl(s, rd, out_path, &created);
     std::string msg = rc != SLX_OK ? slx_last_error() : "";
@@ -425,9 +396,10 @@ extern "C" int slx_sort_file(const char *in_path, const char *out_path, int devi
         slx_set_error("slx_sort_file: '%s' -> '%s': the output must be another file than the input, and neither is a pipe", in_path, out_path);
         return SLX_EINVAL;
     }
-    SORT_CHK(sort_no_device("slx_sort_file"));
+    int ndev = 0;
+    SLX_CHK(slx_count_devices(sort_no_device("slx_sort_file").c_str(), &ndev));
     slx_sort *s = nullptr;
-    SORT_CHK(slx_sort_create(device, &s));
+    SLX_CHK(slx_sort_create(device, &s));
     const int rc = slx_sort_file_ex(s, in_path, out_path);
     std::string msg = rc != SLX_OK ? slx_last_error() : "";
     slx_sort_free(s);
