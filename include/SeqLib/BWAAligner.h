@@ -21,6 +21,8 @@
 // alignToBam (new) is the file -> align -> file form: the records of alignSequences are built on the GPU from the device-resident hits (slx_rec_build,
 // include/seqlib_amd_rec.h) and handed to a UseGpu() BamWriter where they lie (BamWriter::WriteDevice); no BamRecord is made and the host copies nothing down.
 // From the same lrand48 state the file is byte for byte the one alignSequences + WriteRecords of every read's vector, in order, write through such a writer.
+// A SAM writer opened after UseGpuSam() takes the records the same way (slx_samw_write_device, include/seqlib_amd_samw.h): the SAM text is formatted on the GPU
+// and is byte for byte what alignSequences + WriteRecords write through a host BamWriter(SAM).
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -375,7 +377,7 @@ public:
     // The records alignSequences(reads, ...) would produce, written to `w` in read order without ever existing on the host: per chunk the reads and names go up
     // from pinned staging (packed by the host threads while the chunk before is on the GPU), slx_align_batch_device leaves the hits in HBM, slx_rec_build turns them
     // into the record stream and w.WriteDevice stages it for the GPU deflater.  Read i takes lrand48 draw i of the call, as in alignSequences.  Returns the number of
-    // records written.  Throws as alignSequences does; std::invalid_argument for a writer that is not an open BAM writer with UseGpu(), with UseBwaMemRecords(true)
+    // records written.  Throws as alignSequences does; std::invalid_argument for a writer that is neither an open BAM writer with UseGpu() nor an open SAM writer with UseGpuSam(), with UseBwaMemRecords(true)
     // (XA / SA / MD are host-built) and for a multi-device aligner; std::runtime_error when a read cannot be a BAM record (a name beyond 254 bytes, more than 65 535
     // CIGAR operations): nothing of that chunk is written and the writer stays usable.  Comments (BC:Z) are not carried.
     size_t alignToBam(const UnalignedSequenceVector &reads, BamWriter &w, bool hardclip, double keepSecFrac, int maxSecondary) const
@@ -629,7 +631,7 @@ private:
     }
     void check_bam_target(const BamWriter &w) const
     {
-        if (!w.IsGpuBam()) throw std::invalid_argument("BWAAligner::alignToBam: the writer must be an open BAM writer with UseGpu() (records are handed over in HBM)");
+        if (!w.IsGpuBam() && !w.IsGpuSam()) throw std::invalid_argument("BWAAligner::alignToBam: the writer must be an open BAM writer with UseGpu() or an open SAM writer with UseGpuSam() (records are handed over in HBM)");
         if (memopt_.flag & SLX_F_REG2SAM) throw std::invalid_argument("BWAAligner::alignToBam: UseBwaMemRecords records carry host-built XA / SA / MD tags; use alignSequences + WriteRecords");
     }
 

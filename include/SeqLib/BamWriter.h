@@ -21,6 +21,12 @@
 // with SO:coordinate, the records of WriteRecord(s) and WriteDevice go into a sorter in HBM in call order, Close() sorts them there -- tid ascending as unsigned,
 // then pos, ties in call order -- and writes them; BuildIndex() afterwards succeeds.  Everything must fit the sorter's budget in HBM (half of what is free at
 // Open()); what does not is refused by the write that passes it.  No host fallback.  Without SortByCoordinate() the writer behaves exactly as before.
+// UseGpuSam() before Open() moves a SAM writer's formatting to the GPU (slx_samw_*, include/seqlib_amd_samw.h): WriteRecord(s) serialise the records and hand them
+// over, WriteDevice(d, n, d_rec_off, n_records) takes records that lie in HBM -- which is what BWAAligner::alignToBam calls, so that it writes SAM -- and the text
+// is byte for byte what the host writer writes (format_sam below is the definition).  With bgzip the text leaves through the GPU BGZF writer as a bgzip'd SAM.
+// A record the host writer would also refuse (a reference id outside the header, a cut optional field) fails the call and nothing of that call's records is
+// written; B arrays of subtype d, which the host writer prints, are refused here.  No fallback: without a GPU Open() then returns false.  Without UseGpuSam() a
+// SAM writer is what it was: format_sam on the calling thread, no GPU touched, WriteDevice refused.
 #pragma once
 #include <cstdio>
 #include <algorithm>
@@ -34,6 +40,7 @@
 #include "SeqLib/BamRecord.h"
 #include "seqlib_amd_bam.h"
 #include "seqlib_amd_sort.h"
+#include "seqlib_amd_samw.h"
 
 namespace SeqLib {
 
@@ -59,7 +66,7 @@ public:
 
     void SetHeader(const BamHeader &h) { hdr = h; }
     BamHeader Header() const { return hdr; }
-    bool IsOpen() const { return fop != nullptr || gz != nullptr; }
+    bool IsOpen() const { return fop != nullptr || gz != nullptr || samw != nullptr; }
 
     // BAM only, before Open(): the BGZF members are compressed on GPU `device` (-1: the current one) instead of by zlib on the calling thread
     bool UseGpu(int device = -1)
@@ -69,6 +76,17 @@ public:
         use_gpu = true; gpu_device = device;
         return true;
     }
+
+    // SAM only, before Open(): the lines are formatted on GPU `device` (-1: the current one); bgzip: the file is a bgzip'd SAM, compressed there too
+    bool UseGpuSam(int device = -1, bool bgzip = false)
+    {
+        if (IsOpen()) { std::cerr << "BamWriter::UseGpuSam - call it before Open()" << std::endl; return false; }
+        if (output_format != "w") { std::cerr << "BamWriter::UseGpuSam - only SAM output is formatted on the GPU (UseGpu() is for BAM)" << std::endl; return false; }
+        use_gpu_sam = true; gpu_device = device; sam_bgzip = bgzip;
+        return true;
+    }
+    bool IsGpuSam() const { return samw != nullptr; }         // an open SAM writer whose lines are formatted on the GPU
+    int64_t GpuSamCounter(const char *name) const { return samw ? slx_samw_counter(samw, name) : -1; }          // slx_samw_counter of the open GPU SAM writer
 
     // after UseGpu(), before Open(): the records are coordinate-sorted in HBM at Close() (see the top of the file)
     bool SortByCoordinate()
@@ -89,6 +107,14 @@ public:
         if (output_format == "wc") {
             std::cerr << "BamWriter::Open - CRAM output needs htslib; not available in the MI355X drop-in" << std::endl;
             return false;
+        }
+        if (use_gpu_sam) {
+            if (slx_samw_open(f.c_str(), gpu_device, sam_bgzip ? SLX_SAMW_BGZF : 0, &samw) != SLX_OK) {
+                std::cerr << "BamWriter::Open - " << slx_last_error() << std::endl;
+                samw = nullptr;
+                return false;
+            }
+            return true;
         }
         if (use_gpu) {
             if (slx_bgzf_open(f.c_str(), gpu_device, &gz) != SLX_OK) {
@@ -128,6 +154,13 @@ public:
             (void)slx_sort_header(text.data(), (int64_t)text.size(), &so[0], (int64_t)so.size());
             text.swap(so);
         }
+        if (samw) {                                  // the names become the RNAME / RNEXT table in HBM
+            std::vector<std::string> names;
+            std::vector<const char *> ptr;
+            for (int i = 0; i < hdr.NumSequences(); ++i) names.push_back(hdr.IDtoName(i));
+            for (const std::string &nm : names) ptr.push_back(nm.c_str());
+            return gpu_ok(slx_samw_header(samw, text.data(), (int64_t)text.size(), ptr.data(), (int)ptr.size()));
+        }
         if (output_format == "w") return std::fwrite(text.data(), 1, text.size(), fop) == text.size();
         std::string h("BAM\1", 4);
         put32(h, (uint32_t)text.size());
@@ -149,6 +182,12 @@ public:
         if (!IsOpen()) return false;
         const bam1_t *b = r.raw();
         if (!b) return false;
+        if (samw) {
+            many.clear();
+            put_record(b, many);
+            const uint64_t off[2] = {0, many.size()};
+            return gpu_ok(slx_samw_write_host(samw, many.data(), (int64_t)many.size(), off, 1));
+        }
         if (output_format == "w") {
             std::string line;
             if (!format_sam(b, line)) return false;
@@ -166,6 +205,15 @@ public:
     bool WriteRecords(const BamRecordPtrVector &recs)
     {
         if (!IsOpen()) return false;
+        if (samw) {                                  // serialised with their offsets into the reused buffers, one slx_samw_write_host
+            many.clear(); sort_off.assign(1, 0);
+            for (const BamRecordPtr &r : recs) {
+                const bam1_t *b = r ? r->raw() : nullptr;
+                if (!b) return false;
+                put_record(b, many); sort_off.push_back(many.size());
+            }
+            return gpu_ok(slx_samw_write_host(samw, many.data(), (int64_t)many.size(), sort_off.data(), (int64_t)sort_off.size() - 1));
+        }
         if (!gz) {
             for (const BamRecordPtr &r : recs) if (!r || !WriteRecord(*r)) return false;
             return true;
@@ -192,6 +240,7 @@ public:
     // false with a message for a SAM writer, a host-zlib writer and a closed writer.
     bool WriteDevice(const void *d, int64_t n)
     {
+        if (samw) { std::cerr << "BamWriter::WriteDevice - a GPU SAM writer needs the records' offsets: use WriteDevice(d, n, d_rec_off, n_records)" << std::endl; return false; }
         if (output_format != "wb") { std::cerr << "BamWriter::WriteDevice - only BAM output takes records from the GPU" << std::endl; return false; }
         if (!IsOpen()) { std::cerr << "BamWriter::WriteDevice - Output not open for writing. Open with Open()" << std::endl; return false; }
         if (!gz) { std::cerr << "BamWriter::WriteDevice - the writer compresses on the host; call UseGpu() before Open()" << std::endl; return false; }
@@ -202,6 +251,7 @@ public:
     // sorter (slx_sort_add_device), any other GPU writer ignores the offsets and does what WriteDevice(d, n) does
     bool WriteDevice(const void *d, int64_t n, const void *d_rec_off, int64_t n_records)
     {
+        if (samw) return gpu_ok(slx_samw_write_device(samw, d, n, d_rec_off, n_records));
         if (!sorter) return WriteDevice(d, n);
         return sort_flush() && gpu_ok(slx_sort_add_device(sorter, d, n, d_rec_off, n_records));          // (what the host wrote before comes before)
     }
@@ -210,6 +260,11 @@ public:
 
     bool Close()
     {
+        if (samw) {
+            const bool ok = gpu_ok(slx_samw_close(samw));    // what is in flight reaches the file; the handle is freed
+            samw = nullptr;
+            return ok;
+        }
         if (gz) {
             bool ok = true;
             if (sorter) {                                    // the sort, and the sorted stream into the writer
@@ -423,6 +478,9 @@ private:
     int gpu_device = -1;
     slx_bgzf *gz = nullptr;         // the open GPU writer
     std::string many;               // WriteRecords' reused buffer
+    bool use_gpu_sam = false;       // UseGpuSam(): the SAM lines are formatted on the GPU
+    bool sam_bgzip = false;
+    slx_samw *samw = nullptr;       // the open GPU SAM writer
     static constexpr size_t SORT_STAGE = (size_t)16 << 20;          // serialised bytes that make one slx_sort_add_host
     bool sort_on = false;           // SortByCoordinate()
     slx_sort *sorter = nullptr;     // of the open sorting writer
