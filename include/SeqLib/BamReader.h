@@ -37,6 +37,7 @@ namespace SeqLib {
 
 class BamReader {
     friend class BWAAligner;
+    friend class STCoverage;          // addReads(BamReader&): the batches as they lie in HBM
 public:
     BamReader() = default;
     BamReader(const BamReader &) = delete;
