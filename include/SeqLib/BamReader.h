@@ -38,6 +38,7 @@ namespace SeqLib {
 class BamReader {
     friend class BWAAligner;
     friend class STCoverage;          // addReads(BamReader&): the batches as they lie in HBM
+    friend class BamStats;
 public:
     BamReader() = default;
     BamReader(const BamReader &) = delete;
