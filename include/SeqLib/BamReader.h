@@ -39,6 +39,7 @@ class BamReader {
     friend class BWAAligner;
     friend class STCoverage;          // addReads(BamReader&): the batches as they lie in HBM
     friend class BamStats;
+    friend class RefGenome;           // NmMd(BamReader&): the same
 public:
     BamReader() = default;
     BamReader(const BamReader &) = delete;
