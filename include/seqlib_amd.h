@@ -270,6 +270,10 @@ uint64_t slx_lrand48_advance(uint64_t state, uint64_t n);   /* state after n dra
 uint64_t slx_lrand48_peek_libc(void);                       /* this process's current libc state */
 void     slx_lrand48_skip_libc(uint64_t n);                 /* advance the libc state by n draws */
 
+/* diagnostics and tests: bytes of HBM (pinned = 0) or of pinned host memory (pinned != 0) that the grow-only buffers of every live handle of the I/O and pipeline
+ * units hold right now, process-wide.  A handle's free gives back what its create and its calls took: the figure before a create equals the figure after the free. */
+int64_t slx_hip_live_bytes(int pinned);
+
 const char *slx_last_error(void);
 const char *slx_version(void);
 

@@ -23,6 +23,7 @@ EXPORTS = [
     "slx_aligner_free", "slx_aligner_set", "slx_align_batch", "slx_align_batch_device", "slx_hits_free", "slx_hits_packed_size", "slx_hits_pack",
     "slx_aligner_stage_ms", "slx_stage_name", "slx_aligner_probe_ms", "slx_debug_stage", "slx_lrand48_advance", "slx_lrand48_peek_libc", "slx_lrand48_skip_libc",
     "slx_last_error", "slx_version", "slx_device_count", "slx_aligner_probe_launches", "slx_aligner_counter", "slx_host_alloc", "slx_host_free", "slx_host_trim",
+    "slx_hip_live_bytes",
 ]
 
 
@@ -100,6 +101,8 @@ def lib():
     L.slx_host_alloc.argtypes = [C.c_uint64]
     L.slx_host_alloc.restype = C.c_void_p
     L.slx_host_free.argtypes = [C.c_void_p]
+    L.slx_hip_live_bytes.argtypes = [C.c_int]
+    L.slx_hip_live_bytes.restype = C.c_int64
     _LIB = L
     return L
 

@@ -114,26 +114,23 @@ struct FqProducer {
 };
 
 // ------------------------------------------------------------------ the source and the text window
-struct FqText {
+struct FqText : SlxGpu<10> {          // the device, the stream and the events; a reader built on it hangs its own buffers on it too
     const char *who = "FASTQ reader";          // the reader's name in messages
     std::string path;
-    int device = 0, source = 0;                // source: 0 plain, 1 BGZF, 2 gzip
-    hipStream_t st = nullptr;
-    hipEvent_t ev[10] = {};
+    int source = 0;                            // 0 plain, 1 BGZF, 2 gzip
     // BGZF: the file mapped, its members
     int fd = -1; const uint8_t *map = nullptr; uint64_t fsize = 0;
     std::vector<slx_bam_member> mem; int64_t next_member = 0;
     FqProducer prod;
     // the text window: d_text[cur][used, have) is text not yet delivered, [0, used) has been
-    FqDBuf d_text[2]; int cur = 0; uint64_t have = 0, used = 0; bool src_eof = false;
+    FqDBuf d_text[2] = {*this, *this}; int cur = 0; uint64_t have = 0, used = 0; bool src_eof = false;
     uint32_t tile_bytes = 4096;
     bgzf_stage stage;                    // slx_bgzf_inflate_members' buffers
-    FqDBuf d_count, d_base, d_tmp, d_line;
-    FqHBuf h_small;
+    FqDBuf d_count{*this}, d_base{*this}, d_tmp{*this}, d_line{*this};
+    FqHBuf h_small{*this};
     float us[4] = {0, 0, 0, 0};          // lines, check, gather, inflate
     int64_t c_members = 0;               // BGZF members inflated since the last fq_text_start
-    std::vector<FqDBuf *> text_dbufs() { return {&d_text[0], &d_text[1], &d_count, &d_base, &d_tmp, &d_line}; }
-    std::vector<FqHBuf *> text_hbufs() { return {&h_small}; }
+    std::vector<FqDBuf *> text_dbufs() { return {&d_text[0], &d_text[1], &d_count, &d_base, &d_tmp, &d_line}; }          // for a reader that gives the window back early (slx_ref.hip)
 };
 
 // the kind of source from the file's first bytes, the BGZF member table, the device, the stream and the events.  SLX_ENODEVICE without a GPU

@@ -478,11 +478,8 @@ extern "C" void slx_bam_members_free(slx_bam_member *members) { free(members); }
 typedef SlxDevBuf<SlxMargin<4, 256>> BamDBuf;
 typedef SlxPinBuf<SlxMargin<4, 256>> BamHBuf;
 
-struct slx_bam {
+struct slx_bam : SlxGpu<10> {
     BamFile f;
-    int device = 0;
-    hipStream_t st = nullptr;
-    hipEvent_t ev[10] = {};
     std::string text;
     std::vector<std::string> ref_names;
     std::vector<int64_t> ref_lens;
@@ -491,9 +488,10 @@ struct slx_bam {
     uint64_t chunk_bytes = 65536;
     int idx_fail = 0;
     bgzf_stage stage;                                      // slx_bgzf_inflate_members' buffers
-    BamDBuf d_out, d_guess, d_used, d_exit_a, d_exit_b, d_count, d_base, d_state, d_rec, d_keep, d_blen, d_kidx, d_boff, d_tmp, d_bases, d_offs, d_map;
-    BamDBuf d_cs, d_cr;                                    // region mode: the kept records compacted, and their offsets
-    BamHBuf h_out, h_rec, h_state, h_map;
+    BamDBuf d_out{*this}, d_guess{*this}, d_used{*this}, d_exit_a{*this}, d_exit_b{*this}, d_count{*this}, d_base{*this}, d_state{*this}, d_rec{*this}, d_keep{*this}, d_blen{*this},
+            d_kidx{*this}, d_boff{*this}, d_tmp{*this}, d_bases{*this}, d_offs{*this}, d_map{*this};
+    BamDBuf d_cs{*this}, d_cr{*this};                      // region mode: the kept records compacted, and their offsets
+    BamHBuf h_out{*this}, h_rec{*this}, h_state{*this}, h_map{*this};
     int64_t c_members_done = 0, c_repaired = 0, c_rounds = 0, c_records = 0, c_region_cand = 0, c_region_kept = 0;
     float us[5] = {0, 0, 0, 0, 0};
     const void *map_stream = nullptr; int64_t map_reads = 0; // the batch slx_bam_reads_device last unpacked (d_bases, d_offs, d_map hold its reads), and how many
@@ -508,18 +506,13 @@ struct slx_bam {
     int64_t piece_cur = -1;                                // next member of pieces[piece_i]; -1: not begun
     bool region_mode = false;
     slx_filter *flt = nullptr;                             // a read filter attached by slx_filter_attach; nullptr: nothing new is launched
-    BamDBuf d_fkeep;                                       // its keep bytes
+    BamDBuf d_fkeep{*this};                                     // its keep bytes
     slx_samsrc *sam = nullptr;                             // a reader over SAM text (slx_sam_open): the batches come from slx_sam.hip, there are no members
-    std::vector<BamDBuf *> dbufs() { return {&d_fkeep, &d_out, &d_guess, &d_used, &d_exit_a, &d_exit_b, &d_count, &d_base, &d_state, &d_rec, &d_keep, &d_blen, &d_kidx, &d_boff, &d_tmp, &d_bases, &d_offs, &d_map, &d_cs, &d_cr}; }
-    std::vector<BamHBuf *> hbufs() { return {&h_out, &h_rec, &h_state, &h_map}; }
 };
 
 static int bam_dev_init(slx_bam *rd, int device)
 {
-    SLX_CHK(slx_pick_device(device, "no HIP device: the BAM reader inflates and indexes on MI355X only (no CPU fallback)", "BAM reader", &rd->device));
-    SLX_HIPCHK(hipStreamCreateWithFlags(&rd->st, hipStreamNonBlocking));
-    for (auto &e : rd->ev) SLX_HIPCHK(hipEventCreate(&e));
-    return SLX_OK;
+    return rd->open(device, "BAM reader", "no HIP device: the BAM reader inflates and indexes on MI355X only (no CPU fallback)");
 }
 
 static void bam_dev_free(slx_bam *rd)
@@ -528,12 +521,8 @@ static void bam_dev_free(slx_bam *rd)
         (void)hipSetDevice(rd->device);
         (void)hipStreamSynchronize(rd->st);
     }
-    for (BamDBuf *b : rd->dbufs()) b->release();
-    for (BamHBuf *b : rd->hbufs()) b->release();
-    rd->stage.release();
-    for (auto &e : rd->ev) if (e) (void)hipEventDestroy(e);
-    if (rd->st) (void)hipStreamDestroy(rd->st);
-    rd->st = nullptr;
+    rd->stage.release();          // (dev_inflate.h's staging buffers: they have no owner, the stream has drained)
+    rd->close();
 }
 
 // members [a, b) inflated to d_out[dst_off ..), CRC-checked; d_out holds out_bytes.  Returns after the stream has drained.
@@ -1066,9 +1055,10 @@ extern "C" int slx_bam_next(slx_bam *rd, int64_t max_bytes, slx_bam_batch *out)
 
 // ------------------------------------------------------------------ the BAI build
 namespace {
-struct BaiBuild {
-    BamDBuf ne_start, ne_file, lin_off, lin, first, last, n_map, n_unmap, n_intv, bst, carry, key, tp, vbeg, vend, head, hidx, ckey, cbeg, cend, skey, sidx_in, sidx, tmp;
-    ~BaiBuild() { for (BamDBuf *b : {&ne_start, &ne_file, &lin_off, &lin, &first, &last, &n_map, &n_unmap, &n_intv, &bst, &carry, &key, &tp, &vbeg, &vend, &head, &hidx, &ckey, &cbeg, &cend, &skey, &sidx_in, &sidx, &tmp}) b->release(); }
+struct BaiBuild : SlxBufOwner {          // the scratch of one build: it goes with the call
+    BamDBuf ne_start{*this}, ne_file{*this}, lin_off{*this}, lin{*this}, first{*this}, last{*this}, n_map{*this}, n_unmap{*this}, n_intv{*this}, bst{*this}, carry{*this}, key{*this},
+            tp{*this}, vbeg{*this}, vend{*this}, head{*this}, hidx{*this}, ckey{*this}, cbeg{*this}, cend{*this}, skey{*this}, sidx_in{*this}, sidx{*this}, tmp{*this};
+    ~BaiBuild() { release_bufs(); }
 };
 void put_u32(std::string &o, uint32_t v) { o.append((const char *)&v, 4); }
 void put_u64(std::string &o, uint64_t v) { o.append((const char *)&v, 8); }
@@ -1166,10 +1156,9 @@ static int bai_build_body(slx_bam *rd, int64_t batch_bytes, BaiBuild &B, std::st
         SLX_CHK(B.skey.ensure(8 * nc)); SLX_CHK(B.sidx_in.ensure(4 * nc)); SLX_CHK(B.sidx.ensure(4 * nc));
         k_bai_iota<<<(unsigned)((nc + 255) / 256), 256, 0, st>>>(B.sidx_in.as<uint32_t>(), nc);
         SLX_HIPCHK(hipGetLastError());
-        size_t tb = 0;
-        SLX_HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, B.ckey.as<ull>(), B.skey.as<ull>(), B.sidx_in.as<uint32_t>(), B.sidx.as<uint32_t>(), (int)nc, 0, 64, st));
-        SLX_CHK(B.tmp.ensure(tb + 8));
-        SLX_HIPCHK(hipcub::DeviceRadixSort::SortPairs(B.tmp.p, tb, B.ckey.as<ull>(), B.skey.as<ull>(), B.sidx_in.as<uint32_t>(), B.sidx.as<uint32_t>(), (int)nc, 0, 64, st));
+        SLX_CHK(slx_cub("the BAI build's hipcub::DeviceRadixSort::SortPairs", B.tmp, 8, [&](void *t, size_t &b) {
+            return hipcub::DeviceRadixSort::SortPairs(t, b, B.ckey.as<ull>(), B.skey.as<ull>(), B.sidx_in.as<uint32_t>(), B.sidx.as<uint32_t>(), (int)nc, 0, 64, st);
+        }));
         SLX_CHK(down(skey.data(), B.skey.p, 8 * nc)); SLX_CHK(down(sidx.data(), B.sidx.p, 4 * nc)); SLX_CHK(down(cbeg.data(), B.cbeg.p, 8 * nc)); SLX_CHK(down(cend.data(), B.cend.p, 8 * nc));
     }
     if (n_ref) {

@@ -77,20 +77,18 @@ typedef SlxPinBuf<SlxExact> HBuf;
 
 static const unsigned char BGZF_EOF[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
-struct slx_bgzf {
+struct slx_bgzf : SlxGpu<4> {          // st is the worker's stream
     FILE *fp = nullptr;
     bool is_stdout = false;
     std::string path;
-    int device = 0;
-    hipStream_t st_stage = nullptr, st_work = nullptr;
-    hipEvent_t ev[4] = {};
+    hipStream_t st_stage = nullptr;          // the caller's copies into d_in: the unit's own, beside the context's
     int64_t batch_bytes = 64ll << 20;
-    DBuf d_in[2];                   // the two input segments
+    DBuf d_in[2] = {*this, *this};                  // the two input segments
     int cur = 0;                    // the one being filled
     uint64_t fill = 0;
     // the worker's buffers: one batch is compressed at a time
-    DBuf d_slots, d_tok, d_size, d_off, d_flag, d_tmp, d_pack;
-    HBuf h_pack, h_flag, h_total;
+    DBuf d_slots{*this}, d_tok{*this}, d_size{*this}, d_off{*this}, d_flag{*this}, d_tmp{*this}, d_pack{*this};
+    HBuf h_pack{*this}, h_flag{*this}, h_total{*this};
     std::thread worker;
     bool worker_on = false;
     int worker_rc = SLX_OK;         // of the batch in flight; read after join
@@ -113,7 +111,7 @@ static int bgzf_compress(slx_bgzf *w, int set, uint64_t bytes)
 {
     SLX_HIPCHK(hipSetDevice(w->device));
     const int n = (int)((bytes + DEF_MEMBER - 1) / DEF_MEMBER);
-    hipStream_t st = w->st_work;
+    hipStream_t st = w->st;
     SLX_CHK(w->d_slots.ensure((size_t)n * BGZF_SLOT));
     SLX_CHK(w->d_tok.ensure((size_t)n * DEF_MEMBER * 4));          // the token arena, computed from the batch: one token per input byte at most
     SLX_CHK(w->d_size.ensure(sizeof(ull) * ((size_t)n + 1)));
@@ -190,16 +188,13 @@ static int bgzf_submit(slx_bgzf *w, bool final)
 static void bgzf_free(slx_bgzf *w)
 {
     if (w->worker_on) { w->worker.join(); w->worker_on = false; }
-    if (w->st_work) {
+    if (w->st_stage) {
         (void)hipSetDevice(w->device);
-        (void)hipStreamSynchronize(w->st_work);
+        if (w->st) (void)hipStreamSynchronize(w->st);
         (void)hipStreamSynchronize(w->st_stage);
     }
-    for (DBuf *b : {&w->d_in[0], &w->d_in[1], &w->d_slots, &w->d_tok, &w->d_size, &w->d_off, &w->d_flag, &w->d_tmp, &w->d_pack}) b->release();
-    for (HBuf *b : {&w->h_pack, &w->h_flag, &w->h_total}) b->release();
-    for (auto &e : w->ev) if (e) (void)hipEventDestroy(e);
+    w->close();
     if (w->st_stage) (void)hipStreamDestroy(w->st_stage);
-    if (w->st_work) (void)hipStreamDestroy(w->st_work);
     if (w->fp && !w->is_stdout) std::fclose(w->fp);
     delete w;
 }
@@ -207,26 +202,19 @@ static void bgzf_free(slx_bgzf *w)
 static int bgzf_open_impl(slx_bgzf *w, const char *path, int device)
 {
     const std::string no_device = std::string("no HIP device: the BGZF writer compresses on MI355X only (no CPU fallback); '") + path + "' is not created";
-    SLX_CHK(slx_pick_device(device, no_device.c_str(), "BGZF writer", &w->device));
+    SLX_CHK(w->open(device, "BGZF writer", no_device.c_str()));
     w->path = path;
     w->is_stdout = w->path == "-";
     w->fp = w->is_stdout ? stdout : std::fopen(path, "wb");
     if (!w->fp) { slx_set_error("BGZF writer: cannot create '%s': %s", path, strerror(errno)); return SLX_EIO; }
     SLX_HIPCHK(hipStreamCreateWithFlags(&w->st_stage, hipStreamNonBlocking));
-    SLX_HIPCHK(hipStreamCreateWithFlags(&w->st_work, hipStreamNonBlocking));
-    for (auto &e : w->ev) SLX_HIPCHK(hipEventCreate(&e));
     return SLX_OK;
 }
 
 extern "C" int slx_bgzf_open(const char *path, int device, slx_bgzf **out)
 {
     if (!path || !out) { slx_set_error("slx_bgzf_open: null argument"); return SLX_EINVAL; }
-    *out = nullptr;
-    slx_bgzf *w = new slx_bgzf();
-    const int rc = bgzf_open_impl(w, path, device);
-    if (rc != SLX_OK) { bgzf_free(w); return rc; }
-    *out = w;
-    return SLX_OK;
+    return slx_create(out, bgzf_free, [&](slx_bgzf *w) { return bgzf_open_impl(w, path, device); });
 }
 
 static int bgzf_write_impl(slx_bgzf *w, const void *p, int64_t n, bool from_device)

@@ -32,8 +32,10 @@ typedef unsigned long long ull;
 typedef SlxDevBuf<SlxMargin<4, 256>> CDBuf;
 typedef SlxPinBuf<SlxMargin<4, 256>> CHBuf;
 
-struct slx_cov {
-    int device = -1;          // -1: host only
+static const char COV_NO_DEVICE[] = "no HIP device: coverage is computed on MI355X only (no CPU fallback)";
+
+struct slx_cov : SlxGpu<> {
+    slx_cov() : SlxGpu(COV_NO_DEVICE) {}
     std::vector<int64_t> len, beg, end, off;
     std::vector<std::string> names;
     uint64_t total = 0;
@@ -41,39 +43,20 @@ struct slx_cov {
     uint32_t lds_window = 8192, slice = 1024;
     uint64_t scan_chunk = 1ull << 30;
     bool settled = false;          // the array holds depths, not differences
-    hipStream_t st = nullptr;
-    hipEvent_t ev[2] = {};
-    SlxDevBuf<SlxExact> d_arr;
-    CDBuf d_geo, d_names, d_noff, d_in, d_off, d_long, d_cnt, d_tmp, d_bound, d_items, d_sums, d_len, d_at, d_text, d_max;
-    CHBuf h_cnt, h_items, h_sums, h_text[2];
+    SlxDevBuf<SlxExact> d_arr{*this};
+    CDBuf d_geo{*this}, d_names{*this}, d_noff{*this}, d_in{*this}, d_off{*this}, d_long{*this}, d_cnt{*this}, d_tmp{*this}, d_bound{*this}, d_items{*this}, d_sums{*this}, d_len{*this},
+          d_at{*this}, d_text{*this}, d_max{*this};
+    CHBuf h_cnt{*this}, h_items{*this}, h_sums{*this}, h_text[2] = {*this, *this};
     int64_t c_seen = 0, c_counted = 0, c_long = 0, c_lds = 0, c_global = 0, c_runs = 0;
     double us_add = 0, us_settle = 0;
-    std::vector<CDBuf *> dbufs() { return {&d_geo, &d_names, &d_noff, &d_in, &d_off, &d_long, &d_cnt, &d_tmp, &d_bound, &d_items, &d_sums, &d_len, &d_at, &d_text, &d_max}; }
-    std::vector<CHBuf *> hbufs() { return {&h_cnt, &h_items, &h_sums, &h_text[0], &h_text[1]}; }
     cov_geo geo() const { const int64_t *g = d_geo.as<int64_t>(); const size_t n = len.size(); return cov_geo{g, g + n, g + 2 * n, (int32_t)n, 0, (int64_t)total}; }
     int32_t *arr() const { return d_arr.as<int32_t>(); }
 };
 
-static int cov_need_gpu(const char *who, slx_cov *c)
-{
-    if (!c) { slx_set_error("%s: null object", who); return SLX_EINVAL; }
-    if (c->device < 0) { slx_set_error("%s: no HIP device: coverage is computed on MI355X only (no CPU fallback)", who); return SLX_ENODEVICE; }
-    SLX_HIPCHK(hipSetDevice(c->device));
-    return SLX_OK;
-}
-
 extern "C" void slx_cov_free(slx_cov *c)
 {
     if (!c) return;
-    if (c->device >= 0) {
-        (void)hipSetDevice(c->device);
-        if (c->st) (void)hipStreamSynchronize(c->st);
-        c->d_arr.release();
-        for (CDBuf *b : c->dbufs()) b->release();
-        for (CHBuf *b : c->hbufs()) b->release();
-        for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
-        if (c->st) (void)hipStreamDestroy(c->st);
-    }
+    c->close();
     delete c;
 }
 
@@ -95,11 +78,8 @@ static int cov_create_impl(slx_cov *c, int device, int n_ref, const int64_t *ref
     for (int i = 0; i < n_ref; ++i) kept[i] = c->end[i] - c->beg[i];
     c->off.assign((size_t)n_ref, 0);
     c->total = cov_layout(kept.data(), n_ref, c->off.data());
-    int ndev = 0;
-    if (device < 0 && (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)) { (void)hipGetLastError(); c->device = -1; return SLX_OK; }          // host only
-    SLX_CHK(slx_pick_device(device, "no HIP device: coverage is computed on MI355X only (no CPU fallback)", "slx_cov_create", &c->device));
-    SLX_HIPCHK(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
-    for (auto &e : c->ev) SLX_HIPCHK(hipEventCreate(&e));
+    SLX_CHK(c->open(device, "slx_cov_create", COV_NO_DEVICE, true));
+    if (c->device < 0) return SLX_OK;          // host only
     SLX_CHK(c->d_arr.ensure(4 * c->total + 16));
     SLX_HIPCHK(hipMemsetAsync(c->d_arr.p, 0, 4 * c->total + 16, c->st));
     std::vector<int64_t> g;
@@ -120,12 +100,7 @@ static int cov_create_impl(slx_cov *c, int device, int n_ref, const int64_t *ref
 extern "C" int slx_cov_create(int device, int n_ref, const int64_t *ref_len, const char *const *ref_names, const slx_bam_region *window, slx_cov **out)
 {
     if (!out || n_ref < 0 || (n_ref && !ref_len)) { slx_set_error("slx_cov_create: null or negative argument"); return SLX_EINVAL; }
-    *out = nullptr;
-    slx_cov *c = new slx_cov();
-    const int rc = cov_create_impl(c, device, n_ref, ref_len, ref_names, window);
-    if (rc != SLX_OK) { slx_cov_free(c); return rc; }
-    *out = c;
-    return SLX_OK;
+    return slx_create(out, slx_cov_free, [&](slx_cov *c) { return cov_create_impl(c, device, n_ref, ref_len, ref_names, window); });
 }
 
 extern "C" int slx_cov_set(slx_cov *c, const char *key, int64_t v)
@@ -175,10 +150,7 @@ static int cov_settle(slx_cov *c)
     for (uint64_t at = 0; at < c->total; at += c->scan_chunk) {
         const uint64_t n = std::min(c->scan_chunk, c->total - at);
         if (at) { k_cov_carry<<<1, 1, 0, c->st>>>(c->arr(), at); SLX_HIPCHK(hipGetLastError()); }
-        size_t tb = 0;
-        SLX_HIPCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tb, c->arr() + at, c->arr() + at, (int)n, c->st));
-        SLX_CHK(c->d_tmp.ensure(tb + 8));
-        SLX_HIPCHK(hipcub::DeviceScan::InclusiveSum(c->d_tmp.p, tb, c->arr() + at, c->arr() + at, (int)n, c->st));
+        SLX_CHK(slx_cub("hipcub::DeviceScan::InclusiveSum (coverage, settle)", c->d_tmp, 8, [&](void *t, size_t &b) { return hipcub::DeviceScan::InclusiveSum(t, b, c->arr() + at, c->arr() + at, (int)n, c->st); }));
     }
     SLX_HIPCHK(hipEventRecord(c->ev[1], c->st));
     SLX_HIPCHK(slx_wait_stream(c->st));
@@ -222,26 +194,19 @@ static int cov_add(slx_cov *c, const uint8_t *d_s, uint64_t n_bytes, const ull *
     return SLX_OK;
 }
 
-static int cov_add_args(const char *who, slx_cov *c, const void *s, int64_t n_bytes, const void *off, int64_t n)
-{
-    SLX_CHK(cov_need_gpu(who, c));
-    if (n_bytes < 0 || n < 0 || (n_bytes && !s) || (n && !off)) { slx_set_error("%s: null or negative argument", who); return SLX_EINVAL; }
-    return SLX_OK;
-}
-
 extern "C" int slx_cov_add_device(slx_cov *c, const void *d_stream, int64_t n_bytes, const void *d_rec_off, int64_t n_records)
 {
-    SLX_CHK(cov_add_args("slx_cov_add_device", c, d_stream, n_bytes, d_rec_off, n_records));
+    SLX_CHK(slx_need(c, "slx_cov_add_device"));
+    SLX_CHK(slx_batch_args("slx_cov_add_device", d_stream, n_bytes, d_rec_off, n_records));
     return cov_add(c, (const uint8_t *)d_stream, (uint64_t)n_bytes, (const ull *)d_rec_off, (uint64_t)n_records);
 }
 
 extern "C" int slx_cov_add_host(slx_cov *c, const void *stream, int64_t n_bytes, const uint64_t *rec_off, int64_t n_records)
 {
-    SLX_CHK(cov_add_args("slx_cov_add_host", c, stream, n_bytes, rec_off, n_records));
+    SLX_CHK(slx_need(c, "slx_cov_add_host"));
+    SLX_CHK(slx_batch_args("slx_cov_add_host", stream, n_bytes, rec_off, n_records));
     if (n_records == 0) return SLX_OK;
-    SLX_CHK(c->d_in.ensure((size_t)n_bytes + 8)); SLX_CHK(c->d_off.ensure(8 * ((size_t)n_records + 1)));
-    if (n_bytes) SLX_HIPCHK(hipMemcpyAsync(c->d_in.p, stream, (size_t)n_bytes, hipMemcpyHostToDevice, c->st));
-    SLX_HIPCHK(hipMemcpyAsync(c->d_off.p, rec_off, 8 * ((size_t)n_records + 1), hipMemcpyHostToDevice, c->st));
+    SLX_CHK(slx_batch_stage(c->d_in, c->d_off, 8, stream, n_bytes, rec_off, n_records, c->st));
     return cov_add(c, c->d_in.as<uint8_t>(), (uint64_t)n_bytes, c->d_off.as<ull>(), (uint64_t)n_records);
 }
 
@@ -279,7 +244,7 @@ static int cov_tid(const char *who, const slx_cov *c, int tid)
 
 extern "C" int slx_cov_depth(slx_cov *c, int tid, int64_t beg, int64_t end, int32_t *out)
 {
-    SLX_CHK(cov_need_gpu("slx_cov_depth", c));
+    SLX_CHK(slx_need(c, "slx_cov_depth"));
     SLX_CHK(cov_tid("slx_cov_depth", c, tid));
     if (beg > end || (beg < end && !out)) { slx_set_error("slx_cov_depth: null output or an interval that ends before it begins"); return SLX_EINVAL; }
     SLX_CHK(cov_settle(c));
@@ -292,7 +257,7 @@ extern "C" int slx_cov_depth(slx_cov *c, int tid, int64_t beg, int64_t end, int3
 
 extern "C" int slx_cov_depth_device(slx_cov *c, int tid, const void **d_depth, int64_t *n)
 {
-    SLX_CHK(cov_need_gpu("slx_cov_depth_device", c));
+    SLX_CHK(slx_need(c, "slx_cov_depth_device"));
     SLX_CHK(cov_tid("slx_cov_depth_device", c, tid));
     if (!d_depth || !n) { slx_set_error("slx_cov_depth_device: null argument"); return SLX_EINVAL; }
     SLX_CHK(cov_settle(c));
@@ -302,7 +267,7 @@ extern "C" int slx_cov_depth_device(slx_cov *c, int tid, const void **d_depth, i
 
 extern "C" int64_t slx_cov_at(slx_cov *c, int tid, int64_t pos)
 {
-    SLX_CHK(cov_need_gpu("slx_cov_at", c));
+    SLX_CHK(slx_need(c, "slx_cov_at"));
     if (tid < 0 || tid >= (int)c->len.size() || pos < c->beg[tid] || pos >= c->end[tid]) return 0;
     SLX_CHK(cov_settle(c));
     int32_t v = 0;
@@ -312,7 +277,7 @@ extern "C" int64_t slx_cov_at(slx_cov *c, int tid, int64_t pos)
 
 extern "C" int64_t slx_cov_max(slx_cov *c, int tid)
 {
-    SLX_CHK(cov_need_gpu("slx_cov_max", c));
+    SLX_CHK(slx_need(c, "slx_cov_max"));
     if (tid != -1) SLX_CHK(cov_tid("slx_cov_max", c, tid));
     SLX_CHK(cov_settle(c));
     const uint64_t g0 = tid < 0 ? 0 : (uint64_t)c->off[tid], g1 = tid < 0 ? c->total : g0 + (uint64_t)(c->end[tid] - c->beg[tid]);
@@ -330,7 +295,7 @@ extern "C" int64_t slx_cov_max(slx_cov *c, int tid)
 
 extern "C" int slx_cov_regions(slx_cov *c, const slx_bam_region *regs, int64_t n, int32_t min_depth, int64_t *sum, int64_t *n_at_least)
 {
-    SLX_CHK(cov_need_gpu("slx_cov_regions", c));
+    SLX_CHK(slx_need(c, "slx_cov_regions"));
     if (n < 0 || (n && (!regs || !sum || !n_at_least))) { slx_set_error("slx_cov_regions: null or negative argument"); return SLX_EINVAL; }
     for (int64_t i = 0; i < n; ++i) SLX_CHK(cov_tid("slx_cov_regions", c, regs[i].tid));
     SLX_CHK(cov_settle(c));
@@ -419,7 +384,7 @@ static int cov_bedgraph_impl(slx_cov *c, int tid, int include_zero, CovWriter &W
 
 extern "C" int slx_cov_bedgraph(slx_cov *c, int tid, int include_zero, const char *path)
 {
-    SLX_CHK(cov_need_gpu("slx_cov_bedgraph", c));
+    SLX_CHK(slx_need(c, "slx_cov_bedgraph"));
     if (!path) { slx_set_error("slx_cov_bedgraph: null path"); return SLX_EINVAL; }
     if (tid != -1) SLX_CHK(cov_tid("slx_cov_bedgraph", c, tid));
     SLX_CHK(cov_settle(c));
@@ -435,7 +400,7 @@ extern "C" int slx_cov_bedgraph(slx_cov *c, int tid, int include_zero, const cha
 
 extern "C" int slx_cov_clear(slx_cov *c)
 {
-    SLX_CHK(cov_need_gpu("slx_cov_clear", c));
+    SLX_CHK(slx_need(c, "slx_cov_clear"));
     SLX_HIPCHK(hipMemsetAsync(c->d_arr.p, 0, 4 * c->total + 16, c->st));
     SLX_HIPCHK(slx_wait_stream(c->st));
     c->settled = false;

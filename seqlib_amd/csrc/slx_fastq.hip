@@ -154,38 +154,28 @@ __global__ __launch_bounds__(256) void k_fq_gather(const fq_u64 *src, const fq_u
 struct slx_fastq : FqText {          // the source, the text window and its line starts: fq_text.h
     bool done = false;
     uint32_t gather_tile = 2048; int fast_fail = 0;
-    FqDBuf d_first, d_slow;
-    FqDBuf d_len_b, d_len_n, d_len_c, d_src_b, d_src_q, d_src_n, d_src_c, d_flags, d_off_b, d_off_n, d_off_c, d_bases, d_quals, d_names, d_coms;
-    FqHBuf h_tail, h_slow;
+    FqDBuf d_first{*this}, d_slow{*this};
+    FqDBuf d_len_b{*this}, d_len_n{*this}, d_len_c{*this}, d_src_b{*this}, d_src_q{*this}, d_src_n{*this}, d_src_c{*this}, d_flags{*this},
+           d_off_b{*this}, d_off_n{*this}, d_off_c{*this}, d_bases{*this}, d_quals{*this}, d_names{*this}, d_coms{*this};
+    FqHBuf h_tail{*this}, h_slow{*this};
     int64_t c_reads = 0, c_fast = 0, c_slow = 0, c_batches = 0, c_bad_tail = 0;
     slx_fastq_batch last = {};
     uint64_t tot_b = 0, tot_n = 0, tot_c = 0;
-    std::vector<FqDBuf *> dbufs() { return {&d_first, &d_slow, &d_len_b, &d_len_n, &d_len_c, &d_src_b, &d_src_q, &d_src_n, &d_src_c,
-                                           &d_flags, &d_off_b, &d_off_n, &d_off_c, &d_bases, &d_quals, &d_names, &d_coms}; }
-    std::vector<FqHBuf *> hbufs() { return {&h_tail, &h_slow}; }
 };
 
 void fq_text_free(FqText *t)
 {
     t->prod.release();
     if (t->st) { (void)hipSetDevice(t->device); (void)hipStreamSynchronize(t->st); }
-    for (FqDBuf *b : t->text_dbufs()) b->release();
-    for (FqHBuf *b : t->text_hbufs()) b->release();
-    t->stage.release();
-    for (auto &e : t->ev) if (e) (void)hipEventDestroy(e);
-    if (t->st) (void)hipStreamDestroy(t->st);
+    t->stage.release();          // (dev_inflate.h's staging buffers: they have no owner, the stream has drained)
+    t->close();                  // the window's buffers and the reader's own
     if (t->map) munmap((void *)t->map, t->fsize);
     if (t->fd >= 0) ::close(t->fd);
-    t->st = nullptr; t->map = nullptr; t->fd = -1;
-    for (auto &e : t->ev) e = nullptr;
+    t->map = nullptr; t->fd = -1;
 }
 
 static void fq_free(slx_fastq *fq)
 {
-    fq->prod.release();
-    if (fq->st) { (void)hipSetDevice(fq->device); (void)hipStreamSynchronize(fq->st); }
-    for (FqDBuf *b : fq->dbufs()) b->release();
-    for (FqHBuf *b : fq->hbufs()) b->release();
     fq_text_free(fq);
     delete fq;
 }
@@ -218,7 +208,7 @@ int fq_text_open(FqText *t, const char *path, int device)
     int source = 0;
     if (got >= 2 && h[0] == 0x1f && h[1] == 0x8b) source = (got >= 18 && h[2] == 8 && (h[3] & 4) && h[12] == 'B' && h[13] == 'C') ? 1 : 2;
     const std::string no_device = std::string("no HIP device: the ") + who + " parses on MI355X only (no CPU fallback)";
-    const int rc = slx_pick_device(device, no_device.c_str(), who, &t->device);
+    const int rc = t->open(device, who, no_device.c_str());
     if (rc != SLX_OK) { ::close(fd); return rc; }
     t->path = path; t->source = source;
     if (source == 1) {
@@ -231,8 +221,6 @@ int fq_text_open(FqText *t, const char *path, int device)
         t->mem.assign(m, m + nm);
         slx_bam_members_free(m);
     } else ::close(fd);
-    if (hipStreamCreateWithFlags(&t->st, hipStreamNonBlocking) != hipSuccess) { slx_set_error("%s: cannot create a stream on device %d", who, t->device); return SLX_ENODEVICE; }
-    for (auto &e : t->ev) if (hipEventCreate(&e) != hipSuccess) { slx_set_error("%s: cannot create an event", who); return SLX_ENODEVICE; }
     return SLX_OK;
 }
 

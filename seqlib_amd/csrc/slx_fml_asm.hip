@@ -151,10 +151,7 @@ int build_and_assemble(slx_fml *f, const std::vector<int> &h_ns, const std::vect
         SLX_HIPCHK(hipMemcpyAsync(h_text, d_text.p, (size_t)text_len, hipMemcpyDeviceToHost, f->st_copy));
         hipLaunchKernelGGL(k_asm_keys, dim3((unsigned)((n_str + 255) / 256)), dim3(256), 0, f->st, d_text.as<unsigned char>(), d_strs.as<FmlStr>(), n_str, kk, keys_in, vals_in, d_rep, d_cont);
         SLX_HIPCHK(hipGetLastError());
-        size_t tmp_bytes = 0;
-        SLX_HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys_in, keys_out, vals_in, vals_out, (int)n_str, 0, 64, f->st));
-        if ((rc = d_sort.ensure(tmp_bytes + 256))) return rc;
-        SLX_HIPCHK(hipcub::DeviceRadixSort::SortPairs(d_sort.p, tmp_bytes, keys_in, keys_out, vals_in, vals_out, (int)n_str, 0, 64, f->st));
+        SLX_CHK(slx_cub("hipcub::DeviceRadixSort::SortPairs (assembler, overlap keys)", d_sort, 256, [&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortPairs(t, b, keys_in, keys_out, vals_in, vals_out, (int)n_str, 0, 64, f->st); }));
         // an index over the sorted keys (key -> first position), then
         // the join: overlaps as (u, v, length) triples; room for 40 per string at first (about the coverage), more when they do not fit
         unsigned long long *d_trin = f->d_misc.as<unsigned long long>(), *d_outn = d_trin + 1;

@@ -25,26 +25,21 @@ typedef SlxPinBuf<SlxMargin<4, 256>> GHBuf;
 
 static_assert(sizeof(slx_grc_iv) == sizeof(grc_iv) && sizeof(grc_iv) == 16, "slx_grc_iv and grc_iv are one layout");
 
-struct slx_grc {
-    int device = -1;          // -1: host only
+static const char GRC_NO_DEVICE[] = "no HIP device: interval batches are joined on MI355X only (no CPU fallback)";
+
+struct slx_grc : SlxGpu<> {
+    slx_grc() : SlxGpu(GRC_NO_DEVICE) {}
     uint32_t n = 0;
     grc_host_arrays H;          // the host mirror of the index
     uint32_t wave_range = 64, long_cigar = 64;
     uint64_t slice = 1ull << 20;
-    hipStream_t st = nullptr;
-    hipEvent_t ev[2] = {};
-    GDBuf d_chr, d_p1, d_p2, d_perm, d_run, d_ends, d_strand, d_segchr, d_segbeg;          // the index
-    GDBuf d_q, d_cand, d_cnt32, d_cnt, d_at, d_lane, d_wave, d_ctr, d_tmp, d_qid, d_sid, d_c1, d_c2, d_width;          // a join
-    GDBuf d_in, d_off, d_ks, d_ke, d_ks2, d_ke2, d_long, d_subj;          // records
-    GDBuf d_a, d_b, d_c, d_d, d_iv;          // build and merge scratch
-    GHBuf h_ctr;
+    GDBuf d_chr{*this}, d_p1{*this}, d_p2{*this}, d_perm{*this}, d_run{*this}, d_ends{*this}, d_strand{*this}, d_segchr{*this}, d_segbeg{*this};          // the index
+    GDBuf d_q{*this}, d_cand{*this}, d_cnt32{*this}, d_cnt{*this}, d_at{*this}, d_lane{*this}, d_wave{*this}, d_ctr{*this}, d_tmp{*this}, d_qid{*this}, d_sid{*this}, d_c1{*this}, d_c2{*this}, d_width{*this};          // a join
+    GDBuf d_in{*this}, d_off{*this}, d_ks{*this}, d_ke{*this}, d_ks2{*this}, d_ke2{*this}, d_long{*this}, d_subj{*this};          // records
+    GDBuf d_a{*this}, d_b{*this}, d_c{*this}, d_d{*this}, d_iv{*this};          // build and merge scratch
+    GHBuf h_ctr{*this};
     int64_t c_queries = 0, c_lane = 0, c_wave = 0, c_pairs = 0, c_records = 0, c_long = 0, c_merged = 0;
     double us_build = 0, us_count = 0, us_fill = 0, us_records = 0, us_merge = 0;
-    std::vector<GDBuf *> dbufs()
-    {
-        return {&d_chr, &d_p1, &d_p2, &d_perm, &d_run, &d_ends, &d_strand, &d_segchr, &d_segbeg, &d_q, &d_cand, &d_cnt32, &d_cnt, &d_at, &d_lane, &d_wave, &d_ctr, &d_tmp, &d_qid, &d_sid,
-                &d_c1, &d_c2, &d_width, &d_in, &d_off, &d_ks, &d_ke, &d_ks2, &d_ke2, &d_long, &d_subj, &d_a, &d_b, &d_c, &d_d, &d_iv};
-    }
     grc_idx host_idx() const { return H.idx(); }
     grc_idx dev_idx() const
     {
@@ -55,43 +50,21 @@ struct slx_grc {
 
 static inline unsigned grc_blocks(uint64_t n, unsigned per = 256) { return (unsigned)((n + per - 1) / per); }
 
-static int grc_need_gpu(const char *who, slx_grc *g)
-{
-    if (!g) { slx_set_error("%s: null object", who); return SLX_EINVAL; }
-    if (g->device < 0) { slx_set_error("%s: no HIP device: interval batches are joined on MI355X only (no CPU fallback)", who); return SLX_ENODEVICE; }
-    SLX_HIPCHK(hipSetDevice(g->device));
-    return SLX_OK;
-}
-
 extern "C" void slx_grc_free(slx_grc *g)
 {
     if (!g) return;
-    if (g->device >= 0) {
-        (void)hipSetDevice(g->device);
-        if (g->st) (void)hipStreamSynchronize(g->st);
-        for (GDBuf *b : g->dbufs()) b->release();
-        g->h_ctr.release();
-        for (auto &e : g->ev) if (e) (void)hipEventDestroy(e);
-        if (g->st) (void)hipStreamDestroy(g->st);
-    }
+    g->close();
     delete g;
 }
 
+// a radix sort over all bits of the key (hipCUB takes the count as an int)
 template <class K, class V> static int grc_sort_pairs(slx_grc *g, const K *kin, K *kout, const V *vin, V *vout, uint32_t n)
 {
-    size_t tb = 0;
-    SLX_HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, (int)n, 0, (int)(8 * sizeof(K)), g->st));
-    SLX_CHK(g->d_tmp.ensure(tb + 8));
-    SLX_HIPCHK(hipcub::DeviceRadixSort::SortPairs(g->d_tmp.p, tb, kin, kout, vin, vout, (int)n, 0, (int)(8 * sizeof(K)), g->st));
-    return SLX_OK;
+    return slx_cub("hipcub::DeviceRadixSort::SortPairs (intervals)", g->d_tmp, 8, [&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortPairs(t, b, kin, kout, vin, vout, (int)n, 0, (int)(8 * sizeof(K)), g->st); });
 }
 static int grc_sort_keys(slx_grc *g, const ull *kin, ull *kout, uint64_t n)
 {
-    size_t tb = 0;
-    SLX_HIPCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, kin, kout, (int)n, 0, 64, g->st));
-    SLX_CHK(g->d_tmp.ensure(tb + 8));
-    SLX_HIPCHK(hipcub::DeviceRadixSort::SortKeys(g->d_tmp.p, tb, kin, kout, (int)n, 0, 64, g->st));
-    return SLX_OK;
+    return slx_cub("hipcub::DeviceRadixSort::SortKeys (intervals)", g->d_tmp, 8, [&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortKeys(t, b, kin, kout, (int)n, 0, 64, g->st); });
 }
 
 static int grc_build_device(slx_grc *g, const slx_grc_iv *iv)
@@ -118,10 +91,7 @@ static int grc_build_device(slx_grc *g, const slx_grc_iv *iv)
         k_grc_gather<<<grc_blocks(n), 256, 0, st>>>(d_iv, idx, n, g->d_chr.as<int32_t>(), g->d_p1.as<int32_t>(), g->d_p2.as<int32_t>(), g->d_strand.as<uint8_t>(), g->d_perm.as<int32_t>(), k64);
         SLX_HIPCHK(hipGetLastError());
         // (chr, p2) keys in k64: their max-scan into k64o, their sort into the query scratch
-        size_t tb = 0;
-        SLX_HIPCHK(hipcub::DeviceScan::InclusiveScan(nullptr, tb, k64, k64o, hipcub::Max(), (int)n, st));
-        SLX_CHK(g->d_tmp.ensure(tb + 8));
-        SLX_HIPCHK(hipcub::DeviceScan::InclusiveScan(g->d_tmp.p, tb, k64, k64o, hipcub::Max(), (int)n, st));
+        SLX_CHK(slx_cub("hipcub::DeviceScan::InclusiveScan (intervals, build)", g->d_tmp, 8, [&](void *t, size_t &b) { return hipcub::DeviceScan::InclusiveScan(t, b, k64, k64o, hipcub::Max(), (int)n, st); }));
         SLX_CHK(g->d_ks.ensure(n8));
         SLX_CHK(grc_sort_keys(g, k64, g->d_ks.as<ull>(), n));
         k_grc_low_halves<<<grc_blocks(n), 256, 0, st>>>(k64o, g->d_ks.as<ull>(), n, g->d_run.as<int32_t>(), g->d_ends.as<int32_t>());
@@ -153,16 +123,9 @@ static int grc_create_impl(slx_grc *g, int device, const slx_grc_iv *iv, int64_t
         if (iv[i].pos2 < iv[i].pos1) { slx_set_error("slx_grc_create: interval %lld ends (%d) before it starts (%d)", (long long)i, iv[i].pos2, iv[i].pos1); return SLX_EINVAL; }
     g->n = (uint32_t)n;
     g->H.resize((uint32_t)n);
-    int ndev = 0;
-    if (device == SLX_GRC_HOST || (device == SLX_GRC_AUTO && (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0))) {          // host only
-        if (device == SLX_GRC_AUTO) (void)hipGetLastError();
-        g->device = -1;
-        grc_build_host((const grc_iv *)iv, g->n, g->H);
-        return SLX_OK;
-    }
-    SLX_CHK(slx_pick_device(device, "no HIP device: interval batches are joined on MI355X only (no CPU fallback)", "slx_grc_create", &g->device));
-    SLX_HIPCHK(hipStreamCreateWithFlags(&g->st, hipStreamNonBlocking));
-    for (auto &e : g->ev) SLX_HIPCHK(hipEventCreate(&e));
+    // SLX_GRC_HOST never asks the runtime; SLX_GRC_AUTO is the current device, or host only without one
+    if (device != SLX_GRC_HOST) SLX_CHK(g->open(device == SLX_GRC_AUTO ? -1 : device, "slx_grc_create", GRC_NO_DEVICE, device == SLX_GRC_AUTO));
+    if (g->device < 0) { grc_build_host((const grc_iv *)iv, g->n, g->H); return SLX_OK; }          // host only
     return grc_build_device(g, iv);
 }
 
@@ -172,11 +135,7 @@ extern "C" int slx_grc_create(int device, const slx_grc_iv *iv, int64_t n, slx_g
     *out = nullptr;
     if (n >= 0x7fffffffll) { slx_set_error("slx_grc_create: 2^31 intervals or more"); return SLX_EINVAL; }
     if (device < SLX_GRC_AUTO) { slx_set_error("slx_grc_create: device %d", device); return SLX_EINVAL; }
-    slx_grc *g = new slx_grc();
-    const int rc = grc_create_impl(g, device, iv, n);
-    if (rc != SLX_OK) { slx_grc_free(g); return rc; }
-    *out = g;
-    return SLX_OK;
+    return slx_create(out, slx_grc_free, [&](slx_grc *g) { return grc_create_impl(g, device, iv, n); });
 }
 
 extern "C" int slx_grc_set(slx_grc *g, const char *key, int64_t v)
@@ -375,7 +334,7 @@ static int grc_upload_queries(const char *who, slx_grc *g, const slx_grc_iv *q, 
 
 extern "C" int slx_grc_overlaps(slx_grc *g, const slx_grc_iv *q, int64_t nq, int ignore_strand, slx_grc_result *res)
 {
-    SLX_CHK(grc_need_gpu("slx_grc_overlaps", g));
+    SLX_CHK(slx_need(g, "slx_grc_overlaps"));
     if (!res) { slx_set_error("slx_grc_overlaps: null result"); return SLX_EINVAL; }
     memset(res, 0, sizeof *res);
     SLX_CHK(grc_upload_queries("slx_grc_overlaps", g, q, nq));
@@ -386,7 +345,7 @@ extern "C" int slx_grc_overlaps(slx_grc *g, const slx_grc_iv *q, int64_t nq, int
 
 extern "C" int slx_grc_count(slx_grc *g, const slx_grc_iv *q, int64_t nq, int ignore_strand, int contained, uint32_t *count)
 {
-    SLX_CHK(grc_need_gpu("slx_grc_count", g));
+    SLX_CHK(slx_need(g, "slx_grc_count"));
     if (nq > 0 && !count) { slx_set_error("slx_grc_count: null output"); return SLX_EINVAL; }
     SLX_CHK(grc_upload_queries("slx_grc_count", g, q, nq));
     uint64_t total = 0;
@@ -439,33 +398,24 @@ static int grc_records(slx_grc *g, const uint8_t *d_s, uint64_t n_bytes, const u
     return grc_result(g, n, total, pairs, res);
 }
 
-static int grc_records_args(const char *who, slx_grc *g, const void *s, int64_t n_bytes, const void *off, int64_t n)
-{
-    SLX_CHK(grc_need_gpu(who, g));
-    if (n_bytes < 0 || n < 0 || (n_bytes && !s) || (n && !off)) { slx_set_error("%s: null or negative argument", who); return SLX_EINVAL; }
-    return SLX_OK;
-}
-
 extern "C" int slx_grc_overlaps_device(slx_grc *g, const void *d_stream, int64_t n_bytes, const void *d_rec_off, int64_t n_records, int want_pairs, slx_grc_result *res)
 {
-    SLX_CHK(grc_records_args("slx_grc_overlaps_device", g, d_stream, n_bytes, d_rec_off, n_records));
+    SLX_CHK(slx_need(g, "slx_grc_overlaps_device"));
+    SLX_CHK(slx_batch_args("slx_grc_overlaps_device", d_stream, n_bytes, d_rec_off, n_records));
     return grc_records(g, (const uint8_t *)d_stream, (uint64_t)n_bytes, (const ull *)d_rec_off, (uint64_t)n_records, want_pairs != 0, res);
 }
 
 extern "C" int slx_grc_overlaps_host(slx_grc *g, const void *stream, int64_t n_bytes, const uint64_t *rec_off, int64_t n_records, int want_pairs, slx_grc_result *res)
 {
-    SLX_CHK(grc_records_args("slx_grc_overlaps_host", g, stream, n_bytes, rec_off, n_records));
-    if (n_records) {
-        SLX_CHK(g->d_in.ensure((size_t)n_bytes + 8)); SLX_CHK(g->d_off.ensure(8 * ((size_t)n_records + 1)));
-        if (n_bytes) SLX_HIPCHK(hipMemcpyAsync(g->d_in.p, stream, (size_t)n_bytes, hipMemcpyHostToDevice, g->st));
-        SLX_HIPCHK(hipMemcpyAsync(g->d_off.p, rec_off, 8 * ((size_t)n_records + 1), hipMemcpyHostToDevice, g->st));
-    }
+    SLX_CHK(slx_need(g, "slx_grc_overlaps_host"));
+    SLX_CHK(slx_batch_args("slx_grc_overlaps_host", stream, n_bytes, rec_off, n_records));
+    if (n_records) SLX_CHK(slx_batch_stage(g->d_in, g->d_off, 8, stream, n_bytes, rec_off, n_records, g->st));
     return grc_records(g, g->d_in.as<uint8_t>(), (uint64_t)n_bytes, g->d_off.as<ull>(), (uint64_t)n_records, want_pairs != 0, res);
 }
 
 extern "C" int slx_grc_subject_counts(slx_grc *g, int64_t *out)
 {
-    SLX_CHK(grc_need_gpu("slx_grc_subject_counts", g));
+    SLX_CHK(slx_need(g, "slx_grc_subject_counts"));
     if (g->n && !out) { slx_set_error("slx_grc_subject_counts: null output"); return SLX_EINVAL; }
     if (g->n) SLX_HIPCHK(hipMemcpy(out, g->d_subj.p, 8 * (size_t)g->n, hipMemcpyDeviceToHost));
     return SLX_OK;
@@ -473,7 +423,7 @@ extern "C" int slx_grc_subject_counts(slx_grc *g, int64_t *out)
 
 extern "C" int slx_grc_clear_counts(slx_grc *g)
 {
-    SLX_CHK(grc_need_gpu("slx_grc_clear_counts", g));
+    SLX_CHK(slx_need(g, "slx_grc_clear_counts"));
     SLX_HIPCHK(hipMemsetAsync(g->d_subj.p, 0, 8 * (size_t)g->n + 16, g->st));
     SLX_HIPCHK(slx_wait_stream(g->st));
     return SLX_OK;

@@ -1,10 +1,13 @@
-// slx_hip.h -- the host-side HIP plumbing the translation units of libseqlib_amd.so share: the error macros, the grow-only device and pinned buffers, the event
-// timer, hipCUB's exclusive sum with its temporary storage, and the device preamble of the handles.  Host code only; included from .hip files and their internal
+// slx_hip.h -- the host-side HIP plumbing the translation units of libseqlib_amd.so share: the error macros, the grow-only device and pinned buffers and
+// their tally, the event timer, one runner for hipCUB calls with their temporary storage, the device context of a handle (device, stream, events, owned buffers:
+// SlxGpu) and the intake of a batch of records.  Host code only; included from .hip files and their internal
 // headers.  Nothing here is part of the C-ABI.  DESIGN.md section 9.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
+#include <atomic>
 #include <cstddef>
+#include <cstdint>
 #include "slx_internal.h"
 
 // A HIP call that failed ends the function: out of memory is SLX_ENOMEM, anything else SLX_ENODEVICE; the message carries the expression.
@@ -19,6 +22,8 @@
 #define SLX_CHK(x) do { const int rc_ = (x); if (rc_ != SLX_OK) return rc_; } while (0)
 
 // ------------------------------------------------------------------ buffers
+// The tallies of slx_internal.h: bytes held through SlxDevBuf / SlxPinBuf right now, what a test of create and free reads (slx_hip_live_bytes).
+static inline void slx_live(std::atomic<int64_t> &t, size_t taken, size_t given_back) { t.fetch_add((int64_t)taken - (int64_t)given_back, std::memory_order_relaxed); }
 // How much a buffer asks for when n bytes no longer fit.  The policy belongs to the buffer's type: every owner names its own once, by alias.
 struct SlxExact { static size_t want(size_t n) { return n; } };
 template <size_t DIV, size_t PAD> struct SlxMargin { static size_t want(size_t n) { return n + n / DIV + PAD; } };
@@ -29,7 +34,7 @@ static inline int slx_dev_realloc(void **p, size_t *cap, size_t want, hipStream_
 {
     if (!*p) keep = 0;
     if (!keep) {
-        if (*p) (void)hipFree(*p);
+        if (*p) { (void)hipFree(*p); slx_live(slx_live_dev, 0, *cap); }
         *p = nullptr; *cap = 0;
     }
     void *q = nullptr;
@@ -40,8 +45,10 @@ static inline int slx_dev_realloc(void **p, size_t *cap, size_t want, hipStream_
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) { (void)hipFree(q); SLX_HIPCHK(e); }
         (void)hipFree(*p);
+        slx_live(slx_live_dev, 0, *cap);
     }
     *p = q; *cap = want;
+    slx_live(slx_live_dev, want, 0);
     return SLX_OK;
 }
 
@@ -49,28 +56,50 @@ static inline int slx_dev_realloc(void **p, size_t *cap, size_t want, hipStream_
 // kernel's results can come down into while the host waits on the stream only.
 static inline int slx_pin_realloc(void **p, size_t *cap, size_t want)
 {
-    if (*p) (void)hipHostFree(*p);
+    if (*p) { (void)hipHostFree(*p); slx_live(slx_live_pin, 0, *cap); }
     *p = nullptr; *cap = 0;
     const hipError_t e = hipHostMalloc(p, want, hipHostMallocDefault);
     if (e != hipSuccess) { (void)hipGetLastError(); *p = nullptr; slx_set_error("cannot pin %zu bytes (%s)", want, hipGetErrorString(e)); return SLX_ENOMEM; }
     *cap = want;
+    slx_live(slx_live_pin, want, 0);
     return SLX_OK;
 }
 
-// A grow-only block of HBM.  No destructor: the owner releases it, after the stream that uses it has drained.
-template <class Grow> struct SlxDevBuf {
+// ------------------------------------------------------------------ owned buffers
+struct SlxBuf;
+// What the buffers of one handle (or of one call's scratch) hang on: a buffer constructed with its owner links itself in, and release_bufs releases them all.
+struct SlxBufOwner {
+    SlxBuf *bufs = nullptr;
+    inline void release_bufs();
+};
+// A grow-only block.  No destructor: the owner releases it, after the stream that uses it has drained.  Not copied: the owner's list holds its address.
+struct SlxBuf {
     void *p = nullptr; size_t cap = 0;
-    int ensure(size_t n) { return n <= cap ? SLX_OK : slx_dev_realloc(&p, &cap, Grow::want(n), nullptr, 0); }          // the contents may go
-    int ensure(size_t n, hipStream_t st, size_t keep) { return n <= cap ? SLX_OK : slx_dev_realloc(&p, &cap, Grow::want(n), st, keep); }          // keep: leading bytes that survive a growth
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    SlxBuf *next = nullptr;
+    const bool pinned;
+    SlxBuf(bool pin, SlxBufOwner *o) : pinned(pin) { if (o) { next = o->bufs; o->bufs = this; } }
+    SlxBuf(const SlxBuf &) = delete;
+    SlxBuf &operator=(const SlxBuf &) = delete;
+    void release()
+    {
+        if (p) { (void)(pinned ? hipHostFree(p) : hipFree(p)); slx_live(pinned ? slx_live_pin : slx_live_dev, 0, cap); }
+        p = nullptr; cap = 0;
+    }
     template <typename T> T *as() const { return (T *)p; }
 };
-// ... and one of pinned host memory
-template <class Grow> struct SlxPinBuf {
-    void *p = nullptr; size_t cap = 0;
+inline void SlxBufOwner::release_bufs() { for (SlxBuf *b = bufs; b; b = b->next) b->release(); }
+// ... of HBM: `SlxDevBuf<G> d_x{gpu}` belongs to gpu, `SlxDevBuf<G> d_x` to whoever releases it by name
+template <class Grow> struct SlxDevBuf : SlxBuf {
+    SlxDevBuf() : SlxBuf(false, nullptr) {}
+    SlxDevBuf(SlxBufOwner &o) : SlxBuf(false, &o) {}
+    int ensure(size_t n) { return n <= cap ? SLX_OK : slx_dev_realloc(&p, &cap, Grow::want(n), nullptr, 0); }          // the contents may go
+    int ensure(size_t n, hipStream_t st, size_t keep) { return n <= cap ? SLX_OK : slx_dev_realloc(&p, &cap, Grow::want(n), st, keep); }          // keep: leading bytes that survive a growth
+};
+// ... and of pinned host memory
+template <class Grow> struct SlxPinBuf : SlxBuf {
+    SlxPinBuf() : SlxBuf(true, nullptr) {}
+    SlxPinBuf(SlxBufOwner &o) : SlxBuf(true, &o) {}
     int ensure(size_t n) { return n <= cap ? SLX_OK : slx_pin_realloc(&p, &cap, Grow::want(n)); }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-    template <typename T> T *as() const { return (T *)p; }
 };
 
 // ------------------------------------------------------------------ events
@@ -78,23 +107,26 @@ template <class Grow> struct SlxPinBuf {
 static inline float slx_ev_ms(hipEvent_t a, hipEvent_t b) { float ms = 0; return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.f; }
 static inline float slx_ev_us(hipEvent_t a, hipEvent_t b) { return slx_ev_ms(a, b) * 1000.f; }
 
-// ------------------------------------------------------------------ hipCUB's exclusive sum
-// bytes of temporary storage the sum of n items asks for (hipCUB's rocPRIM backend forwards the count as a size_t whatever type it is given)
-template <class In, class Out> static inline int slx_exclusive_sum_bytes(In in, Out out, size_t n, hipStream_t st, size_t *bytes)
+// ------------------------------------------------------------------ hipCUB
+// One hipCUB call with its temporary storage: run(nullptr, bytes) asks for the size, tmp is made to hold it and `slack` bytes more (what the caller's unit has
+// always added to the figure: kept as found), run(tmp.p, bytes) enqueues the work.  run binds the stream and every other argument; what names the call in the
+// message of a failure (the lambda hides the expression from SLX_HIPCHK).
+template <class Buf, class Run> static inline int slx_cub(const char *what, Buf &tmp, size_t slack, Run run)
 {
-    *bytes = 0;
-    SLX_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, *bytes, in, out, n, st));
-    return SLX_OK;
+    size_t bytes = 0;
+    hipError_t e = run((void *)nullptr, bytes);
+    if (e == hipSuccess) {
+        SLX_CHK(tmp.ensure(bytes + slack));
+        e = run(tmp.p, bytes);
+    }
+    if (e == hipSuccess) return SLX_OK;
+    slx_set_error("HIP error %s in %s", hipGetErrorString(e), what);
+    return e == hipErrorOutOfMemory ? SLX_ENOMEM : SLX_ENODEVICE;
 }
-// out[i] = in[0] + ... + in[i - 1] for i < n, enqueued on st; tmp is made to hold hipCUB's temporary storage and `slack` bytes more (what the caller's unit has
-// always added to the figure: kept as found)
+// out[i] = in[0] + ... + in[i - 1] for i < n, enqueued on st (hipCUB's rocPRIM backend forwards the count as a size_t whatever type it is given)
 template <class Buf, class In, class Out> static inline int slx_exclusive_sum(Buf &tmp, In in, Out out, size_t n, hipStream_t st, size_t slack = 0)
 {
-    size_t tb = 0;
-    SLX_CHK(slx_exclusive_sum_bytes(in, out, n, st, &tb));
-    SLX_CHK(tmp.ensure(tb + slack));
-    SLX_HIPCHK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, in, out, n, st));
-    return SLX_OK;
+    return slx_cub("hipcub::DeviceScan::ExclusiveSum", tmp, slack, [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, in, out, n, st); });
 }
 
 // ------------------------------------------------------------------ the device of a handle
@@ -118,5 +150,79 @@ static inline int slx_pick_device(int device, const char *no_device_msg, const c
     if (device >= ndev) { slx_set_error("%s: device %d is not one of the %d visible", who, device, ndev); return SLX_EINVAL; }
     SLX_HIPCHK(hipSetDevice(device));
     *device_out = device;
+    return SLX_OK;
+}
+
+// ------------------------------------------------------------------ the device context of a handle
+// The device, the stream, the events and the owned buffers of one handle.  open's sentence is the message of a create without a device (it may name the file that is
+// not created); the constructor's is need()'s.  N events: most units time one span (2), the SAM writer two overlapping ones (4).
+template <int N = 2> struct SlxGpu : SlxBufOwner {
+    int device = -1;          // -1: host only, or not opened
+    hipStream_t st = nullptr;
+    hipEvent_t ev[N] = {};
+    const char *const no_device;          // what need() says on a host-only handle: the unit's sentence, a constant; units without host-only handles give none
+    explicit SlxGpu(const char *no_device_sentence = "no HIP device") : no_device(no_device_sentence) {}
+
+    // device < 0 is the current one.  host_only_ok: with device < 0 and no visible device the handle stays host only (SLX_OK, device -1); otherwise no device is
+    // SLX_ENODEVICE with the sentence, and a device that is not there SLX_EINVAL
+    int open(int dev, const char *who, const char *no_device_sentence, bool host_only_ok = false)
+    {
+        int ndev = 0;
+        if (host_only_ok && dev < 0 && (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)) { (void)hipGetLastError(); device = -1; return SLX_OK; }
+        SLX_CHK(slx_pick_device(dev, no_device_sentence, who, &device));
+        SLX_HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        for (auto &e : ev) SLX_HIPCHK(hipEventCreate(&e));
+        return SLX_OK;
+    }
+    // before a kernel entry point does anything: the handle's device is the calling thread's, or SLX_ENODEVICE with the unit's sentence
+    int need(const char *who)
+    {
+        if (device < 0) { slx_set_error("%s: %s", who, no_device); return SLX_ENODEVICE; }
+        SLX_HIPCHK(hipSetDevice(device));
+        return SLX_OK;
+    }
+    // the stream drains, then the buffers, the events and the stream go; safe on a context that open left half made, and a second time
+    void close()
+    {
+        if (device >= 0) {
+            (void)hipSetDevice(device);
+            if (st) (void)hipStreamSynchronize(st);
+        }
+        release_bufs();
+        for (auto &e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+        if (st) (void)hipStreamDestroy(st);
+        st = nullptr;
+    }
+};
+// need() for a handle the caller may have passed as null
+template <class H> static inline int slx_need(H *h, const char *who)
+{
+    if (!h) { slx_set_error("%s: null object", who); return SLX_EINVAL; }
+    return h->need(who);
+}
+// The body of a create entry point: a new H, impl(h) fills it, a failure frees it with the unit's own free, *out is the handle or null
+template <class H, class Impl> static inline int slx_create(H **out, void (*free_fn)(H *), Impl impl)
+{
+    *out = nullptr;
+    H *h = new H();
+    const int rc = impl(h);
+    if (rc != SLX_OK) { free_fn(h); return rc; }
+    *out = h;
+    return SLX_OK;
+}
+
+// ------------------------------------------------------------------ a batch of records
+// block_size-prefixed BAM records and their offset table (n + 1 entries), on the host or already in HBM: the argument check every unit's add entry points share ...
+static inline int slx_batch_args(const char *who, const void *s, int64_t n_bytes, const void *off, int64_t n)
+{
+    if (n_bytes < 0 || n < 0 || (n_bytes && !s) || (n && !off)) { slx_set_error("%s: null or negative argument", who); return SLX_EINVAL; }
+    return SLX_OK;
+}
+// ... and a host batch (n > 0) on its way into the handle's d_in / d_off on st; pad: the bytes a unit's kernels may read behind the stream's end
+template <class Buf> static inline int slx_batch_stage(Buf &d_in, Buf &d_off, size_t pad, const void *s, int64_t n_bytes, const uint64_t *off, int64_t n, hipStream_t st)
+{
+    SLX_CHK(d_in.ensure((size_t)n_bytes + pad)); SLX_CHK(d_off.ensure(8 * ((size_t)n + 1)));
+    if (n_bytes) SLX_HIPCHK(hipMemcpyAsync(d_in.p, s, (size_t)n_bytes, hipMemcpyHostToDevice, st));
+    SLX_HIPCHK(hipMemcpyAsync(d_off.p, off, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, st));
     return SLX_OK;
 }

@@ -23,6 +23,7 @@ void slx_set_error(const char *fmt, ...)
 
 extern "C" const char *slx_last_error(void) { return g_err; }
 extern "C" const char *slx_version(void) { return "seqlib_amd 0.1 (gfx950)"; }
+extern "C" int64_t slx_hip_live_bytes(int pinned) { return (pinned ? slx_live_pin : slx_live_dev).load(std::memory_order_relaxed); }
 
 // ---------------------------------------------------------------- libc lrand48 stream
 static const uint64_t LCG_A = 0x5DEECE66DULL, LCG_C = 0xBULL, LCG_M = (1ULL << 48) - 1;

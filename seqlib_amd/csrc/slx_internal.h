@@ -1,6 +1,7 @@
 // slx_internal.h -- internal declarations shared by the host and device translation units of
 // libseqlib_amd.so.  Nothing here is part of the C-ABI (include/seqlib_amd.h).
 #pragma once
+#include <atomic>
 #include <cstdint>
 #include <cstddef>
 #include <string>
@@ -42,6 +43,8 @@ struct slx_index {
 };
 
 void slx_set_error(const char *fmt, ...);
+// Bytes of HBM and of pinned memory this process holds through SlxDevBuf / SlxPinBuf (slx_hip.h keeps them, slx_hip_live_bytes reads them)
+inline std::atomic<int64_t> slx_live_dev{0}, slx_live_pin{0};
 
 // How a host thread waits for a stream: hipStreamSynchronize, or -- SEQLIB_AMD_WAIT=sleep -- polling the stream every 40 us.  Measured with the whole bench confined to two
 // CPUs (taskset, round 6): the default wait is NOT what a starved rank loses to -- BamRecords 15.5 M reads/s (default) against 14.8 M (sleep), C5 4.6 against 4.4 M, and one

@@ -76,15 +76,12 @@ __global__ __launch_bounds__(256) void k_rec_fill(rec_in in, const rec_meta *met
 typedef SlxDevBuf<SlxMargin<4, 256>> RDBuf;
 typedef SlxPinBuf<SlxExact> RHBuf;
 
-struct slx_rec {
+struct slx_rec : SlxGpu<3> {
     slx_aligner *al = nullptr;
-    int device = 0;
-    hipStream_t st = nullptr;
-    hipEvent_t ev[3] = {};
-    RDBuf d_owner, d_meta, d_len, d_off, d_wide, d_state, d_tmp, d_stream;
-    RDBuf u_bases, u_offs, u_names, u_name_offs;      // slx_rec_upload's copies
-    RHBuf h_state;                      // two rec_state: [0] goes up, [1] comes down
-    RHBuf h_total;                      // one ull
+    RDBuf d_owner{*this}, d_meta{*this}, d_len{*this}, d_off{*this}, d_wide{*this}, d_state{*this}, d_tmp{*this}, d_stream{*this};
+    RDBuf u_bases{*this}, u_offs{*this}, u_names{*this}, u_name_offs{*this};      // slx_rec_upload's copies
+    RHBuf h_state{*this};               // two rec_state: [0] goes up, [1] comes down
+    RHBuf h_total{*this};               // one ull
     const void *last_stream = nullptr;  // of the batch handed out last
     int64_t last_records = 0, last_bytes = 0;
     int64_t c_records = 0, c_bytes = 0, c_batches = 0, c_wide = 0;
@@ -94,25 +91,18 @@ struct slx_rec {
 extern "C" void slx_rec_free(slx_rec *rb)
 {
     if (!rb) return;
-    if (rb->st) {
-        (void)hipSetDevice(rb->device);
-        (void)hipStreamSynchronize(rb->st);
-    }
-    for (RDBuf *b : {&rb->d_owner, &rb->d_meta, &rb->d_len, &rb->d_off, &rb->d_wide, &rb->d_state, &rb->d_tmp, &rb->d_stream, &rb->u_bases, &rb->u_offs, &rb->u_names, &rb->u_name_offs}) b->release();
-    rb->h_state.release(); rb->h_total.release();
-    for (auto &e : rb->ev) if (e) (void)hipEventDestroy(e);
-    if (rb->st) (void)hipStreamDestroy(rb->st);
+    rb->close();
     delete rb;
 }
+
+static const char REC_NO_DEVICE[] = "no HIP device: BAM records are built on MI355X only (no CPU fallback)";
 
 static int rec_init(slx_rec *rb, slx_aligner *al)
 {
     const int device = slx_aligner_device_of(al);
     if (device < 0) { slx_set_error("slx_rec_create: single-device aligners only (the hits of a multi-device aligner are merged on the host)"); return SLX_EINVAL; }
-    rb->al = al; rb->device = device;
-    SLX_HIPCHK(hipSetDevice(device));
-    SLX_HIPCHK(hipStreamCreateWithFlags(&rb->st, hipStreamNonBlocking));
-    for (auto &e : rb->ev) SLX_HIPCHK(hipEventCreate(&e));
+    rb->al = al;
+    SLX_CHK(rb->open(device, "slx_rec_create", REC_NO_DEVICE));
     SLX_CHK(rb->h_state.ensure(2 * sizeof(rec_state))); SLX_CHK(rb->h_total.ensure(sizeof(ull)));
     return SLX_OK;
 }
@@ -122,13 +112,9 @@ extern "C" int slx_rec_create(slx_aligner *al, slx_rec **out)
     if (!out) { slx_set_error("slx_rec_create: null argument"); return SLX_EINVAL; }
     *out = nullptr;
     int ndev = 0;          // (before the aligner is looked at: without a GPU there is none to give)
-    SLX_CHK(slx_count_devices("no HIP device: BAM records are built on MI355X only (no CPU fallback)", &ndev));
+    SLX_CHK(slx_count_devices(REC_NO_DEVICE, &ndev));
     if (!al) { slx_set_error("slx_rec_create: null aligner"); return SLX_EINVAL; }
-    slx_rec *rb = new slx_rec();
-    const int rc = rec_init(rb, al);
-    if (rc != SLX_OK) { slx_rec_free(rb); return rc; }
-    *out = rb;
-    return SLX_OK;
+    return slx_create(out, slx_rec_free, [&](slx_rec *rb) { return rec_init(rb, al); });
 }
 
 static int rec_build_impl(slx_rec *rb, const slx_hits *dev, rec_in in, slx_rec_batch *out)

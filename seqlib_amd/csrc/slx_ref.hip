@@ -270,7 +270,7 @@ typedef SlxDevBuf<SlxMargin<4, 256>> RDBuf;
 typedef SlxPinBuf<SlxMargin<4, 256>> RHBuf;
 
 struct slx_ref {
-    FqText T;
+    FqText T;          // the source and its device context: the handle's buffers hang on it
     uint64_t window = 64ull << 20;
     uint32_t gather_tile = 2048, long_record = 64;          // long_record: profiles/NOTES_ref.md
     std::vector<rg_contig> C;
@@ -279,21 +279,18 @@ struct slx_ref {
     std::string fai;
     uint64_t text_base = 0, bases_end = 0;
     bool prev_blank = false;
-    hipEvent_t ev[6] = {};
-    RDBuf d_bases, d_coff, d_clen;
+    hipEvent_t ev[6] = {};          // beside T's ten: the handle makes and destroys them itself
+    RDBuf d_bases{T}, d_coff{T}, d_clen{T};
     // the load
-    RDBuf d_li, d_ish, d_nb64, d_hidx, d_bpre, d_H, d_hline, d_first, d_seg, d_names;
-    RHBuf h_small, h_H, h_seg, h_names;
+    RDBuf d_li{T}, d_ish{T}, d_nb64{T}, d_hidx{T}, d_bpre{T}, d_H{T}, d_hline{T}, d_first{T}, d_seg{T}, d_names{T};
+    RHBuf h_small{T}, h_H{T}, h_seg{T}, h_names{T};
     // the fetch
-    RDBuf d_reg, d_flen, d_fsrc, d_foff, d_fout;
+    RDBuf d_reg{T}, d_flen{T}, d_fsrc{T}, d_foff{T}, d_fout{T};
     // NM and MD
-    RDBuf d_in, d_off, d_map, d_nm, d_sz, d_mdoff, d_md, d_long, d_cnt;
+    RDBuf d_in{T}, d_off{T}, d_map{T}, d_nm{T}, d_sz{T}, d_mdoff{T}, d_md{T}, d_long{T}, d_cnt{T};
     slx_ref_md last_md = {};
     int64_t c_windows = 0, c_text = 0, c_bases = 0, c_long = 0;
     double us_class = 0, us_gather = 0, us_fetch = 0, us_md_size = 0, us_md_text = 0;
-    std::vector<RDBuf *> dbufs() { return {&d_bases, &d_coff, &d_clen, &d_li, &d_ish, &d_nb64, &d_hidx, &d_bpre, &d_H, &d_hline, &d_first, &d_seg, &d_names, &d_reg, &d_flen, &d_fsrc,
-                                           &d_foff, &d_fout, &d_in, &d_off, &d_map, &d_nm, &d_sz, &d_mdoff, &d_md, &d_long, &d_cnt}; }
-    std::vector<RHBuf *> hbufs() { return {&h_small, &h_H, &h_seg, &h_names}; }
     std::vector<RDBuf *> load_dbufs() { return {&d_li, &d_ish, &d_nb64, &d_hidx, &d_bpre, &d_H, &d_hline, &d_first, &d_names}; }
 };
 
@@ -443,12 +440,9 @@ static int ref_window(slx_ref *r, uint64_t *consumed)
 
 static void ref_free(slx_ref *r)
 {
-    r->T.prod.release();
     if (r->T.st) { (void)hipSetDevice(r->T.device); (void)hipStreamSynchronize(r->T.st); }
-    for (RDBuf *b : r->dbufs()) b->release();
-    for (RHBuf *b : r->hbufs()) b->release();
     for (auto &e : r->ev) if (e) (void)hipEventDestroy(e);
-    fq_text_free(&r->T);
+    fq_text_free(&r->T);          // every buffer, T's events, the stream
     delete r;
 }
 
@@ -741,9 +735,7 @@ extern "C" int slx_ref_nm_md_device(slx_ref *r, const void *d_stream, int64_t n_
 extern "C" int slx_ref_nm_md_host(slx_ref *r, const void *stream, int64_t n_bytes, const uint64_t *rec_off, int64_t n_records, const int32_t *tid_map, int64_t n_map, slx_ref_md *out)
 {
     SLX_CHK(ref_md_args("slx_ref_nm_md_host", r, stream, n_bytes, rec_off, n_records, out));
-    SLX_CHK(r->d_in.ensure((size_t)n_bytes + 16)); SLX_CHK(r->d_off.ensure(8 * ((size_t)n_records + 1)));
-    if (n_bytes) SLX_HIPCHK(hipMemcpyAsync(r->d_in.p, stream, (size_t)n_bytes, hipMemcpyHostToDevice, r->T.st));
-    SLX_HIPCHK(hipMemcpyAsync(r->d_off.p, rec_off, 8 * ((size_t)n_records + 1), hipMemcpyHostToDevice, r->T.st));
+    SLX_CHK(slx_batch_stage(r->d_in, r->d_off, 16, stream, n_bytes, rec_off, n_records, r->T.st));
     SLX_HIPCHK(slx_wait_stream(r->T.st));
     return ref_nm_md(r, "slx_ref_nm_md_host", r->d_in.as<uint8_t>(), (uint64_t)n_bytes, r->d_off.as<ull>(), (uint64_t)n_records, tid_map, n_map, out);
 }

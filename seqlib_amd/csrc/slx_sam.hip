@@ -110,22 +110,16 @@ struct slx_samsrc : FqText {
     bool done = false, bad = false;
     std::string bad_msg;
     int fast_fail = 0;
-    FqDBuf d_ref_names, d_ref_off, d_ref_tid, d_fld, d_size, d_verdict, d_src, d_rec, d_out, d_slow, d_cnt;
-    FqHBuf h_text, h_verdict, h_line, h_size, h_src, h_slow;
+    FqDBuf d_ref_names{*this}, d_ref_off{*this}, d_ref_tid{*this}, d_fld{*this}, d_size{*this}, d_verdict{*this}, d_src{*this}, d_rec{*this}, d_out{*this}, d_slow{*this}, d_cnt{*this};
+    FqHBuf h_text{*this}, h_verdict{*this}, h_line{*this}, h_size{*this}, h_src{*this}, h_slow{*this};
     int64_t c_fast = 0, c_slow = 0;
     float us_sam[3] = {0, 0, 0};                   // fields, size, fill
-    std::vector<FqDBuf *> dbufs() { return {&d_ref_names, &d_ref_off, &d_ref_tid, &d_fld, &d_size, &d_verdict, &d_src, &d_rec, &d_out, &d_slow, &d_cnt}; }
-    std::vector<FqHBuf *> hbufs() { return {&h_text, &h_verdict, &h_line, &h_size, &h_src, &h_slow}; }
     sam_refs dev_refs() const { return sam_refs{d_ref_names.as<uint8_t>(), d_ref_off.as<uint32_t>(), d_ref_tid.as<int32_t>(), (int32_t)tab.tid.size()}; }
 };
 
 void slx_samsrc_close(slx_samsrc *S)
 {
     if (!S) return;
-    S->prod.release();
-    if (S->st) { (void)hipSetDevice(S->device); (void)hipStreamSynchronize(S->st); }
-    for (FqDBuf *b : S->dbufs()) b->release();
-    for (FqHBuf *b : S->hbufs()) b->release();
     fq_text_free(S);
     delete S;
 }

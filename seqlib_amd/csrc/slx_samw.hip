@@ -143,19 +143,18 @@ __global__ __launch_bounds__(256) void k_samw_fill_more(const uint8_t *s, const 
 typedef SlxDevBuf<SlxMargin<4, 256>> WDBuf;
 typedef SlxPinBuf<SlxMargin<4, 256>> WHBuf;
 
-struct slx_samw {
+struct slx_samw : SlxGpu<4> {
     int fd = -1;
     bool is_stdout = false;
     std::string path;
-    int device = 0, flags = 0, fast_fail = 0;
+    int flags = 0, fast_fail = 0;
     uint64_t stage_bytes = SAMW_STAGE;
     slx_bgzf *gz = nullptr;                        // SLX_SAMW_BGZF: the file is the BGZF writer's
-    hipStream_t st = nullptr;
-    hipEvent_t ev[4] = {};
     SamwRefTable tab;
     bool have_header = false;
-    WDBuf d_names, d_noff, d_in, d_off, d_size, d_verdict, d_fld, d_extra, d_xoff, d_line, d_text, d_cnt, d_tmp, d_g, d_slow_in, d_slow, d_src;
-    WHBuf h_small, h_verdict, h_off, h_g, h_slow_in, h_slow, h_text[2];
+    WDBuf d_names{*this}, d_noff{*this}, d_in{*this}, d_off{*this}, d_size{*this}, d_verdict{*this}, d_fld{*this}, d_extra{*this}, d_xoff{*this}, d_line{*this}, d_text{*this}, d_cnt{*this},
+          d_tmp{*this}, d_g{*this}, d_slow_in{*this}, d_slow{*this}, d_src{*this};
+    WHBuf h_small{*this}, h_verdict{*this}, h_off{*this}, h_g{*this}, h_slow_in{*this}, h_slow{*this}, h_text[2] = {*this, *this};
     int cur = 0;                                   // the pinned buffer the next SAMW_STAGE bytes come down into; the other one may be on its way to the file
     std::thread worker;
     bool worker_on = false;
@@ -165,8 +164,6 @@ struct slx_samw {
     std::string err_msg;
     int64_t c_records = 0, c_bytes = 0, c_batches = 0, c_fast = 0, c_slow = 0, c_wide = 0, c_extra = 0;
     double us[2] = {0, 0};
-    std::vector<WDBuf *> dbufs() { return {&d_names, &d_noff, &d_in, &d_off, &d_size, &d_verdict, &d_fld, &d_extra, &d_xoff, &d_line, &d_text, &d_cnt, &d_tmp, &d_g, &d_slow_in, &d_slow, &d_src}; }
-    std::vector<WHBuf *> hbufs() { return {&h_small, &h_verdict, &h_off, &h_g, &h_slow_in, &h_slow, &h_text[0], &h_text[1]}; }
     samw_refs dev_refs() const { return samw_refs{d_names.as<uint8_t>(), d_noff.as<uint32_t>(), (int32_t)tab.off.size() - 1}; }
 };
 
@@ -200,11 +197,7 @@ static int samw_write_all(slx_samw *w, const uint8_t *p, uint64_t n)
 static void samw_free(slx_samw *w)
 {
     if (w->worker_on) { w->worker.join(); w->worker_on = false; }
-    if (w->st) { (void)hipSetDevice(w->device); (void)hipStreamSynchronize(w->st); }
-    for (WDBuf *b : w->dbufs()) b->release();
-    for (WHBuf *b : w->hbufs()) b->release();
-    for (auto &e : w->ev) if (e) (void)hipEventDestroy(e);
-    if (w->st) (void)hipStreamDestroy(w->st);
+    w->close();
     if (w->fd >= 0 && !w->is_stdout) ::close(w->fd);
     delete w;
 }
@@ -212,7 +205,7 @@ static void samw_free(slx_samw *w)
 static int samw_open_impl(slx_samw *w, const char *path, int device, int flags)
 {
     const std::string no_device = std::string("no HIP device: the SAM writer formats on MI355X only (no CPU fallback); '") + path + "' is not created";
-    SLX_CHK(slx_pick_device(device, no_device.c_str(), "SAM writer", &w->device));
+    SLX_CHK(w->open(device, "SAM writer", no_device.c_str()));
     w->path = path; w->flags = flags;
     w->is_stdout = w->path == "-";
     if (flags & SLX_SAMW_BGZF) SLX_CHK(slx_bgzf_open(path, w->device, &w->gz));
@@ -220,8 +213,6 @@ static int samw_open_impl(slx_samw *w, const char *path, int device, int flags)
         w->fd = w->is_stdout ? STDOUT_FILENO : ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
         if (w->fd < 0) { slx_set_error("SAM writer: cannot create '%s': %s", path, strerror(errno)); return SLX_EIO; }
     }
-    SLX_HIPCHK(hipStreamCreateWithFlags(&w->st, hipStreamNonBlocking));
-    for (auto &e : w->ev) SLX_HIPCHK(hipEventCreate(&e));
     SLX_CHK(w->h_small.ensure(64));
     w->tab.build({});
     return SLX_OK;
@@ -379,7 +370,7 @@ static int samw_emit(slx_samw *w, uint64_t total)
 static int samw_args(const char *who, slx_samw *w, const void *s, int64_t n_bytes, const void *off, int64_t n)
 {
     if (!w) { slx_set_error("%s: null writer", who); return SLX_EINVAL; }
-    if (n_bytes < 0 || n < 0 || (n_bytes && !s) || (n && !off)) { slx_set_error("%s: null or negative argument", who); return SLX_EINVAL; }
+    SLX_CHK(slx_batch_args(who, s, n_bytes, off, n));
     if (w->err != SLX_OK) return samw_sticky(w);
     SLX_HIPCHK(hipSetDevice(w->device));
     return SLX_OK;
@@ -408,9 +399,7 @@ extern "C" int slx_samw_write_host(slx_samw *w, const void *stream, int64_t n_by
 {
     SLX_CHK(samw_args("slx_samw_write_host", w, stream, n_bytes, rec_off, n_records));
     if (n_records == 0) return SLX_OK;
-    SLX_CHK(w->d_in.ensure((size_t)n_bytes + 8)); SLX_CHK(w->d_off.ensure(8 * ((size_t)n_records + 1)));
-    if (n_bytes) SLX_HIPCHK(hipMemcpyAsync(w->d_in.p, stream, (size_t)n_bytes, hipMemcpyHostToDevice, w->st));
-    SLX_HIPCHK(hipMemcpyAsync(w->d_off.p, rec_off, 8 * ((size_t)n_records + 1), hipMemcpyHostToDevice, w->st));
+    SLX_CHK(slx_batch_stage(w->d_in, w->d_off, 8, stream, n_bytes, rec_off, n_records, w->st));
     uint64_t total = 0;
     SLX_CHK(samw_format(w, w->d_in.as<uint8_t>(), (uint64_t)n_bytes, w->d_off.as<ull>(), (uint64_t)n_records, (const uint8_t *)stream, rec_off, &total));
     return samw_emit(w, total);

@@ -89,16 +89,14 @@ struct Segment {
 static size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 }  // namespace
 
-struct slx_sort {
-    int device = 0;
-    hipStream_t st = nullptr;
-    hipEvent_t ev[2] = {};
+struct slx_sort : SlxGpu<> {
     std::vector<Segment> segs;
     uint64_t held_records = 0, held_bytes = 0;
     ull max_key = 0;
     int64_t max_bytes = 0, slab_bytes = 64ll << 20, batch_bytes = 64ll << 20;
-    SBuf d_state, d_key_in, d_key_out, d_ord_in, d_ord_out, d_len, d_src, d_slen, d_ssrc, d_doff, d_tmp, d_slab;
-    SHBuf h_state;                          // two sort_state: [0] goes up, [1] comes down
+    SBuf d_state{*this}, d_key_in{*this}, d_key_out{*this}, d_ord_in{*this}, d_ord_out{*this}, d_len{*this}, d_src{*this}, d_slen{*this}, d_ssrc{*this}, d_doff{*this}, d_tmp{*this},
+         d_slab{*this};
+    SHBuf h_state{*this};                          // two sort_state: [0] goes up, [1] comes down
     int64_t c_records = 0, c_bytes = 0, c_segments = 0, c_slabs = 0;
     double us_key = 0, us_sort = 0, us_gather = 0;
 };
@@ -114,11 +112,8 @@ extern "C" void slx_sort_free(slx_sort *s)
 {
     if (!s) return;
     if (s->st) { (void)hipSetDevice(s->device); (void)hipStreamSynchronize(s->st); }
-    sort_clear(s);
-    for (SBuf *b : {&s->d_state, &s->d_key_in, &s->d_key_out, &s->d_ord_in, &s->d_ord_out, &s->d_len, &s->d_src, &s->d_slen, &s->d_ssrc, &s->d_doff, &s->d_tmp, &s->d_slab}) b->release();
-    s->h_state.release();
-    for (auto &e : s->ev) if (e) (void)hipEventDestroy(e);
-    if (s->st) (void)hipStreamDestroy(s->st);
+    sort_clear(s);          // (the segments are the sorter's own hipMalloc blocks: they go once the stream has drained, before the context closes)
+    s->close();
     delete s;
 }
 
@@ -126,12 +121,10 @@ static std::string sort_no_device(const char *who) { return std::string(who) + "
 
 static int sort_init(slx_sort *s, int device)
 {
-    SLX_CHK(slx_pick_device(device, sort_no_device("slx_sort_create").c_str(), "slx_sort_create", &s->device));
+    SLX_CHK(s->open(device, "slx_sort_create", sort_no_device("slx_sort_create").c_str()));
     size_t free_b = 0, total_b = 0;
     SLX_HIPCHK(hipMemGetInfo(&free_b, &total_b));
     s->max_bytes = std::max<int64_t>((int64_t)(free_b / 2), 1);
-    SLX_HIPCHK(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
-    for (auto &e : s->ev) SLX_HIPCHK(hipEventCreate(&e));
     SLX_CHK(s->h_state.ensure(2 * sizeof(sort_state)));
     SLX_CHK(s->d_state.ensure(sizeof(sort_state)));
     return SLX_OK;
@@ -140,12 +133,7 @@ static int sort_init(slx_sort *s, int device)
 extern "C" int slx_sort_create(int device, slx_sort **out)
 {
     if (!out) { slx_set_error("slx_sort_create: null argument"); return SLX_EINVAL; }
-    *out = nullptr;
-    slx_sort *s = new slx_sort();
-    const int rc = sort_init(s, device);
-    if (rc != SLX_OK) { slx_sort_free(s); return rc; }
-    *out = s;
-    return SLX_OK;
+    return slx_create(out, slx_sort_free, [&](slx_sort *s) { return sort_init(s, device); });
 }
 
 static int sort_add(slx_sort *s, const void *stream, int64_t n_bytes, const void *rec_off, int64_t n_records, bool from_device, const char *who)
@@ -233,7 +221,7 @@ static int sort_tables(slx_sort *s)
     while (end_bit < 64 && (s->max_key >> end_bit)) ++end_bit;
     size_t tb_sort = 0, tb_scan = 0;          // one block for both: the sum finds it large enough and allocates nothing
     SLX_HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, s->d_key_in.as<ull>(), s->d_key_out.as<ull>(), s->d_ord_in.as<uint32_t>(), s->d_ord_out.as<uint32_t>(), N, 0, end_bit, st));
-    SLX_CHK(slx_exclusive_sum_bytes(s->d_slen.as<ull>(), s->d_doff.as<ull>(), N + 1, st, &tb_scan));
+    SLX_HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb_scan, s->d_slen.as<ull>(), s->d_doff.as<ull>(), N + 1, st));
     SLX_CHK(s->d_tmp.ensure(std::max(tb_sort, tb_scan) + 8));
     SLX_HIPCHK(hipcub::DeviceRadixSort::SortPairs(s->d_tmp.p, tb_sort, s->d_key_in.as<ull>(), s->d_key_out.as<ull>(), s->d_ord_in.as<uint32_t>(), s->d_ord_out.as<uint32_t>(), N, 0, end_bit, st));
     k_sort_perm<<<grid, 256, 0, st>>>(s->d_ord_out.as<uint32_t>(), s->d_len.as<uint32_t>(), s->d_src.as<ull>(), N, s->d_slen.as<ull>(), s->d_ssrc.as<ull>());

@@ -28,8 +28,9 @@ typedef unsigned long long ull;
 typedef SlxDevBuf<SlxMargin<4, 256>> TDBuf;
 typedef SlxPinBuf<SlxMargin<4, 256>> THBuf;
 
-struct slx_stats {
-    int device = -1;          // -1: host only
+static const char ST_NO_DEVICE[] = "no HIP device: batches are counted on MI355X only (no CPU fallback)";
+
+struct slx_stats : SlxGpu<> {
     st_lay L;
     st_par P = {0u, 0, 4096u, 0u};
     int32_t len_max = 250, isize_max = 2000;
@@ -39,63 +40,33 @@ struct slx_stats {
     std::vector<uint64_t> h_counts;          // G.size() rows when synced
     bool synced = true;
     std::vector<std::string> names;          // what slx_stats_group_name hands out
-    hipStream_t st = nullptr;
-    hipEvent_t ev[2] = {};
-    SlxDevBuf<SlxExact> d_counts;
+    SlxDevBuf<SlxExact> d_counts{*this};
     size_t rows_cap = 0;
-    TDBuf d_slots, d_koff, d_pool, d_in, d_off, d_long, d_misslist, d_miss[2], d_cnt, d_pick, d_keys, d_win;
-    THBuf h_cnt, h_list, h_keys;
+    TDBuf d_slots{*this}, d_koff{*this}, d_pool{*this}, d_in{*this}, d_off{*this}, d_long{*this}, d_misslist{*this}, d_miss[2] = {*this, *this}, d_cnt{*this}, d_pick{*this}, d_keys{*this},
+          d_win{*this};
+    THBuf h_cnt{*this}, h_list{*this}, h_keys{*this};
     int64_t c_seen = 0, c_counted = 0, c_long = 0, c_lds = 0, c_global = 0, c_miss = 0;
     double us_add = 0;
-    slx_stats() { st_layout_default(&L, len_max, isize_max); G.reset(group_slots); }
-    std::vector<TDBuf *> dbufs() { return {&d_slots, &d_koff, &d_pool, &d_in, &d_off, &d_long, &d_misslist, &d_miss[0], &d_miss[1], &d_cnt, &d_pick, &d_keys, &d_win}; }
-    std::vector<THBuf *> hbufs() { return {&h_cnt, &h_list, &h_keys}; }
+    slx_stats() : SlxGpu(ST_NO_DEVICE) { st_layout_default(&L, len_max, isize_max); G.reset(group_slots); }
     st_tab tab() const { return st_tab{d_slots.as<uint32_t>(), d_koff.as<uint32_t>(), d_pool.as<uint8_t>(), (uint32_t)G.slots.size() - 1, 0u}; }
 };
-
-static int st_need_gpu(const char *who, slx_stats *c)
-{
-    if (!c) { slx_set_error("%s: null object", who); return SLX_EINVAL; }
-    if (c->device < 0) { slx_set_error("%s: no HIP device: batches are counted on MI355X only (no CPU fallback)", who); return SLX_ENODEVICE; }
-    SLX_HIPCHK(hipSetDevice(c->device));
-    return SLX_OK;
-}
 
 extern "C" void slx_stats_free(slx_stats *c)
 {
     if (!c) return;
-    if (c->device >= 0) {
-        (void)hipSetDevice(c->device);
-        if (c->st) (void)hipStreamSynchronize(c->st);
-        c->d_counts.release();
-        for (TDBuf *b : c->dbufs()) b->release();
-        for (THBuf *b : c->hbufs()) b->release();
-        for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
-        if (c->st) (void)hipStreamDestroy(c->st);
-    }
+    c->close();
     delete c;
-}
-
-static int st_create_impl(slx_stats *c, int device)
-{
-    int ndev = 0;
-    if (device < 0 && (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)) { (void)hipGetLastError(); c->device = -1; return SLX_OK; }          // host only
-    SLX_CHK(slx_pick_device(device, "no HIP device: batches are counted on MI355X only (no CPU fallback)", "slx_stats_create", &c->device));
-    SLX_HIPCHK(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
-    for (auto &e : c->ev) SLX_HIPCHK(hipEventCreate(&e));
-    SLX_CHK(c->d_cnt.ensure(8 * ST_K_N)); SLX_CHK(c->h_cnt.ensure(8 * ST_K_N));
-    return SLX_OK;
 }
 
 extern "C" int slx_stats_create(int device, slx_stats **out)
 {
     if (!out) { slx_set_error("slx_stats_create: null argument"); return SLX_EINVAL; }
-    *out = nullptr;
-    slx_stats *c = new slx_stats();
-    const int rc = st_create_impl(c, device);
-    if (rc != SLX_OK) { slx_stats_free(c); return rc; }
-    *out = c;
-    return SLX_OK;
+    return slx_create(out, slx_stats_free, [&](slx_stats *c) {
+        SLX_CHK(c->open(device, "slx_stats_create", ST_NO_DEVICE, true));
+        if (c->device < 0) return (int)SLX_OK;          // host only
+        SLX_CHK(c->d_cnt.ensure(8 * ST_K_N)); SLX_CHK(c->h_cnt.ensure(8 * ST_K_N));
+        return (int)SLX_OK;
+    });
 }
 
 extern "C" int slx_stats_set(slx_stats *c, const char *key, int64_t v)
@@ -246,26 +217,19 @@ static int st_add(slx_stats *c, const uint8_t *d_s, uint64_t n_bytes, const ull 
     return SLX_OK;
 }
 
-static int st_add_args(const char *who, slx_stats *c, const void *s, int64_t n_bytes, const void *off, int64_t n)
-{
-    SLX_CHK(st_need_gpu(who, c));
-    if (n_bytes < 0 || n < 0 || (n_bytes && !s) || (n && !off)) { slx_set_error("%s: null or negative argument", who); return SLX_EINVAL; }
-    return SLX_OK;
-}
-
 extern "C" int slx_stats_add_device(slx_stats *c, const void *d_stream, int64_t n_bytes, const void *d_rec_off, int64_t n_records)
 {
-    SLX_CHK(st_add_args("slx_stats_add_device", c, d_stream, n_bytes, d_rec_off, n_records));
+    SLX_CHK(slx_need(c, "slx_stats_add_device"));
+    SLX_CHK(slx_batch_args("slx_stats_add_device", d_stream, n_bytes, d_rec_off, n_records));
     return st_add(c, (const uint8_t *)d_stream, (uint64_t)n_bytes, (const ull *)d_rec_off, (uint64_t)n_records);
 }
 
 extern "C" int slx_stats_add_host(slx_stats *c, const void *stream, int64_t n_bytes, const uint64_t *rec_off, int64_t n_records)
 {
-    SLX_CHK(st_add_args("slx_stats_add_host", c, stream, n_bytes, rec_off, n_records));
+    SLX_CHK(slx_need(c, "slx_stats_add_host"));
+    SLX_CHK(slx_batch_args("slx_stats_add_host", stream, n_bytes, rec_off, n_records));
     if (n_records == 0) return SLX_OK;
-    SLX_CHK(c->d_in.ensure((size_t)n_bytes + 16)); SLX_CHK(c->d_off.ensure(8 * ((size_t)n_records + 1)));
-    if (n_bytes) SLX_HIPCHK(hipMemcpyAsync(c->d_in.p, stream, (size_t)n_bytes, hipMemcpyHostToDevice, c->st));
-    SLX_HIPCHK(hipMemcpyAsync(c->d_off.p, rec_off, 8 * ((size_t)n_records + 1), hipMemcpyHostToDevice, c->st));
+    SLX_CHK(slx_batch_stage(c->d_in, c->d_off, 16, stream, n_bytes, rec_off, n_records, c->st));
     return st_add(c, c->d_in.as<uint8_t>(), (uint64_t)n_bytes, c->d_off.as<ull>(), (uint64_t)n_records);
 }
 
@@ -293,7 +257,7 @@ static int st_sync(const char *who, slx_stats *c)
 {
     if (!c) { slx_set_error("%s: null object", who); return SLX_EINVAL; }
     if (c->synced) return SLX_OK;
-    SLX_CHK(st_need_gpu(who, c));
+    SLX_CHK(slx_need(c, who));
     const size_t row = c->L.row;
     c->h_counts.assign((size_t)c->G.size() * row, 0);
     std::vector<uint64_t> all(c->h_counts.size() * ST_REPLICAS);
@@ -374,7 +338,7 @@ extern "C" int slx_stats_merge(slx_stats *dst, slx_stats *src)
     }
     SLX_CHK(st_sync("slx_stats_merge", src));
     if (src->G.size() == 0) return SLX_OK;
-    SLX_CHK(st_need_gpu("slx_stats_merge", dst));
+    SLX_CHK(slx_need(dst, "slx_stats_merge"));
     SLX_CHK(st_sync("slx_stats_merge", dst));
     const size_t row = dst->L.row;
     size_t n_new = 0;
