@@ -40,6 +40,7 @@ class BamReader {
     friend class STCoverage;          // addReads(BamReader&): the batches as they lie in HBM
     friend class BamStats;
     friend class RefGenome;           // NmMd(BamReader&): the same
+    friend class RecordEditor;        // Apply(BamReader&): the same
     template <typename T> friend class GenomicRegionCollection;          // OverlapReads / CountReads(BamReader&): the same
 public:
     BamReader() = default;

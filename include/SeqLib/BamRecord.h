@@ -318,6 +318,38 @@ public:
         std::string z(val);
         bam_aux_append(b.get(), tag.data(), 'Z', static_cast<int>(z.size() + 1), reinterpret_cast<const uint8_t *>(z.c_str()));
     }
+    /** Strip a tag: the first field of that name (SeqLib/BamRecord.h:633-637: bam_aux_get + bam_aux_del) */
+    void RemoveTag(const char *tag)
+    {
+        if (!b) return;
+        uint8_t *p = bam_aux_get(b.get(), tag);
+        if (p) bam_aux_del(b.get(), p);
+    }
+    /** Strip all tags (SeqLib/BamRecord.h:640-645).  The reference gives the tail back with realloc; here the block stays as it is (it may lie in a slab that
+     * many records share) and only l_data moves: the record's bytes are the same. */
+    void RemoveAllTags()
+    {
+        if (!b) return;
+        b->l_data = (int)(((size_t)b->core.n_cigar << 2) + (size_t)b->core.l_qname + (((size_t)b->core.l_qseq + 1) >> 1) + (size_t)b->core.l_qseq);
+    }
+    /** Sequence, qualities and all tags go; l_seq = 0 (src/BamRecord.cpp:368-388).  The block stays, as above. */
+    void ClearSeqQualAndTags()
+    {
+        if (!b) return;
+        b->l_data = (int)((size_t)b->core.l_qname + (size_t)b->core.n_cigar * sizeof(uint32_t));
+        b->core.l_qseq = 0;
+    }
+    /** The value of an f or d tag (src/BamRecord.cpp:845-859).  The reference steps over the type byte before it calls bam_aux2f, which then reads the value's
+     * first byte as the type; this one reads the value. */
+    bool GetFloatTag(std::string_view tag, float &out) const
+    {
+        if (!b) return false;
+        const uint8_t *aux = bam_aux_get(b.get(), tag.data());
+        if (!aux) return false;
+        if (*aux == 'f') { float v; std::memcpy(&v, aux + 1, 4); out = v; return true; }
+        if (*aux == 'd') { double v; std::memcpy(&v, aux + 1, 8); out = (float)v; return true; }
+        return false;
+    }
     bam1_t *raw() const { return b.get(); }
 
 private:

@@ -20,6 +20,7 @@
 #include "SeqLib/BamHeader.h"
 #include "SeqLib/BamReader.h"
 #include "SeqLib/GenomicRegionCollection.h"
+#include "SeqLib/RecordEditor.h"
 #include "SeqLib/UnalignedSequence.h"
 #include "seqlib_amd_rec.h"
 #include "seqlib_amd_ref.h"
@@ -127,6 +128,36 @@ public:
         down(m, nm, md);
         return (size_t)b.n_records;
     }
+    // calmd without leaving HBM: NM and MD of the batch the reader serves next, written back into its records there.  The editor's plan is applied, then NM:i is
+    // replaced and MD:Z is replaced from the columns slx_ref_nm_md_device left in HBM; a record that is not eligible keeps the tags it has (nm -1 and an empty
+    // MD add nothing).  The two adds join the editor's plan for this call only and leave it again: the plan needs room for two more adds and no NM or MD add of its own
+    // (std::invalid_argument otherwise).  The result is ed.Batch(); the reader's
+    // batch is used up.  Returns how many records that was, 0 at the end of the file; what Next() has handed out of the batch already is left out, as in NmMd(BamReader&).
+    size_t WriteNmMd(BamReader &rd, RecordEditor &ed)
+    {
+        need("WriteNmMd");
+        if (!rd.rd_) throw std::runtime_error("RefGenome::WriteNmMd - the reader is not open");
+        const std::vector<int32_t> map = tid_map(rd.Header());
+        if (!rd.advance()) return 0;
+        const slx_bam_batch &b = rd.batch_;
+        const int64_t k = b.n_records - (int64_t)rd.cur_;
+        const uint64_t first = b.rec_off[rd.cur_];
+        slx_ref_md m;
+        const int32_t none = -1;
+        check(slx_ref_nm_md_device(ref_, b.d_stream, b.n_bytes, (const uint64_t *)b.d_rec_off + rd.cur_, k, map.empty() ? &none : map.data(), (int64_t)map.size(), &m));
+        write_back(ed, m, (const uint8_t *)b.d_stream + first, b.n_bytes - (int64_t)first, (const uint64_t *)b.d_rec_off + rd.cur_, k);
+        rd.cur_ = (size_t)b.n_records;
+        return (size_t)k;
+    }
+    // ... of the records a builder left in HBM; their tids are taken as the FASTA's
+    size_t WriteNmMd(const slx_rec_batch &b, RecordEditor &ed)
+    {
+        need("WriteNmMd");
+        slx_ref_md m;
+        check(slx_ref_nm_md_device(ref_, b.d_stream, b.n_bytes, b.d_rec_off, b.n_records, nullptr, 0, &m));
+        write_back(ed, m, b.d_stream, b.n_bytes, b.d_rec_off, b.n_records);
+        return (size_t)b.n_records;
+    }
     // ... of records in host memory (uploaded, then the same kernels); their tids are taken as the FASTA's
     size_t NmMd(const BamRecordPtrVector &recs, std::vector<int32_t> &nm, std::vector<std::string> &md)
     {
@@ -169,6 +200,18 @@ private:
             map.push_back((int32_t)t);
         }
         return map;
+    }
+    void write_back(RecordEditor &ed, const slx_ref_md &m, const void *d_stream, int64_t n_bytes, const void *d_rec_off, int64_t n)
+    {
+        if (slx_edit_add_int_column(ed.e_, "NM", m.d_nm, -1, 1) != SLX_OK) throw std::invalid_argument(std::string("RefGenome::WriteNmMd - ") + slx_last_error());
+        if (slx_edit_add_z_column(ed.e_, "MD", m.d_md, m.md_bytes, m.d_md_off) != SLX_OK) {
+            const std::string why = slx_last_error();
+            (void)slx_edit_drop_column(ed.e_, "NM");
+            throw std::invalid_argument("RefGenome::WriteNmMd - " + why);
+        }
+        // the two adds are the call's own: they leave the plan again, whatever becomes of the apply, so that the editor is afterwards what the caller made it
+        struct Undo { slx_edit *e; ~Undo() { (void)slx_edit_drop_column(e, "MD"); (void)slx_edit_drop_column(e, "NM"); } } undo{ed.e_};
+        ed.Apply(d_stream, n_bytes, d_rec_off, n);
     }
     void down(const slx_ref_md &m, std::vector<int32_t> &nm, std::vector<std::string> &md) const
     {
