@@ -24,6 +24,7 @@
 #include <vector>
 #include "SeqLib/hts_compat.h"
 #include "seqlib_amd_filter.h"
+#include "seqlib_amd_win.h"
 
 namespace SeqLib {
 
@@ -253,6 +254,14 @@ public:
         out.reserve((size_t)b->core.l_qseq);
         for (int i = 0; i < b->core.l_qseq; ++i) out.push_back((char)(q[i] + offset));
         return out;
+    }
+    /** The stretch of the read between its first and its last base of quality qualTrim or more (src/BamRecord.cpp:591-624): (0, -1) for a read without bases or
+     * without qualities (qual[0] == 0xff), which stands for the whole read; (Length(), -1) when no base reaches qualTrim; otherwise [first, one past the last).
+     * The body the window collector's kernels run (slx_win_quality_trim, include/seqlib_amd_win.h). */
+    void QualityTrimmedSequence(int32_t qualTrim, int32_t &startpoint, int32_t &endpoint) const
+    {
+        startpoint = 0; endpoint = -1;
+        if (b) slx_win_quality_trim(bam_get_qual(b.get()), b->core.l_qseq, qualTrim, &startpoint, &endpoint);
     }
     Cigar GetCigar() const
     {

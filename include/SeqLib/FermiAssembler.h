@@ -14,7 +14,9 @@
 #include <stdexcept>
 #include <string>
 #include <vector>
+#include "SeqLib/BamReader.h"
 #include "SeqLib/BamRecord.h"
+#include "SeqLib/GenomicRegionCollection.h"
 #include "SeqLib/UnalignedSequence.h"
 #include "SeqLib/fml_compat.h"
 
@@ -185,6 +187,11 @@ public:
         }
     }
 
+    /** (new) The region loop in one call: every record the reader serves (SetRegions and SetReadFilter are honoured) becomes a read of each window it overlaps,
+     * in HBM, and the windows are assembled as AssembleWindows does -- contigs[w] = what the loop Next() + AddRead into window w's FermiAssembler +
+     * PerformAssembly() + GetContigs() returns.  SeqLib/AssemblyWindows.h, where it is defined, has the steps one by one. */
+    static void AssembleRegions(BamReader &reader, const GRC &windows, std::vector<std::vector<std::string> > &contigs, const fml_opt_t *options = nullptr);
+
 private:
     void push(const std::string &name, const std::string &seq, const std::string &qual, bool has_qual)
     {
@@ -218,3 +225,5 @@ private:
 };
 
 }  // namespace SeqLib
+
+#include "SeqLib/AssemblyWindows.h"          // AssembleRegions is defined there: the collector needs this header's context

@@ -15,7 +15,7 @@
  *   slx_fml_error_correct the histogram -> kcov -> min_cov -> kmer_correct block    src/BFC.cpp:289-362 (BFC::ErrorCorrect)
  *   slx_fml_count_dump    (new) test hook: the count table as sorted (k-mer, value) pairs
  *   slx_fml_assemble      fml_assemble                       src/FermiAssembler.cpp:140-143 (PerformAssembly)
- *   slx_fml_stage, slx_fml_assemble_staged   (new) fml_assemble on reads already resident in HBM; no reference counterpart
+ *   slx_fml_stage, slx_fml_stage_device, slx_fml_assemble_staged   (new) fml_assemble on reads already resident in HBM; no reference counterpart
  *   slx_fml_direct_assemble  fml_seq2fmi + fml_fmi2mag + fml_mag_clean + fml_mag2utg   src/FermiAssembler.cpp:26-44 (DirectAssemble)
  *   slx_fml_utgs_free     fml_utg_destroy                    src/FermiAssembler.cpp:103
  *
@@ -105,6 +105,10 @@ int  slx_fml_assemble(slx_fml *f, const slx_fml_opt *opt, const char *bases, con
 /* The same with the reads resident in HBM: slx_fml_stage uploads them once, slx_fml_assemble_staged assembles the staged reads (any
  * number of times; every call starts from the reads as staged).  What bench.py times: the reads are in HBM before the timed region. */
 int  slx_fml_stage(slx_fml *f, const char *bases, const char *quals, const uint64_t *offs, int64_t n_reads);
+/* slx_fml_stage with the three arrays already in HBM of the context's device (offs: n_reads + 1 uint64; d_quals may be NULL: no qualities): device-to-device
+ * copies, the offsets checked and the longest read found by a kernel, offs copied down (the window setup reads it on the host).  The refusals of slx_fml_stage:
+ * SLX_EUNSUPPORTED for a read above 32 000 bp, SLX_EINVAL for offsets that fall; SLX_EINVAL too for a pointer that is not memory of that device. */
+int  slx_fml_stage_device(slx_fml *f, const void *d_bases, const void *d_quals, const void *d_offs, int64_t n_reads);
 int  slx_fml_assemble_staged(slx_fml *f, const slx_fml_opt *opt, const int64_t *win_off, int n_win, slx_fml_utg **utgs, int *n_utg);
 /* FermiAssembler::DirectAssemble: no correction, no filter; min_ensr / min_insr derived from kcov as src/FermiAssembler.cpp:32-41 does
  * (the caller's opt is updated the same way) */

@@ -370,6 +370,80 @@ extern "C" int slx_fml_stage(slx_fml *f, const char *bases, const char *quals, c
     return SLX_OK;
 }
 
+// offs[0 .. n] in HBM: the first read whose offsets fall (atomicMin into st[0]) and the longest read (atomicMax into st[1])
+__global__ __launch_bounds__(256) void k_fml_offs_check(const unsigned long long *offs, unsigned long long n, unsigned long long *st)
+{
+    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long bad = ~0ull, len = 0;
+    if (i < n) {
+        const unsigned long long a = offs[i], b = offs[i + 1];
+        if (b < a) bad = i; else len = b - a;
+    }
+    for (int o = 32; o; o >>= 1) {
+        const unsigned long long b2 = __shfl_xor(bad, o, 64), l2 = __shfl_xor(len, o, 64);
+        bad = b2 < bad ? b2 : bad; len = l2 > len ? l2 : len;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (bad != ~0ull) atomicMin(&st[0], bad);
+        if (len) atomicMax(&st[1], len);
+    }
+}
+
+// d_p is memory of the context's device
+static int fml_on_device(const slx_fml *f, const void *d_p, const char *what)
+{
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, d_p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != f->device) {
+        (void)hipGetLastError();
+        slx_set_error("slx_fml_stage_device: %s is not memory of device %d, the context's", what, f->device);
+        return SLX_EINVAL;
+    }
+    return SLX_OK;
+}
+
+extern "C" int slx_fml_stage_device(slx_fml *f, const void *d_bases, const void *d_quals, const void *d_offs, int64_t n_reads)
+{
+    if (!f || n_reads < 0 || (n_reads > 0 && (!d_bases || !d_offs))) { slx_set_error("slx_fml_stage_device: bad argument"); return SLX_EINVAL; }
+    std::lock_guard<std::mutex> g(f->mu);
+    SLX_HIPCHK(hipSetDevice(f->device));
+    f->have_count = false; f->staged = false;
+    int rc;
+    if (n_reads > 0) {
+        if ((rc = fml_on_device(f, d_bases, "d_bases")) || (rc = fml_on_device(f, d_offs, "d_offs")) || (d_quals && (rc = fml_on_device(f, d_quals, "d_quals")))) return rc;
+    }
+    unsigned long long hst[2] = {~0ull, 0ull};
+    f->h_offs.assign((size_t)n_reads + 1, 0);
+    if ((rc = f->d_offs.ensure(((size_t)n_reads + 1) * 8)) || (rc = f->d_misc.ensure(64))) return rc;
+    if (n_reads > 0) {
+        SLX_HIPCHK(hipMemcpyAsync(f->d_misc.p, hst, 16, hipMemcpyHostToDevice, f->st));
+        k_fml_offs_check<<<(unsigned)((n_reads + 255) / 256), 256, 0, f->st>>>((const unsigned long long *)d_offs, (unsigned long long)n_reads, f->d_misc.as<unsigned long long>());
+        SLX_HIPCHK(hipGetLastError());
+        SLX_HIPCHK(hipMemcpyAsync(hst, f->d_misc.p, 16, hipMemcpyDeviceToHost, f->st));
+        SLX_HIPCHK(hipMemcpyAsync(f->h_offs.data(), d_offs, ((size_t)n_reads + 1) * 8, hipMemcpyDeviceToHost, f->st));
+        SLX_HIPCHK(slx_wait_stream(f->st));
+        if (hst[0] != ~0ull) { slx_set_error("fml: read offsets are not monotonic at read %llu", hst[0]); return SLX_EINVAL; }
+        if (hst[1] > 32000) { slx_set_error("fml: read of %llu bp: the correction kernels take reads up to 32000 bp", hst[1]); return SLX_EUNSUPPORTED; }
+    }
+    const uint64_t base0 = f->h_offs[0], total = f->h_offs[(size_t)n_reads] - base0;
+    for (uint64_t &o : f->h_offs) o -= base0;          // rebased to 0, as fml_upload leaves them
+    f->n_reads = n_reads; f->total = (int64_t)total; f->max_len = (int)hst[1]; f->has_qual = d_quals != nullptr;
+    f->planes_ok = false;
+    if ((rc = f->d_bases.ensure((size_t)total + 64)) || (rc = f->d_bases0.ensure((size_t)total + 64))) return rc;
+    if (d_quals && ((rc = f->d_quals.ensure((size_t)total + 64)) || (rc = f->d_quals0.ensure((size_t)total + 64)))) return rc;
+    SLX_HIPCHK(hipMemcpyAsync(f->d_offs.p, f->h_offs.data(), ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, f->st));
+    if (total) {
+        SLX_HIPCHK(hipMemcpyAsync(f->d_bases.p, (const char *)d_bases + base0, (size_t)total, hipMemcpyDeviceToDevice, f->st));
+        SLX_HIPCHK(hipMemcpyAsync(f->d_bases0.p, (const char *)d_bases + base0, (size_t)total, hipMemcpyDeviceToDevice, f->st));
+        if (d_quals) {
+            SLX_HIPCHK(hipMemcpyAsync(f->d_quals.p, (const char *)d_quals + base0, (size_t)total, hipMemcpyDeviceToDevice, f->st));
+            SLX_HIPCHK(hipMemcpyAsync(f->d_quals0.p, (const char *)d_quals + base0, (size_t)total, hipMemcpyDeviceToDevice, f->st));
+        }
+    }
+    SLX_HIPCHK(slx_wait_stream(f->st));
+    f->staged = true;
+    return SLX_OK;
+}
+
 extern "C" int slx_fml_assemble_staged(slx_fml *f, const slx_fml_opt *opt, const int64_t *win_off, int n_win, slx_fml_utg **utgs, int *n_utg)
 {
     int rc;

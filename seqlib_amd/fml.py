@@ -13,7 +13,7 @@ from . import _ffi
 # every symbol include/seqlib_amd_fml.h declares (checked by tests/test_abi.py against the header text)
 EXPORTS = [
     "slx_fml_opt_init", "slx_fml_opt_adjust", "slx_fml_create", "slx_fml_free", "slx_fml_correct", "slx_fml_count", "slx_fml_count_hist",
-    "slx_fml_error_correct", "slx_fml_count_dump", "slx_fml_assemble", "slx_fml_direct_assemble", "slx_fml_utgs_free", "slx_fml_probe_ms", "slx_fml_stage", "slx_fml_assemble_staged", "slx_fml_counter",
+    "slx_fml_error_correct", "slx_fml_count_dump", "slx_fml_assemble", "slx_fml_direct_assemble", "slx_fml_utgs_free", "slx_fml_probe_ms", "slx_fml_stage", "slx_fml_stage_device", "slx_fml_assemble_staged", "slx_fml_counter",
 ]
 SLX_FML_N_PROBES = 6
 MAG_F_AGGRESSIVE, MAG_F_POPOPEN, MAG_F_NO_SIMPL = 0x20, 0x40, 0x80
@@ -60,6 +60,7 @@ def lib():
         L.slx_fml_direct_assemble.argtypes = [C.c_void_p, C.POINTER(FmlOpt), C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.POINTER(Utg)), C.POINTER(C.c_int)]
         L.slx_fml_utgs_free.argtypes = [C.c_int, C.POINTER(Utg)]
         L.slx_fml_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+        L.slx_fml_stage_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
         L.slx_fml_assemble_staged.argtypes = [C.c_void_p, C.POINTER(FmlOpt), C.c_void_p, C.c_int, C.POINTER(C.POINTER(Utg)), C.POINTER(C.c_int)]
         L.slx_fml_counter.argtypes = [C.c_void_p, C.c_char_p]
         L.slx_fml_counter.restype = C.c_int64
@@ -180,6 +181,10 @@ class Context:
 
     def stage(self, bases, quals, offs):
         _ffi.check(lib().slx_fml_stage(self.h, bases.ctypes.data, quals.ctypes.data if quals is not None else None, offs.ctypes.data, len(offs) - 1))
+
+    def stage_device(self, d_bases, d_quals, d_offs, n_reads):
+        """the same with the arrays in HBM already: device pointers as ints (d_quals None: no qualities)"""
+        _ffi.check(lib().slx_fml_stage_device(self.h, d_bases, d_quals, d_offs, n_reads))
 
     def assemble_staged(self, opt, win_off, keep=True):
         """fml_assemble over the staged reads; keep=False frees the records at once and returns per-window (n_contigs, total length, lengths)"""
