@@ -42,6 +42,7 @@ class BamReader {
     friend class RefGenome;           // NmMd(BamReader&): the same
     friend class RecordEditor;        // Apply(BamReader&): the same
     friend class AssemblyWindows;     // addReads(BamReader&): the same
+    friend class DuplicateMarker;     // addReads(BamReader&): the same
     template <typename T> friend class GenomicRegionCollection;          // OverlapReads / CountReads(BamReader&): the same
 public:
     BamReader() = default;

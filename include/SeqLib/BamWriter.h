@@ -21,6 +21,9 @@
 // with SO:coordinate, the records of WriteRecord(s) and WriteDevice go into a sorter in HBM in call order, Close() sorts them there -- tid ascending as unsigned,
 // then pos, ties in call order -- and writes them; BuildIndex() afterwards succeeds.  Everything must fit the sorter's budget in HBM (half of what is free at
 // Open()); what does not is refused by the write that passes it.  No host fallback.  Without SortByCoordinate() the writer behaves exactly as before.
+// MarkDuplicates() after SortByCoordinate() and before Open() makes Close() mark the duplicates among the sorter's records (slx_dup_mark_sorter,
+// include/seqlib_amd_dup.h: bit 0x400 rewritten in HBM by that header's rules, the libraries from the header's @RG lines) before they are sorted and written:
+// the chain alignToBam, sort, mark, BGZF, BuildIndex() runs with no record on the host.  Without MarkDuplicates() no flag is touched.
 // UseGpuSam() before Open() moves a SAM writer's formatting to the GPU (slx_samw_*, include/seqlib_amd_samw.h): WriteRecord(s) serialise the records and hand them
 // over, WriteDevice(d, n, d_rec_off, n_records) takes records that lie in HBM -- which is what BWAAligner::alignToBam calls, so that it writes SAM -- and the text
 // is byte for byte what the host writer writes (format_sam below is the definition).  With bgzip the text leaves through the GPU BGZF writer as a bgzip'd SAM.
@@ -41,6 +44,7 @@
 #include "seqlib_amd_bam.h"
 #include "seqlib_amd_sort.h"
 #include "seqlib_amd_samw.h"
+#include "seqlib_amd_dup.h"
 
 namespace SeqLib {
 
@@ -62,7 +66,7 @@ public:
     }
     BamWriter(const BamWriter &) = delete;
     BamWriter &operator=(const BamWriter &) = delete;
-    ~BamWriter() { Close(); }
+    ~BamWriter() { Close(); if (marker) slx_dup_free(marker); }
 
     void SetHeader(const BamHeader &h) { hdr = h; }
     BamHeader Header() const { return hdr; }
@@ -97,6 +101,17 @@ public:
         sort_on = true;
         return true;
     }
+    // after SortByCoordinate(), before Open(): Close() marks the duplicates among the sorter's records before it sorts and writes them (see the top of the file)
+    bool MarkDuplicates()
+    {
+        if (IsOpen()) { std::cerr << "BamWriter::MarkDuplicates - call it before Open()" << std::endl; return false; }
+        if (!sort_on) { std::cerr << "BamWriter::MarkDuplicates - duplicates are marked among the sorter's records; call SortByCoordinate() first" << std::endl; return false; }
+        mark_on = true;
+        return true;
+    }
+    bool IsMarking() const { return marker != nullptr; }     // an open writer that marks duplicates
+    // slx_dup_counter of the marking writer; the counters of the last Close() stay readable until the next Open()
+    int64_t MarkCounter(const char *name) const { return marker ? slx_dup_counter(marker, name) : -1; }
     bool IsSorting() const { return sorter != nullptr; }      // an open writer that sorts
     int64_t SortCounter(const char *name) const { return sorter ? slx_sort_counter(sorter, name) : -1; }          // slx_sort_counter of the open sorting writer
 
@@ -125,6 +140,15 @@ public:
             if (sort_on && slx_sort_create(gpu_device, &sorter) != SLX_OK) {
                 std::cerr << "BamWriter::Open - " << slx_last_error() << std::endl;
                 sorter = nullptr;
+                (void)slx_bgzf_close(gz); gz = nullptr;
+                std::remove(f.c_str());
+                return false;
+            }
+            if (marker) { slx_dup_free(marker); marker = nullptr; }
+            if (mark_on && slx_dup_create(gpu_device, &marker) != SLX_OK) {
+                std::cerr << "BamWriter::Open - " << slx_last_error() << std::endl;
+                marker = nullptr;
+                slx_sort_free(sorter); sorter = nullptr;
                 (void)slx_bgzf_close(gz); gz = nullptr;
                 std::remove(f.c_str());
                 return false;
@@ -268,7 +292,12 @@ public:
         if (gz) {
             bool ok = true;
             if (sorter) {                                    // the sort, and the sorted stream into the writer
-                ok = sort_flush() && gpu_ok(slx_sort_finish(sorter, gz));
+                ok = sort_flush();
+                if (ok && marker) {
+                    const std::string text = hdr.AsString();
+                    ok = gpu_ok(slx_dup_set_header(marker, text.data(), (int64_t)text.size())) && gpu_ok(slx_dup_mark_sorter(marker, sorter));
+                }
+                ok = ok && gpu_ok(slx_sort_finish(sorter, gz));
                 slx_sort_free(sorter); sorter = nullptr;
             }
             ok = gpu_ok(slx_bgzf_close(gz)) && ok;           // the last member, the EOF block; the handle is freed
@@ -484,6 +513,8 @@ private:
     static constexpr size_t SORT_STAGE = (size_t)16 << 20;          // serialised bytes that make one slx_sort_add_host
     bool sort_on = false;           // SortByCoordinate()
     slx_sort *sorter = nullptr;     // of the open sorting writer
+    bool mark_on = false;           // MarkDuplicates()
+    slx_dup *marker = nullptr;      // of the marking writer; kept after Close() for its counters
     std::string sort_buf;           // records serialised for the sorter, and their offsets
     std::vector<uint64_t> sort_off;
 };

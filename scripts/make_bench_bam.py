@@ -4,9 +4,11 @@
 them reverse-complemented, stored as unmapped records -- so the same file feeds BWAAligner::alignSequences(BamReader&) with that reference's index.
 --sorted writes the coordinate-sorted variant tools/bamregion_bench.cpp takes: the same windows as mapped records (150M, 0x10 on half of them) at the
 place they were cut from, in (reference, position) order; --shuffled writes the same mapped records in random order (SO:unsorted), the input of
-tools/bamsort_bench.cpp; without either option the output is what it always was.
+tools/bamsort_bench.cpp; without either option the output is what it always was.  --pairs (with --shuffled) turns the first half of every slice of records
+into read pairs -- two neighbours share a name, 0x1 | 0x40 | 0x20 forward and 200 bp upstream, 0x1 | 0x80 | 0x10 reverse -- and lets every tenth pair and
+every tenth fragment take the place and strand of the one before it: the input of tools/bammarkdup_bench.cpp, about 10 % duplicates.
 
-    python scripts/make_bench_bam.py out.bam [--records 2000000] [--ref tests/golden/tiny.fa] [--procs 8] [--seed 1] [--sorted | --shuffled]
+    python scripts/make_bench_bam.py out.bam [--records 2000000] [--ref tests/golden/tiny.fa] [--procs 8] [--seed 1] [--sorted | --shuffled [--pairs]]
 """
 import argparse
 import os
@@ -84,11 +86,36 @@ def placed_records(first, ref, rng, tid, pos):
     return a, 40 + name_w
 
 
+def pair_up(a, rng):
+    """--pairs, in place: records 2k and 2k + 1 of the first half become a pair, and every tenth pair and fragment a duplicate of its predecessor"""
+    n = len(a)
+    k = n // 4
+    first, second = np.arange(0, 2 * k, 2), np.arange(1, 2 * k, 2)
+    pos = a[:, 8:12].copy().view("<i4").reshape(n)
+    a[second, 4:8] = a[first, 4:8]
+    a[second, 36:46] = a[first, 36:46]
+    pos[second] = pos[first]
+    pos[first] = np.maximum(pos[first] - 200, 0)
+    a[first, 18] = 0x1 | 0x40 | 0x20
+    a[second, 18] = 0x1 | 0x80 | 0x10
+    for j in np.nonzero(rng.random(k) < 0.1)[0]:
+        if j:
+            a[2 * j, 4:8] = a[2 * j - 2, 4:8]; a[2 * j + 1, 4:8] = a[2 * j - 2, 4:8]
+            pos[2 * j] = pos[2 * j - 2]; pos[2 * j + 1] = pos[2 * j - 1]
+    for i in 2 * k + 1 + np.nonzero(rng.random(n - 2 * k - 1) < 0.1)[0]:
+        a[i, 4:8] = a[i - 1, 4:8]; a[i, 18] = a[i - 1, 18]
+        pos[i] = pos[i - 1]
+    a[:, 8:12] = pos.astype("<i4").view(np.uint8).reshape(n, 4)
+    a[:, 14:16] = reg2bin(pos.astype(np.int64), pos.astype(np.int64) + L).astype("<u2").view(np.uint8).reshape(n, 2)
+
+
 def slice_job(args):
-    if len(args) == 6:
-        n, first, ref, seed, tid, start = args
+    if len(args) >= 6:
+        n, first, ref, seed, tid, start = args[:6]
         rng = np.random.default_rng(seed)
         a, so = placed_records(first, ref, rng, tid, start[1])
+        if len(args) == 7 and args[6]:
+            pair_up(a, rng)
         codes = ref[start[0][:, None] + np.arange(L)[None, :]]
         codes = np.where(rng.random((n, L)) < 0.01, (codes + rng.integers(1, 4, size=(n, L))) & 3, codes)
         nib = (1 << codes).astype(np.uint8)
@@ -108,7 +135,10 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--sorted", action="store_true", help="mapped records in coordinate order (the input of tools/bamregion_bench.cpp)")
     ap.add_argument("--shuffled", action="store_true", help="the mapped records of --sorted in random order (the input of tools/bamsort_bench.cpp)")
+    ap.add_argument("--pairs", action="store_true", help="with --shuffled: half of the records in pairs, about 10 %% duplicates (the input of tools/bammarkdup_bench.cpp)")
     o = ap.parse_args()
+    if o.pairs and not o.shuffled:
+        ap.error("--pairs goes with --shuffled")
     names, seqs = [], []
     for ln in open(o.ref):
         if ln.startswith(">"):
@@ -137,7 +167,7 @@ def main():
             order = order[np.random.default_rng(o.seed + 7).permutation(len(order))]
         g, tid = g[order], tid[order]
         pos = g - (ends[tid] - np.array([len(s) for s in seqs])[tid])
-        jobs = [j + (tid[j[1]:j[1] + j[0]], (g[j[1]:j[1] + j[0]], pos[j[1]:j[1] + j[0]])) for j in jobs]
+        jobs = [j + (tid[j[1]:j[1] + j[0]], (g[j[1]:j[1] + j[0]], pos[j[1]:j[1] + j[0]])) + ((True,) if o.pairs else ()) for j in jobs]
     with open(o.out, "wb") as f, ProcessPoolExecutor(o.procs) as ex:
         f.write(members(hdr))
         for part in ex.map(slice_job, jobs):

@@ -19,6 +19,7 @@
 #include <unistd.h>
 #include "slx_internal.h"
 #include "seqlib_amd_sort.h"
+#include "seqlib_amd_dup.h"
 #include "dev_wave.h"
 #include "dev_recsort.h"
 #include "recsort_host.h"
@@ -418,4 +419,26 @@ extern "C" int64_t slx_sort_counter(const slx_sort *s, const char *name)
     if (!strcmp(name, "held_records")) return (int64_t)s->held_records;
     if (!strcmp(name, "held_bytes")) return (int64_t)s->held_bytes;
     return -1;
+}
+
+// The duplicate marker's route through the sorter (include/seqlib_amd_dup.h): it lives here because the segments are this unit's.  The order key does not read
+// the flag, so the sort is what it would have been.
+extern "C" int slx_dup_mark_sorter(slx_dup *d, slx_sort *s)
+{
+    if (!d || !s) { slx_set_error("slx_dup_mark_sorter: null argument"); return SLX_EINVAL; }
+    if (slx_dup_counter(d, "device") != s->device) {
+        slx_set_error("slx_dup_mark_sorter: the marker is on device %lld, the sorter on device %d: both must be on one", (long long)slx_dup_counter(d, "device"), s->device);
+        return SLX_EINVAL;
+    }
+    if (slx_dup_counter(d, "records") != 0 || slx_dup_counter(d, "finished") != 0) { slx_set_error("slx_dup_mark_sorter: the marker is not empty (slx_dup_clear first)"); return SLX_EINVAL; }
+    SLX_HIPCHK(hipSetDevice(s->device));
+    SLX_HIPCHK(hipStreamSynchronize(s->st));
+    for (const Segment &g : s->segs) SLX_CHK(slx_dup_add_device(d, g.base, (int64_t)g.n_bytes, g.off, (int64_t)g.n));
+    SLX_CHK(slx_dup_finish(d));
+    int64_t first = 0;
+    for (const Segment &g : s->segs) {
+        SLX_CHK(slx_dup_apply_device(d, g.base, (int64_t)g.n_bytes, g.off, (int64_t)g.n, first, nullptr));
+        first += (int64_t)g.n;
+    }
+    return SLX_OK;
 }
