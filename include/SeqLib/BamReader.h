@@ -43,6 +43,7 @@ class BamReader {
     friend class RecordEditor;        // Apply(BamReader&): the same
     friend class AssemblyWindows;     // addReads(BamReader&): the same
     friend class DuplicateMarker;     // addReads(BamReader&): the same
+    friend class Pileup;              // addReads(BamReader&): the same
     template <typename T> friend class GenomicRegionCollection;          // OverlapReads / CountReads(BamReader&): the same
 public:
     BamReader() = default;

@@ -31,6 +31,7 @@ namespace SeqLib {
 struct RefBatch { const void *d_bases = nullptr, *d_offs = nullptr; int64_t n_regions = 0, n_bytes = 0; };
 
 class RefGenome {
+    friend class Pileup;              // Sites(RefGenome&): the reference's handle, as it lies in HBM
 public:
     RefGenome() = default;
     RefGenome(const RefGenome &) = delete;

@@ -30,7 +30,8 @@
  *   regions    a reader with SetRegions serves a record once per region it overlaps; such a record is counted once per time it is served.
  *
  * No CPU fallback for batches: without a GPU slx_cov_create succeeds with device = -1 (for slx_cov_free and the host-only slx_cov_record_intervals) and
- * every other entry returns SLX_ENODEVICE.  Not carried: the reference's unordered-map storage and its uint16 vector, per-base pileup, CRAM, several GPUs.
+ * every other entry returns SLX_ENODEVICE.  Not carried: the reference's unordered-map storage and its uint16 vector, CRAM, several GPUs.  The bases
+ * of the reads at a position (per-base pileup) are the pileup unit's: seqlib_amd_pile.h.
  */
 #ifndef SEQLIB_AMD_COV_H
 #define SEQLIB_AMD_COV_H
