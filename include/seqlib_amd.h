@@ -146,6 +146,10 @@ void slx_aligner_free(slx_aligner *al);
  *                             measures L; k_first_lanes clamps).  1: the jobs whose sides all have such a band run in a launch of their own on rows of 32 columns;
  *                             2: the band only; 3: as 1, the narrow jobs binned by sqrt(left^2 + right^2) like the others (1 bins them by bases x band width).
  *                             Same records; 0: every job in the band "w"
+ *   "wave_sort" 0|1|2 (1)     the sorts of a many-region read's handles (k_regs_wave, k_regs_wave_long: by region end; by score, rb, qb; by score, alt, hash) and of a
+ *                             many-hit read's hits (k_hits_wave) run on the whole wave as a compare-exchange network in LDS (dev_wave_sort.h) when the list has 128
+ *                             elements or more (shorter lists: ranks counted); with two equal keys, whose order the serial sorts decide, one lane sorts again from the
+ *                             saved order.  2: the network for every list (tests).  Same records; 0: ranks counted up to 768 elements, one lane beyond
  *   "first_lanes" 0|1 (1)     the other top-seed extensions of the light reads (the dynamic program) one lane per job, binned by work (k_first_lanes); 0: one wave per job (k_ext_first)
  *   "lane_narrow" 0|1 (1)     k_ext_lanes keeps 8-bit H / E cells when no score can reach 256
  *   "p2_coop" 0|1 (1)         seeding pass 2: re-seeding calls inside repeats one wave per call (k_seed2_coop); needs p2_items
@@ -255,7 +259,10 @@ int  slx_aligner_probe_launches(const slx_aligner *al);
  * "walk_staged_chains" = chains of the last batch that k_extend_reg opened from a lane-made header ("walk_stage"; 0 with the knob off);
  * "ext_narrow_sides" / "ext_narrow_jobs" = of the sides of k_first_lanes' jobs of the last batch that the diagonal does not answer, the ones given a narrow band /
  * the jobs whose sides all fit the narrow launch's 32 columns ("ext_narrow"; both 0 with the knob off);
- * "ext_row_exits" = dynamic programs of the last batch's short-read extension kernels (band trials, in the lane kernels) that the row exit ended ("ext_row_exit"; 0 with the knob off) */
+ * "ext_row_exits" = dynamic programs of the last batch's short-read extension kernels (band trials, in the lane kernels) that the row exit ended ("ext_row_exit"; 0 with the knob off);
+ * "sort_wave" / "sort_serial" = sorts of two or more handles in the last batch's wave-per-read region kernels that ended on the wave / fell back to one lane (two equal keys;
+ * with "wave_sort" 0 also more than 768 handles); "sort_serial_re" = of the latter, the reads' first sort, by region end;
+ * "hits_sort_wave" / "hits_sort_serial" = hit lists of the last batch that k_hits_wave sorted on the whole wave / on one lane (two equal keys, or more than 2 048 hits) */
 int64_t slx_aligner_counter(const slx_aligner *al, const char *key);
 
 /* Test hook (per-stage differential tests): intermediate results of one read of the LAST batch, copied out of the device work

@@ -9,8 +9,10 @@
 #pragma once
 #include "dev_ext.h"
 #include "dev_as.h"
+#include "dev_wave_sort.h"
 
 #define DEV_MINUS_INF (-0x40000000)
+#define SORT_NET_MIN 128          // "wave_sort" 1: lists of at least this many handles (regions of a read, hits of a read) are sorted by the network of dev_wave_sort.h
 
 // ksw_global2 (score; direction bytes into z when z != nullptr)
 template <typename QF, typename TF>
@@ -387,14 +389,43 @@ __device__ int dev_fin_regs(const DevRef &R, const Chunk &ck, const slx_opt &opt
         const bool dbg = ck.dbg_cyc && ck.dbg_stage == 2;
         unsigned long long t0 = dbg ? __builtin_readcyclecounter() : 0ull, t1 = t0, t2 = t0, t3 = t0;
         // sort a[0..m) with `less` over handles: in LDS by one lane when staged (fill(h) copies handle h's keys), else in place
-        auto sort_handles = [&](int m, auto fill, auto less_lds, auto less_glb) {
+        // (first: the read's first sort, by region end, for the "sort_serial_re" count)
+        auto sort_handles = [&](int m, bool first, auto fill, auto less_lds, auto less_glb) {
             if (!staged) { ks_introsort_idx(m, a, less_glb); return; }
             __threadfence_block();                                   // a[] and G[] were last written by other lanes' stores
             for (int i = S.lane; i < m; i += 64) { const int h = ag[i]; S.idx[i] = h; fill(h); }
             fin_sync<MAXQ>();
-            // When no two keys are equal every correct sort gives klib's order, so the wave counts ranks (64 elements at a time against
-            // all m, keys broadcast from LDS): ~m * m / 64 comparisons per lane instead of one lane's m log m at LDS latency.  With a tie
-            // anywhere the tie order of ks_introsort shows in the output: then the serial algorithm itself runs, on one lane as before.
+            auto count = [&](bool serial) {
+                if (S.lane != 0 || !ck.sort_cnt) return;
+                atomicAdd(ck.sort_cnt + (serial ? 1 : 0), 1u);
+                if (serial && first) atomicAdd(ck.sort_cnt + 2, 1u);
+            };
+            // When no two keys are equal every correct sort gives klib's order, so the wave sorts the handles in S.idx[] itself, with the
+            // compare-exchange network of dev_wave_sort.h: log2(m) * (log2(m) + 1) / 2 stages of m / 128 exchanges per lane.  With a tie
+            // anywhere the tie order of ks_introsort shows in the output: then S.idx[] is filled again from a[], which still holds the order
+            // before the sort, and the serial algorithm itself runs on it, on one lane.
+            // A stage costs two dependent LDS reads, a write and a barrier however short the list is; below SORT_NET_MIN handles the rank count
+            // further down (m * m / 64 steps that do not depend on each other) is the shorter way, as measured ("wave_sort" 2 = the network from 2 handles on).
+            if (ck.wave_sort && m >= (ck.wave_sort == 1 ? SORT_NET_MIN : 2)) {
+                const lds_ptr<int> idx = S.idx;
+                wave_sort(m, S.lane, [&](int i) { return idx[i]; }, [&](int i, int h) { idx[i] = h; }, less_lds, [] { fin_sync<MAXQ>(); });
+                const bool tie = __any(wave_sort_tie(m, S.lane, [&](int i) { return idx[i]; }, less_lds)) != 0;
+                count(tie);
+                if (!tie) for (int e = S.lane; e < m; e += 64) ag[e] = idx[e];
+                else {
+                    fin_sync<MAXQ>();                                // (every lane has looked at its neighbours)
+                    for (int i = S.lane; i < m; i += 64) idx[i] = ag[i];
+                    fin_sync<MAXQ>();
+                    if (S.lane == 0) ks_introsort_idx(m, idx, less_lds);
+                    fin_sync<MAXQ>();
+                    for (int i = S.lane; i < m; i += 64) ag[i] = idx[i];
+                }
+                fin_sync<MAXQ>();
+                __threadfence_block();
+                return;
+            }
+            // Short lists, and every list with "wave_sort" 0 (kept for comparison): ranks counted (64 elements at a time against all m, keys
+            // broadcast from LDS), ~m * m / 64 comparisons per lane, up to 768 handles; one lane beyond that and with a tie.
             bool tie = m > 768;                                      // (beyond that the quadratic count costs more than it saves on average)
             if (!tie) for (int e = S.lane; e < m; e += 64) {
                 const int he = S.idx[e];
@@ -407,6 +438,7 @@ __device__ int dev_fin_regs(const DevRef &R, const Chunk &ck, const slx_opt &opt
                 }
                 S.m_w[e] = rank;                                   // (m_w / m_rid are free during the three sorts)
             }
+            if (m >= 2) count(__any(tie) != 0);
             if (!__any(tie)) {
                 fin_sync<MAXQ>();
                 for (int e = S.lane; e < m; e += 64) S.m_rid[S.m_w[e]] = S.idx[e];
@@ -425,7 +457,7 @@ __device__ int dev_fin_regs(const DevRef &R, const Chunk &ck, const slx_opt &opt
         else for (int i = 0; i < n; ++i) a[i] = i;
         // ---------------- mem_sort_dedup_patch
         if (n > 1) {
-            sort_handles(n, [&](int h) { S.k64[h] = Gg[h].re; },
+            sort_handles(n, true, [&](int h) { S.k64[h] = Gg[h].re; },
                          [&](int x, int y) { return S.k64[x] < S.k64[y]; },
                          [&](int x, int y) { return G[x].re < G[y].re; });
             if (dbg) t1 = __builtin_readcyclecounter();
@@ -581,7 +613,7 @@ __device__ int dev_fin_regs(const DevRef &R, const Chunk &ck, const slx_opt &opt
             if (staged) m = compact_staged(n, 0);
             else for (int i = 0; i < n; ++i) if (G[a[i]].qe > G[a[i]].qb) a[m++] = a[i];
             n = m;
-            sort_handles(n, [&](int h) { S.ka[h] = Gg[h].score; S.k64[h] = Gg[h].rb; S.kb[h] = Gg[h].qb; },
+            sort_handles(n, false, [&](int h) { S.ka[h] = Gg[h].score; S.k64[h] = Gg[h].rb; S.kb[h] = Gg[h].qb; },
                          [&](int x, int y) {
                              const int sx = S.ka[x], sy = S.ka[y];
                              const int64_t bx = S.k64[x], by = S.k64[y];
@@ -686,7 +718,7 @@ __device__ int dev_fin_regs(const DevRef &R, const Chunk &ck, const slx_opt &opt
                     n_pri += (int)__popcll(__ballot(pri));
                 }
                 __threadfence_block();
-                sort_handles(n, [&](int h) { S.ka[h] = Gg[h].score; S.k64[h] = (int64_t)Gg[h].hash; },
+                sort_handles(n, false, [&](int h) { S.ka[h] = Gg[h].score; S.k64[h] = (int64_t)Gg[h].hash; },
                              [&](int x, int y) {
                                  const int sx = S.ka[x], sy = S.ka[y];
                                  if (sx != sy) return sx > sy;
@@ -699,7 +731,7 @@ __device__ int dev_fin_regs(const DevRef &R, const Chunk &ck, const slx_opt &opt
                     for (int i = lane; i < n; i += 64) { const int h = S.idx[i], sidx = Gg[h].secondary; l_par[h] = sidx >= 0 ? S.idx[sidx] : -1; }
                     fin_sync<MAXQ>();
                     if (n_pri > 0)
-                        sort_handles(n, [&](int h) { S.ka[h] = Gg[h].score; S.k64[h] = (int64_t)Gg[h].hash; },
+                        sort_handles(n, false, [&](int h) { S.ka[h] = Gg[h].score; S.k64[h] = (int64_t)Gg[h].hash; },
                                      [&](int x, int y) {
                                          const int ax = l_alt[x], ay = l_alt[y];
                                          if (ax != ay) return ax < ay;
@@ -735,7 +767,7 @@ __device__ int dev_fin_regs(const DevRef &R, const Chunk &ck, const slx_opt &opt
                 p.sub = 0; p.secondary = -1;
                 p.hash = dev_hash_64(id + (uint64_t)i);
             }
-            sort_handles(n, [&](int h) { S.ka[h] = Gg[h].score; S.k64[h] = (int64_t)Gg[h].hash; },
+            sort_handles(n, false, [&](int h) { S.ka[h] = Gg[h].score; S.k64[h] = (int64_t)Gg[h].hash; },
                          [&](int x, int y) {
                              const int sx = S.ka[x], sy = S.ka[y];
                              return sx > sy || (sx == sy && (uint64_t)S.k64[x] < (uint64_t)S.k64[y]);

@@ -435,6 +435,23 @@ __global__ void __launch_bounds__(64) k_regs_wave(DevRef R, Chunk ck, DevOpt dop
     }
 }
 
+// The lists of the two many-region launches of k_regs_wave.  The list of ALL multi-region reads of a chunk (~900 000 of 16.7 M reads of C3, in read order)
+// holds a few thousand reads for the 640-region table and a few dozen for the 2 048-region one.  A wave that takes that list one slot at a time pays an atomic
+// and two dependent loads per slot to skip nearly all of it: that walk, not the reads, was the launches' time (12 ms for 21 reads).  Here one lane per slot
+// copies the reads with lo..mid regions to list_mid and the ones beyond mid to list_big, so that the wave kernels take lists that hold their own reads only,
+// one read per take as before: reads that stand side by side in the batch still go to different waves.
+__global__ void __launch_bounds__(256) k_regs_pick(const int *order, const unsigned int *n_slots, const int *n_reg, int lo, int mid, int *list_mid, unsigned int *n_mid,
+                                                   int *list_big, unsigned int *n_big)
+{
+    const unsigned int n = *n_slots;
+    for (unsigned int t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
+        const int r = order[t];
+        const int nr = n_reg[r];
+        if (nr >= lo && nr <= mid) list_mid[wave_fetch_inc(n_mid)] = r;
+        else if (nr > mid && nr >= lo) list_big[wave_fetch_inc(n_big)] = r;
+    }
+}
+
 // final position / rid / clipping of mem_reg2aln once the core cigar [cs, cs+nc) is in the pool with one free slot on each side
 __device__ __forceinline__ void dev_finish_hit(const DevRef &R, const Chunk &ck, const DJob &j, int l_query, DHit &h, int64_t cs, int nc)
 {
@@ -737,10 +754,21 @@ __global__ void __launch_bounds__(64, CIG_MIN_WAVES) k_cig_dp(DevRef R, Chunk ck
 
 // Reads with many hits (a read inside a repeat keeps hundreds): on one lane the sort of 500 hits is ~30 000 dependent loads while the other 63 lanes of its wave
 // wait -- the whole of k_hits' time was a few thousand such reads (1.5 active lanes per instruction).  k_hits puts reads with more than HITS_BIG hits on a list
-// and k_hits_wave takes them one wave per read: keys in LDS, ranks counted 64 elements at a time against all (every correct sort gives std::sort's order when no
+// and k_hits_wave takes them one wave per read: keys in LDS, sorted there by the whole wave (every correct sort gives std::sort's order when no
 // two keys are equal; with a tie anywhere the serial algorithm itself runs on lane 0, as before), the filters as a scan with the primary's score carried along.
 #define HITS_BIG 12
 #define HITS_WAVE_N 2048
+// the glue's hit order (src/BWAAligner.cpp:133): mapq descending, then rid, then pos
+__device__ __forceinline__ bool dev_hit_less(int am, int ar, int64_t ap, int bm, int br, int64_t bp)
+{
+    if (am != bm) return am > bm;
+    if (ar != br) return ar < br;
+    return ap < bp;
+}
+// a hit's keys as one record of k_hits_wave's network sort: the keys themselves move, and the hit's number rides below the mapq
+struct HitKey { int64_t pos; int rid, mq_e; };          // mq_e = mapq << HIT_KEY_SH | number in the read's list (< HITS_WAVE_N)
+#define HIT_KEY_SH 11
+static_assert(HITS_WAVE_N <= 1 << HIT_KEY_SH, "HitKey: the hit's number must fit below the mapq");
 __global__ void __launch_bounds__(64) k_hits_wave(Chunk ck, const int *list, const unsigned int *n_list, unsigned int *queue)
 {
     __shared__ int64_t s_pos[HITS_WAVE_N];
@@ -756,12 +784,22 @@ __global__ void __launch_bounds__(64) k_hits_wave(Chunk ck, const int *list, con
         int *hh = w.ic;
         auto less_glb = [&](int x, int y) {
             const DHit &A = w.hits[x], &B = w.hits[y];
-            if (A.mapq != B.mapq) return A.mapq > B.mapq;
-            if (A.rid != B.rid) return A.rid < B.rid;
-            return A.pos < B.pos;
+            return dev_hit_less(A.mapq, A.rid, A.pos, B.mapq, B.rid, B.pos);
         };
         bool serial = nh > HITS_WAVE_N;
-        if (!serial) {
+        if (!serial && ck.wave_sort && nh >= (ck.wave_sort == 1 ? SORT_NET_MIN : 2)) {
+            // the records sorted in place by the wave's compare-exchange network (dev_wave_sort.h): log2(nh) * (log2(nh) + 1) / 2 stages of nh / 128 exchanges
+            // per lane, each two record reads with nothing depending on another read.  No two records equal: every correct sort gives std::sort's order.
+            __syncthreads();                                  // (the previous read's keys are no longer read)
+            for (int e = lane; e < nh; e += 64) { const DHit &h = w.hits[e]; s_pos[e] = h.pos; s_rid[e] = h.rid; s_mapq[e] = (int)h.mapq << HIT_KEY_SH | e; }
+            __syncthreads();
+            auto load = [&](int i) { HitKey k; k.pos = s_pos[i]; k.rid = s_rid[i]; k.mq_e = s_mapq[i]; return k; };
+            auto store = [&](int i, const HitKey &k) { s_pos[i] = k.pos; s_rid[i] = k.rid; s_mapq[i] = k.mq_e; };
+            auto less = [](const HitKey &a, const HitKey &b) { return dev_hit_less(a.mq_e >> HIT_KEY_SH, a.rid, a.pos, b.mq_e >> HIT_KEY_SH, b.rid, b.pos); };
+            wave_sort(nh, lane, load, store, less, [] { __syncthreads(); });
+            serial = __any(wave_sort_tie(nh, lane, load, less)) != 0;
+            if (!serial) for (int e = lane; e < nh; e += 64) hh[e] = s_mapq[e] & ((1 << HIT_KEY_SH) - 1);
+        } else if (!serial) {                                 // short lists, and "wave_sort" 0: ranks counted, 64 elements at a time against all
             __syncthreads();                                  // (the previous read's keys are no longer read)
             for (int e = lane; e < nh; e += 64) { const DHit &h = w.hits[e]; s_pos[e] = h.pos; s_rid[e] = h.rid; s_mapq[e] = h.mapq; }
             __syncthreads();
@@ -775,7 +813,7 @@ __global__ void __launch_bounds__(64) k_hits_wave(Chunk ck, const int *list, con
                 for (int j = 0; j < nh; ++j) {                // (keys broadcast from LDS: every lane reads the same address)
                     const int jm = s_mapq[j], jr = s_rid[j];
                     const int64_t jp = s_pos[j];
-                    const bool lt = jm != em ? jm > em : (jr != er ? jr < er : jp < ep);
+                    const bool lt = dev_hit_less(jm, jr, jp, em, er, ep);
                     rank += lt ? 1 : 0;
                     if (live && j != e && jm == em && jr == er && jp == ep) tie = true;
                 }
@@ -784,6 +822,7 @@ __global__ void __launch_bounds__(64) k_hits_wave(Chunk ck, const int *list, con
             serial = __any(tie) != 0;
         }
         __threadfence_block();
+        if (lane == 0 && ck.sort_cnt) atomicAdd(ck.sort_cnt + (serial ? 6 : 5), 1u);          // "hits_sort_serial" / "hits_sort_wave"
         if (serial) {
             if (lane == 0) {
                 for (int i = 0; i < nh; ++i) hh[i] = i;

@@ -138,6 +138,8 @@ struct Chunk {
     int dbg_stage;                 // 1 = the extension kernel fills them, 2 = the region kernel
     int ext_row_exit;              // "ext_row_exit": 1 = the short-read extension loops end after a row that rules out any change (dev_ext_wave.h, "the row exit")
     unsigned int *ext_exits;       // ... DPs / band trials it ended ("ext_row_exits"; may be null)
+    int wave_sort;                 // "wave_sort": 1 = the staged region sorts and the many-hit sort run on the wave's compare-exchange network (dev_wave_sort.h) from SORT_NET_MIN elements on, 2 = always; 0 = ranks counted
+    unsigned int *sort_cnt;        // ... [0] staged region sorts that ended on the wave, [1] that fell back to one lane, [2] of those the sorts by region end; [5] / [6] hit sorts of k_hits_wave that ended on the wave / on one lane ([3], [4] are not counters) (may be null)
     // per-read results
     int32_t *n_chain;         // kept chains
     int32_t *n_reg;

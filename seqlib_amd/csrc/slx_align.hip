@@ -556,6 +556,7 @@ extern "C" int slx_aligner_set(slx_aligner *al, const char *key, int64_t value)
     else if (!strcmp(key, "top_reuse")) al->top_reuse = value != 0;
     else if (!strcmp(key, "walk_stage")) al->walk_stage = value != 0;
     else if (!strcmp(key, "ext_row_exit")) al->ext_row_exit = value != 0;
+    else if (!strcmp(key, "wave_sort")) { if (value < 0 || value > 2) return SLX_EINVAL; al->wave_sort = (int)value; }
     else if (!strcmp(key, "ext_narrow")) { if (value < 0 || value > 3) return SLX_EINVAL; al->ext_narrow = (int)value; }
     else if (!strcmp(key, "p2_items")) al->p2_items = value != 0;
     else if (!strcmp(key, "p2_coop")) al->p2_coop = value != 0;
@@ -661,7 +662,18 @@ extern "C" int64_t slx_aligner_counter(const slx_aligner *al, const char *key)
             if (al->is_group) for (const slx_aligner *sub : al->subs) take(sub); else take(al);
             return v;
         }
-        if (!strcmp(key, "ext_row_exits")) {          // last batch: DPs of the short-read extension kernels ended by the row exit (ext_row_exit)
+        // last batch: staged region sorts that ended on the wave / fell back to one lane (a tie; with wave_sort = 0 also more than 768 handles) / of those the first sort, by
+        // region end; hit sorts of k_hits_wave that ended on the wave / on one lane
+        static const char *const sort_keys[5] = {"sort_wave", "sort_serial", "sort_serial_re", "hits_sort_wave", "hits_sort_serial"};
+        int which = -1;
+        for (int i = 0; i < 5; ++i) if (!strcmp(key, sort_keys[i])) which = i;
+        if (which >= 0) {
+            long long v = 0;
+            auto take = [&](const slx_aligner *a) { for (const Worker *wk : a->workers) v += (long long)wk->sort_stat[which]; };
+            if (al->is_group) for (const slx_aligner *sub : al->subs) take(sub); else take(al);
+            return v;
+        }
+        if (!strcmp(key, "ext_row_exits")) {        // last batch: DPs of the short-read extension kernels ended by the row exit (ext_row_exit)
             long long v = 0;
             auto take = [&](const slx_aligner *a) { for (const Worker *wk : a->workers) v += (long long)wk->exit_stat; };
             if (al->is_group) for (const slx_aligner *sub : al->subs) take(sub); else take(al);
@@ -799,6 +811,7 @@ static int worker_run(slx_aligner *al, Worker *wk, const slx_opt *opt, const uin
     wk->walk_stat = 0;
     wk->exit_stat = 0;
     wk->narrow_stat[0] = wk->narrow_stat[1] = 0;
+    for (unsigned long long &c : wk->sort_stat) c = 0;
     int rc;
     const int64_t n_part = r_hi - r_lo;
     if ((rc = wk->o_hit_off.ensure(((size_t)n_part + 1) * 8)) != SLX_OK) return rc;

@@ -70,6 +70,7 @@ struct Worker {
     unsigned long long walk_stat = 0;                                              // k_extend_reg: chains it served from a lane-made header, of the last batch
     unsigned long long narrow_stat[2] = {0, 0};                                    // k_first_diag: DP sides given a narrow band, jobs whose sides all have one, of the last batch
     unsigned long long exit_stat = 0;                                              // extension kernels: DPs (lane kernels: band trials) the row exit ended, of the last batch
+    unsigned long long sort_stat[5] = {0, 0, 0, 0, 0};                             // region kernels: staged sorts that ended on the wave / fell back to one lane / of those the sorts by region end; k_hits_wave: hit sorts on the wave / on one lane, of the last batch
     unsigned int pseg_stat = 0;                                                    // ... how many
     unsigned int gseg_stat[3] = {0, 0, 0};                                         // ... segments taken as speculated / run again / jobs cut
     unsigned int xseg_stat[4] = {0, 0, 0, 0};                                      // ... segments taken as speculated / computed again / second band tries / sides cut, summed over this worker's launches
@@ -206,6 +207,9 @@ struct slx_aligner {
                                   // reads (dev_ext_wave.h, "the row exit"); 0 = they run to z-drop, an all-zero row or the tail bound
     int ext_narrow = 1;           // 1 = a top-seed extension of a light read whose flank loses little on its main diagonal runs in the narrow band that bound allows (ext_narrow_band,
                                   // dev_lane_rows.h), and the jobs whose sides all have one run on LaneRing rows in a launch of their own; 2 = the band only, one launch; 3 = as 1 with the narrow jobs binned by the wide launch's key (for measuring); 0 = neither
+    int wave_sort = 1;            // 1 = the sorts of the many-region reads' handles (dev_fin_regs, staged) and of the many-hit reads' hits (k_hits_wave) run on the wave as a
+                                  // compare-exchange network in LDS (dev_wave_sort.h) from SORT_NET_MIN elements on, one lane only when two keys are equal; 2 = the network from two
+                                  // elements on (tests); 0 = ranks counted up to 768 elements, one lane beyond
     int seed_free_cus = 0;        // see "seed_free_cus" in slx_aligner_set
     int stream_prio = 0;
     int n_workers = 3;            // concurrent parts of a large batch

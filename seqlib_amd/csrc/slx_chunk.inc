@@ -412,12 +412,16 @@ static void launch_tail(slx_aligner *al, Worker *wk, const Chunk &ck, const DevO
     if constexpr (MAXQ <= 704) {
         if (al->regs_big < (1 << 20)) {   // two launches: a 640-region LDS table at six waves per CU, then the few reads beyond it on the 2 048-region table
             const int mid = std::max(al->regs_big, REGS_MID_N);
+            // each launch takes a list of its own reads (k_regs_pick; part_flag / part_pos are free since the scatter above), counts in queue words 64 / 65
+            int *list_mid = wk->part_flag.as<int>(), *list_big = wk->part_pos.as<int>();
+            hipLaunchKernelGGL(k_regs_pick, dim3(std::max(1, std::min(n / 256 + 1, al->n_cu * 8))), dim3(256), 0, st, (const int *)multi, (const unsigned int *)(cnt2 + 1), (const int *)ck.n_reg,
+                               al->regs_big, al->regs_big <= REGS_MID_N ? REGS_MID_N : al->regs_big - 1, list_mid, q + 64, list_big, q + 65);
             if (al->regs_big <= REGS_MID_N)
                 hipLaunchKernelGGL((k_regs_wave<MAXQ, REGS_MID_N>), dim3(std::max(1, std::min(n / 64 + 1, al->n_cu * 8))), dim3(64), 0, st, al->ref, ck, dopt, fl,
-                                   multi, q + 11, cnt2 + 1, al->regs_big, REGS_MID_N);
+                                   (const int *)list_mid, q + 11, (const unsigned int *)(q + 64), al->regs_big, REGS_MID_N);
             if (mid < 512 || wk->max_seed_cnt > (unsigned int)mid)       // (regions <= seed occurrences; counts up to 512 are not tracked)
                 hipLaunchKernelGGL((k_regs_wave<MAXQ, REGS_BIG_N>), dim3(std::max(1, std::min(n / 4096 + 1, al->n_cu))), dim3(64), 0, st, al->ref, ck, dopt, fl,
-                                   multi, q + 15, cnt2 + 1, al->regs_big <= REGS_MID_N ? mid + 1 : al->regs_big, 1 << 30);
+                                   (const int *)list_big, q + 15, (const unsigned int *)(q + 65), al->regs_big <= REGS_MID_N ? mid + 1 : al->regs_big, 1 << 30);
         }
         // the lane-per-read kernel hands the reads in which mem_patch_reg would run its alignment on to a wave-per-read launch (queue words 46 / 47)
         int *defer_list = (al->regs_defer && wk->defer_list.ensure((size_t)n * 4) == SLX_OK) ? wk->defer_list.as<int>() : nullptr;
@@ -634,8 +638,8 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
     ENS(counters, 64); ENS(p2mask, (size_t)n * 8); ENS(p2list, (size_t)n * 4); ENS(p2items, (size_t)n * 4); ENS(p2long, (size_t)n * 4);
     // counters: [0] zused, [1] cigused, [2] flags(u32), then one u32 of site bits that raise no flag (OVS_Z_DP_WAVE, dev_types.h)
     HIPCHK(hipMemsetAsync(wk->counters.p, 0, 64, st));
-    ENS(queues, 256);
-    HIPCHK(hipMemsetAsync(wk->queues.p, 0, 256, st));
+    ENS(queues, 320);          // (80 words: 0..63 as numbered at their uses, 64 / 65 the lengths of the two many-region lists of k_regs_pick)
+    HIPCHK(hipMemsetAsync(wk->queues.p, 0, 320, st));
     wk->first_lanes_ran = false;
     HIPCHK(hipMemsetAsync(wk->seed_cnt.as<unsigned long long>() + n, 0, 8, st));      // (k_seed_epi writes the count of every read; the scan takes n + 1 entries)
 
@@ -663,6 +667,7 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
     ck.sam_mode = (opt->flag & SLX_F_REG2SAM) ? 1 : 0;
     ck.seed_cnt = wk->seed_cnt.as<unsigned long long>();
     ck.ext_row_exit = al->ext_row_exit; ck.ext_exits = wk->queues.as<unsigned int>() + 56;          // [56] DPs the row exit ended (the extension kernels add to it)
+    ck.wave_sort = al->wave_sort; ck.sort_cnt = wk->queues.as<unsigned int>() + 61;          // [61] staged region sorts that ended on the wave, [62] that fell back to one lane, [63] of those the sorts by region end; [66] / [67] hit sorts of k_hits_wave on the wave / on one lane (sort_cnt[5], [6])
     const bool production = al->chain_mode == 1 && n >= al->split_min && !has_long;
     const bool use_cand = al->cand_mode == 1 && production;
     if (use_cand) {
@@ -1079,7 +1084,7 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
         m_defer = part(wk->queues.as<unsigned int>() + 46, 1);          // reads k_regs deferred to the wave kernel
         m_big = part(wk->queues.as<unsigned int>() + 48, 1);            // reads k_hits left to k_hits_wave
         m_chain = part(wk->queues.as<unsigned int>() + 50, 2);          // reads k_chain_lds started over on the HBM columns, reads it finished in LDS
-        m_walk = part(wk->queues.as<unsigned int>() + 55, 5);           // chains k_extend_reg opened from a lane-made header, DPs the row exit ended, -, narrow jobs, narrow sides
+        m_walk = part(wk->queues.as<unsigned int>() + 55, 13);          // chains k_extend_reg opened from a lane-made header, DPs the row exit ended, -, narrow jobs, narrow sides, (a queue), the region sorts' three counts, (two list lengths), the hit sorts' two counts
         if (wk->first_lanes_ran) m_first = part(wk->queues.as<unsigned int>() + 54, 1);          // jobs k_first_lanes counted as run
         if (m_hits < 0 || m_cig < 0 || m_flags < 0 || m_defer < 0 || m_big < 0 || m_chain < 0 || m_walk < 0 || (wk->first_lanes_ran && m_first < 0)) {
             slx_set_error("run_chunk: more counters than k_mail has parts (SLX_MAIL_PARTS)");
@@ -1096,6 +1101,8 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
     wk->walk_stat += wk->h_mail[m_walk];
     wk->exit_stat += wk->h_mail[m_walk + 1];
     wk->narrow_stat[0] += wk->h_mail[m_walk + 4]; wk->narrow_stat[1] += wk->h_mail[m_walk + 3];
+    for (int i = 0; i < 3; ++i) wk->sort_stat[i] += wk->h_mail[m_walk + 6 + i];
+    wk->sort_stat[3] += wk->h_mail[m_walk + 11]; wk->sort_stat[4] += wk->h_mail[m_walk + 12];
     if (m_first >= 0) wk->first_stat += wk->h_mail[m_first];
     // grow the outputs and compact
     const size_t H = (size_t)*hit_base + Hc, C = (size_t)*cig_base + Cc;
@@ -1196,6 +1203,9 @@ static int run_chunk(slx_aligner *al, Worker *wk, const slx_opt *opt, const uint
                 fprintf(stderr, "[>= 256 regions, l_rep >= %d] reads %ld  mean ticks %.3g\n", lb[b], cnt, cnt ? (double)cy / (double)cnt : 0.0);
             }
         }
+        if (ck.dbg_stage == 2)
+            fprintf(stderr, "[region sorts] wave_sort %d: on the wave %llu, one lane %llu (of those by region end %llu)\n", al->wave_sort, (unsigned long long)wk->h_mail[m_walk + 6],
+                    (unsigned long long)wk->h_mail[m_walk + 7], (unsigned long long)wk->h_mail[m_walk + 8]);
         fprintf(stderr, "[ext cycles] n=%d total=%.3g (100 MHz ticks) heavy share=%.3f\n", n, (double)tot, tot ? (double)tot_heavy / (double)tot : 0.0);
         for (int i = 0; i < top; ++i) {
             const size_t r = (size_t)ord[(size_t)i];
