@@ -21,6 +21,10 @@
 // with SO:coordinate, the records of WriteRecord(s) and WriteDevice go into a sorter in HBM in call order, Close() sorts them there -- tid ascending as unsigned,
 // then pos, ties in call order -- and writes them; BuildIndex() afterwards succeeds.  Everything must fit the sorter's budget in HBM (half of what is free at
 // Open()); what does not is refused by the write that passes it.  No host fallback.  Without SortByCoordinate() the writer behaves exactly as before.
+// SortByCoordinate(spill_prefix) is the same for an output beyond that budget: the write that would pass it first writes the sorter's records, sorted, as a run
+// file "<spill_prefix>.run%04d.bam" (slx_sort_spill), and Close() merges the runs into the file (slx_merge_*, include/seqlib_amd_merge.h) and removes them; the file
+// is byte for byte what the plain overload writes when everything fits.  WriteHeader() comes before the first record, as the runs carry the header.  It does not
+// combine with MarkDuplicates(), which works among the records the sorter holds: Open() then returns false with a message.
 // MarkDuplicates() after SortByCoordinate() and before Open() makes Close() mark the duplicates among the sorter's records (slx_dup_mark_sorter,
 // include/seqlib_amd_dup.h: bit 0x400 rewritten in HBM by that header's rules, the libraries from the header's @RG lines) before they are sorted and written:
 // the chain alignToBam, sort, mark, BGZF, BuildIndex() runs with no record on the host.  Without MarkDuplicates() no flag is touched.
@@ -101,6 +105,14 @@ public:
         sort_on = true;
         return true;
     }
+    // the same, for an output that may pass the sorter's budget: sorted runs go to "<spill_prefix>.run%04d.bam" and Close() merges them (see the top of the file)
+    bool SortByCoordinate(const std::string &spill_prefix)
+    {
+        if (spill_prefix.empty()) { std::cerr << "BamWriter::SortByCoordinate - an empty spill prefix; SortByCoordinate() sorts without run files" << std::endl; return false; }
+        if (!SortByCoordinate()) return false;
+        spill_prefix_ = spill_prefix;
+        return true;
+    }
     // after SortByCoordinate(), before Open(): Close() marks the duplicates among the sorter's records before it sorts and writes them (see the top of the file)
     bool MarkDuplicates()
     {
@@ -114,6 +126,15 @@ public:
     int64_t MarkCounter(const char *name) const { return marker ? slx_dup_counter(marker, name) : -1; }
     bool IsSorting() const { return sorter != nullptr; }      // an open writer that sorts
     int64_t SortCounter(const char *name) const { return sorter ? slx_sort_counter(sorter, name) : -1; }          // slx_sort_counter of the open sorting writer
+    // slx_sort_set of the open sorting writer ("max_bytes", "slab_bytes").  With a budget below four stages of host records a stage shrinks to a quarter of it,
+    // so that a spilling writer fills its runs
+    bool SortKnob(const char *key, int64_t v)
+    {
+        if (!sorter) { std::cerr << "BamWriter::SortKnob - no open sorting writer" << std::endl; return false; }
+        if (!gpu_ok(slx_sort_set(sorter, key, v))) return false;
+        if (!std::strcmp(key, "max_bytes")) sort_stage = std::max<size_t>(1, std::min<size_t>(SORT_STAGE, (size_t)v / 4));
+        return true;
+    }
 
     bool Open(const std::string &f)
     {
@@ -132,6 +153,11 @@ public:
             return true;
         }
         if (use_gpu) {
+            if (mark_on && !spill_prefix_.empty()) {
+                std::cerr << "BamWriter::Open - MarkDuplicates() marks among the records the sorter holds and does not combine with SortByCoordinate(spill_prefix); sort with spilling, "
+                             "then mark the file (slx_dup_file)" << std::endl;
+                return false;
+            }
             if (slx_bgzf_open(f.c_str(), gpu_device, &gz) != SLX_OK) {
                 std::cerr << "BamWriter::Open - " << slx_last_error() << std::endl;
                 gz = nullptr;
@@ -154,6 +180,7 @@ public:
                 return false;
             }
             sort_buf.clear(); sort_off.assign(1, 0);
+            sort_stage = SORT_STAGE;
             return true;
         }
         fop = (f == "-") ? stdout : std::fopen(f.c_str(), "wb");
@@ -196,6 +223,7 @@ public:
             h += nm; h.push_back('\0');
             put32(h, (uint32_t)hdr.GetSequenceLength(i));
         }
+        if (sorter && !spill_prefix_.empty() && !gpu_ok(slx_sort_spill(sorter, spill_prefix_.c_str(), h.data(), (int64_t)h.size()))) return false;          // the runs carry the header
         if (gz) return gpu_ok(slx_bgzf_write(gz, h.data(), (int64_t)h.size())) && gpu_ok(slx_bgzf_flush(gz));
         if (!bgzf_write(h.data(), h.size())) return false;
         return bgzf_flush();                         // htslib starts the records in a fresh block
@@ -217,7 +245,7 @@ public:
             if (!format_sam(b, line)) return false;
             return std::fwrite(line.data(), 1, line.size(), fop) == line.size();
         }
-        if (sorter) { put_record(b, sort_buf); sort_off.push_back(sort_buf.size()); return sort_buf.size() < SORT_STAGE || sort_flush(); }
+        if (sorter) { put_record(b, sort_buf); sort_off.push_back(sort_buf.size()); return sort_buf.size() < sort_stage || sort_flush(); }
         std::string rec;
         rec.reserve(36 + (size_t)b->l_data);
         put_record(b, rec);
@@ -248,7 +276,7 @@ public:
                 if (!b) return false;
                 put_record(b, sort_buf); sort_off.push_back(sort_buf.size());
             }
-            return sort_buf.size() < SORT_STAGE || sort_flush();
+            return sort_buf.size() < sort_stage || sort_flush();
         }
         many.clear();
         for (const BamRecordPtr &r : recs) {
@@ -511,7 +539,9 @@ private:
     bool sam_bgzip = false;
     slx_samw *samw = nullptr;       // the open GPU SAM writer
     static constexpr size_t SORT_STAGE = (size_t)16 << 20;          // serialised bytes that make one slx_sort_add_host
+    size_t sort_stage = SORT_STAGE;
     bool sort_on = false;           // SortByCoordinate()
+    std::string spill_prefix_;      // SortByCoordinate(spill_prefix): where the run files go
     slx_sort *sorter = nullptr;     // of the open sorting writer
     bool mark_on = false;           // MarkDuplicates()
     slx_dup *marker = nullptr;      // of the marking writer; kept after Close() for its counters

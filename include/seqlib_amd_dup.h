@@ -94,7 +94,8 @@ int  slx_dup_flags_to_host(slx_dup *d, uint8_t *dst, int64_t cap);
 int  slx_dup_clear(slx_dup *d);
 
 /* adds the records the sorter holds, segment by segment in input order, finishes, and applies the verdicts to the segments where they lie: what
- * slx_sort_finish or slx_sort_to_host hands out afterwards carries the marks.  The marker must be empty and on the sorter's device. */
+ * slx_sort_finish or slx_sort_to_host hands out afterwards carries the marks.  The marker must be empty and on the sorter's device.  SLX_EUNSUPPORTED for a sorter that has spilled runs to disk
+ * (slx_sort_spill): the marker works among held records only, and slx_dup_file is the route for files beyond HBM. */
 int  slx_dup_mark_sorter(slx_dup *d, slx_sort *s);
 
 /* in_path marked into out_path.  Pass 1 reads the file into a marker, taking the header's @RG lines; pass 2 reads it again, applies batch by batch in HBM and

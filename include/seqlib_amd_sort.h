@@ -14,6 +14,8 @@
  *   slx_sort_to_host       (new) the sorted stream, its offsets and the permutation copied down, for tests and tools
  *   slx_sort_file, slx_sort_file_ex     (new) file to file, what `samtools sort` is called for between BamWriter::Close and BamWriter::BuildIndex
  *   slx_sort_header        the SO: field of the @HD line that sam_hdr_write emits for a sorted file (host only)
+ *   slx_sort_spill, slx_sort_file_spill (new) the sort of an input beyond HBM: sorted runs on disk, merged by a slx_merge (seqlib_amd_merge.h) -- the
+ *                          temporary files and the merge of `samtools sort`
  *   slx_sort_set, slx_sort_counter      (new) knobs and diagnostics
  *
  * The rules.
@@ -24,7 +26,10 @@
  *   The bytes    are never edited, the stored bin included.
  *   The arena    one segment of HBM per add call, filled by one device-to-device (or host-to-device) copy and never moved again.  The budget "max_bytes"
  *                is, by default, HALF of the HBM that is free when slx_sort_create runs (the rest is for the sort's tables -- 60 bytes per record -- one
- *                slab, and the writer's staging).  What does not fit is refused: there is no out-of-core merge.
+ *                slab, and the writer's staging).  What does not fit is refused -- unless slx_sort_spill has named a place for run files: then the add
+ *                that would pass the budget first writes the held records, sorted, as a run file and empties the arena, and slx_sort_finish merges the runs
+ *                (at most 64) with a slx_merge.  Runs are consecutive stretches of the input, each sorted stably, and the merge breaks ties by run index,
+ *                then by position: the result is the stable sort of the whole, byte for byte the file an arena that held everything would have given.
  *   The header   (slx_sort_header) an @HD line with an SO: field gets its value replaced, every other field and the field order kept; an @HD line without
  *                SO: gets "\tSO:coordinate" appended; a text without @HD gets "@HD\tVN:1.6\tSO:coordinate\n" in front.
  *   Refusals     SLX_EUNSUPPORTED: more bytes than max_bytes (the message gives both figures), 2^32 records or more.  SLX_EINVAL: offsets that do not rise
@@ -33,7 +38,7 @@
  *                that does not end at n_bytes; it is found by the key kernel before any byte is gathered, and nothing of the call is added.
  *
  * Not carried: samtools' further tie-break on the strand flag (ties keep input order instead, which is what makes a sorted input come out unchanged),
- * sorting by name or by tag, an out-of-core merge for inputs beyond HBM, CRAM, SAM text.  NUL padding behind the header text is not kept by slx_sort_file.
+ * sorting by name or by tag, a second merge pass for more than 64 runs, merging the last run from HBM instead of through a file, CRAM, SAM text.  NUL padding behind the header text is not kept by slx_sort_file.
  *
  * No CPU fallback: without a GPU slx_sort_create, slx_sort_file and slx_sort_file_ex return SLX_ENODEVICE.
  */
@@ -72,6 +77,16 @@ int  slx_sort_to_host(slx_sort *s, void *dst, uint64_t cap, uint64_t *rec_off_ds
  * _ex: with the caller's sorter -- its device, its knobs, its counters; it must be empty, and is empty afterwards. */
 int  slx_sort_file(const char *in_path, const char *out_path, int device);
 int  slx_sort_file_ex(slx_sort *s, const char *in_path, const char *out_path);
+/* prefix != NULL: an add that would pass max_bytes first writes the held records, sorted, as the run file "<prefix>.run%04d.bam" -- bam_header[0, l_header)
+ * (a BAM header block) in a member of its own, the records, the EOF block, through the GPU BGZF writer -- and empties the sorter; slx_sort_finish then
+ * writes what is still held as a last run and merges all runs into w with a slx_merge.  NULL: off, the default, behaviour as before.  With no run spilled
+ * slx_sort_finish does what it does without the call.  Run files are removed by slx_sort_finish, by an error of a spill or of the merge, and by slx_sort_free;
+ * a refused add (a single call's records beyond max_bytes stay refused) leaves the sorter and its runs as they were.  More than 64 runs: SLX_EUNSUPPORTED with the
+ * count, and the runs are removed.  While runs are pending slx_sort_to_host returns SLX_EUNSUPPORTED, and so does the duplicate marker's route through the sorter
+ * (seqlib_amd_dup.h: the marker works among held records only, and its file-to-file route is the one for large files); slx_sort_spill itself SLX_EINVAL. */
+int  slx_sort_spill(slx_sort *s, const char *prefix, const void *bam_header, int64_t l_header);
+/* slx_sort_file_ex with spilling for the length of the call; prefix NULL = out_path */
+int  slx_sort_file_spill(slx_sort *s, const char *in_path, const char *out_path, const char *prefix);
 /* host only, no GPU: the header text of a coordinate-sorted file made from text[0, l_text) (the rule above).  Returns its length; it is written to dst when
  * cap holds it (no terminator is added).  SLX_EINVAL: a null text or a negative length.  The rule itself is one host function (recsort_host.h beside the
  * kernels); it is exported because the header-only BamWriter reaches the library through this ABI alone, so that the class and slx_sort_file share the
@@ -81,7 +96,8 @@ int64_t slx_sort_header(const char *text, int64_t l_text, char *dst, int64_t cap
  * hand-over to the writer;  "batch_bytes" (64 MiB; >= 1): the reader's batch size in slx_sort_file_ex */
 int  slx_sort_set(slx_sort *s, const char *key, int64_t value);
 /* over the sorter's life: "records", "bytes", "segments", "slabs", and kernel times from HIP events in microseconds "us_key", "us_sort" (tables, radix sort,
- * prefix sum), "us_gather"; what it holds now: "held_records", "held_bytes"; -1 = unknown name */
+ * prefix sum), "us_gather"; of the spill "runs", "run_bytes" (record bytes written to run files) and "us_merge" (wall time of the merge of the runs); what it
+ * holds now: "held_records", "held_bytes"; -1 = unknown name */
 int64_t slx_sort_counter(const slx_sort *s, const char *name);
 
 #ifdef __cplusplus

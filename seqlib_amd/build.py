@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libseqlib_amd.so")
-SOURCES = ["slx_index.cpp", "slx_index_gpu.hip", "slx_index_gpu64.hip", "slx_align.hip", "slx_align_wide.hip", "slx_fml.hip", "slx_fml_asm.hip", "slx_bam.hip", "slx_bai.cpp", "slx_bgzf.hip", "slx_rec.hip", "slx_sort.hip", "slx_filter.hip", "slx_fastq.hip", "slx_sam.hip", "slx_samw.hip", "slx_cov.hip", "slx_stats.hip", "slx_ref.hip", "slx_grc.hip", "slx_edit.hip", "slx_win.hip", "slx_dup.hip", "slx_pile.hip"]
+SOURCES = ["slx_index.cpp", "slx_index_gpu.hip", "slx_index_gpu64.hip", "slx_align.hip", "slx_align_wide.hip", "slx_fml.hip", "slx_fml_asm.hip", "slx_bam.hip", "slx_bai.cpp", "slx_bgzf.hip", "slx_rec.hip", "slx_sort.hip", "slx_filter.hip", "slx_fastq.hip", "slx_sam.hip", "slx_samw.hip", "slx_cov.hip", "slx_stats.hip", "slx_ref.hip", "slx_grc.hip", "slx_edit.hip", "slx_win.hip", "slx_dup.hip", "slx_pile.hip", "slx_merge.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-value",
          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 
@@ -61,7 +61,7 @@ def build(force=False, verbose=False):
         subprocess.check_call(cmd)
     # tools/*: the C++ drop-in class timed end to end (bench.py's value_bamrecords, value_per_call); host-only code over the C-ABI (csrc is on the include path
     # for the tools whose host loops run a *_host.h themselves)
-    for name in ("bamrec_bench", "percall_bench", "bamread_bench", "bamregion_bench", "bamwrite_bench", "alignbam_bench", "bamsort_bench", "bamfilter_bench", "fastq_bench", "samread_bench", "samwrite_bench", "bamcov_bench", "bamstats_bench", "refgenome_bench", "grc_bench", "bamedit_bench", "bamasm_bench", "bammarkdup_bench", "bampile_bench"):
+    for name in ("bamrec_bench", "percall_bench", "bamread_bench", "bamregion_bench", "bamwrite_bench", "alignbam_bench", "bamsort_bench", "bamfilter_bench", "fastq_bench", "samread_bench", "samwrite_bench", "bamcov_bench", "bamstats_bench", "refgenome_bench", "grc_bench", "bamedit_bench", "bamasm_bench", "bammarkdup_bench", "bampile_bench", "bammerge_bench"):
         tool_src = os.path.join(ROOT, "tools", name + ".cpp")
         tool = os.path.join(HERE, name)
         dep = os.path.join(HERE, "build", name + ".d")

@@ -8,6 +8,8 @@
 //   hipCUB            exclusive sum of the lengths = dst_off
 //   k_sort_gather     one wave per RS_TILE bytes of the sorted stream, brought together in LDS, stored 16 bytes per lane; launched per slab (a range of tiles)
 // Records map to lanes and tiles to waves statically: no work queue.
+// Beyond HBM (slx_sort_spill): the add that would pass max_bytes first writes the held records through the same tables and gather as a sorted run file, and
+// slx_sort_finish hands the runs to a slx_merge (slx_merge.hip).  Without a spill prefix no line of that runs.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
@@ -16,10 +18,12 @@
 #include <cstring>
 #include <string>
 #include <vector>
+#include <chrono>
 #include <unistd.h>
 #include "slx_internal.h"
 #include "seqlib_amd_sort.h"
 #include "seqlib_amd_dup.h"
+#include "seqlib_amd_merge.h"
 #include "dev_wave.h"
 #include "dev_recsort.h"
 #include "recsort_host.h"
@@ -76,6 +80,8 @@ __global__ __launch_bounds__(256) void k_sort_gather(const ull *dst_off, const u
 }
 
 // ------------------------------------------------------------------ host
+static void sort_put32(std::string &o, uint32_t v) { const char b[4] = {(char)v, (char)(v >> 8), (char)(v >> 16), (char)(v >> 24)}; o.append(b, 4); }
+
 namespace {
 // no margin: the tables are sized by the held records, which max_bytes bounds -- HBM a margin took would be HBM the budget cannot give to records
 typedef SlxDevBuf<SlxExact> SBuf;
@@ -100,7 +106,21 @@ struct slx_sort : SlxGpu<> {
     SHBuf h_state{*this};                          // two sort_state: [0] goes up, [1] comes down
     int64_t c_records = 0, c_bytes = 0, c_segments = 0, c_slabs = 0;
     double us_key = 0, us_sort = 0, us_gather = 0;
+    // slx_sort_spill: the run files of the sort in progress, in the order their records were added
+    bool spill_on = false;
+    std::string spill_prefix, spill_header;
+    std::vector<std::string> runs;
+    int64_t c_runs = 0, c_run_bytes = 0;
+    double us_merge = 0;
 };
+
+static const size_t SORT_MAX_RUNS = 64;          // what one merger takes (MG_MAX_IN of dev_merge.h)
+
+static void sort_drop_runs(slx_sort *s)
+{
+    for (const std::string &r : s->runs) (void)unlink(r.c_str());
+    s->runs.clear();
+}
 
 static void sort_clear(slx_sort *s)
 {
@@ -114,6 +134,7 @@ extern "C" void slx_sort_free(slx_sort *s)
     if (!s) return;
     if (s->st) { (void)hipSetDevice(s->device); (void)hipStreamSynchronize(s->st); }
     sort_clear(s);          // (the segments are the sorter's own hipMalloc blocks: they go once the stream has drained, before the context closes)
+    sort_drop_runs(s);
     s->close();
     delete s;
 }
@@ -137,6 +158,8 @@ extern "C" int slx_sort_create(int device, slx_sort **out)
     return slx_create(out, slx_sort_free, [&](slx_sort *s) { return sort_init(s, device); });
 }
 
+static int sort_spill_run(slx_sort *s);
+
 static int sort_add(slx_sort *s, const void *stream, int64_t n_bytes, const void *rec_off, int64_t n_records, bool from_device, const char *who)
 {
     if (!s || n_bytes < 0 || n_records < 0 || (n_records && (!stream || !rec_off))) { slx_set_error("%s: null argument or negative size", who); return SLX_EINVAL; }
@@ -144,8 +167,9 @@ static int sort_add(slx_sort *s, const void *stream, int64_t n_bytes, const void
         if (n_bytes) { slx_set_error("%s: %lld bytes in 0 records", who, (long long)n_bytes); return SLX_EINVAL; }
         return SLX_OK;
     }
+    if (s->spill_on && s->held_records && n_bytes <= s->max_bytes && s->held_bytes + (uint64_t)n_bytes > (uint64_t)s->max_bytes) SLX_CHK(sort_spill_run(s));
     if (s->held_bytes + (uint64_t)n_bytes > (uint64_t)s->max_bytes) {
-        slx_set_error("%s: %llu bytes of records do not fit the sorter's max_bytes of %lld (the sort is in HBM only: there is no out-of-core merge)", who,
+        slx_set_error("%s: %llu bytes of records do not fit the sorter's max_bytes of %lld (without slx_sort_spill the sort is in HBM only, and one call's records are never split)", who,
                       (ull)(s->held_bytes + (uint64_t)n_bytes), (long long)s->max_bytes);
         return SLX_EUNSUPPORTED;
     }
@@ -266,9 +290,88 @@ static int sort_finish_impl(slx_sort *s, slx_bgzf *w)
     return SLX_OK;
 }
 
+// The held records, sorted, as the next run file: the header block in a member of its own, the records, the EOF block.  Empties the sorter.  On an error the
+// run files written so far go too, and nothing is held.
+static int sort_spill_run(slx_sort *s)
+{
+    auto run = [&]() -> int {
+        if (s->runs.size() >= SORT_MAX_RUNS) {
+            slx_set_error("slx_sort: run %zu would be written: more than %zu runs cannot be merged in one pass (raise max_bytes)", s->runs.size() + 1, SORT_MAX_RUNS);
+            return SLX_EUNSUPPORTED;
+        }
+        char num[32];
+        snprintf(num, sizeof num, ".run%04d.bam", (int)s->runs.size());
+        const std::string path = s->spill_prefix + num;
+        slx_bgzf *w = nullptr;
+        SLX_CHK(slx_bgzf_open(path.c_str(), s->device, &w));
+        s->runs.push_back(path);
+        int rc = slx_bgzf_write(w, s->spill_header.data(), (int64_t)s->spill_header.size());
+        if (rc == SLX_OK) rc = slx_bgzf_flush(w);
+        const int64_t bytes = (int64_t)s->held_bytes;
+        if (rc == SLX_OK) rc = sort_finish_impl(s, w);
+        const std::string msg = rc != SLX_OK ? slx_last_error() : "";
+        const int rc2 = slx_bgzf_close(w);
+        if (rc != SLX_OK) { slx_set_error("%s", msg.c_str()); return rc; }
+        SLX_CHK(rc2);
+        ++s->c_runs; s->c_run_bytes += bytes;
+        return SLX_OK;
+    };
+    const int rc = run();
+    const std::string msg = rc != SLX_OK ? slx_last_error() : "";
+    (void)hipSetDevice(s->device);
+    (void)hipStreamSynchronize(s->st);
+    sort_clear(s);
+    if (rc != SLX_OK) { sort_drop_runs(s); slx_set_error("%s", msg.c_str()); }
+    return rc;
+}
+
+// the run files merged into w; they are removed whatever happens
+static int sort_merge_runs(slx_sort *s, slx_bgzf *w)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    slx_merge *m = nullptr;
+    int rc = slx_merge_create(s->device, &m);
+    if (rc == SLX_OK) rc = slx_merge_set(m, "slab_bytes", s->slab_bytes);
+    if (rc == SLX_OK) rc = slx_merge_set(m, "batch_bytes", std::max<int64_t>(1, std::min<int64_t>(s->batch_bytes, s->max_bytes / (int64_t)std::max<size_t>(s->runs.size(), 1))));
+    for (size_t i = 0; rc == SLX_OK && i < s->runs.size(); ++i) rc = slx_merge_add_file(m, s->runs[i].c_str());
+    if (rc == SLX_OK) rc = slx_merge_run(m, w);
+    const std::string msg = rc != SLX_OK ? slx_last_error() : "";
+    if (m) slx_merge_free(m);
+    sort_drop_runs(s);
+    s->us_merge += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    if (rc != SLX_OK) slx_set_error("%s", msg.c_str());
+    return rc;
+}
+
+extern "C" int slx_sort_spill(slx_sort *s, const char *prefix, const void *bam_header, int64_t l_header)
+{
+    if (!s || (prefix && (!bam_header || l_header < 12))) { slx_set_error("slx_sort_spill: null argument, or a header block that cannot be one"); return SLX_EINVAL; }
+    if (!s->runs.empty()) { slx_set_error("slx_sort_spill: %zu runs are pending; slx_sort_finish first", s->runs.size()); return SLX_EINVAL; }
+    s->spill_on = prefix != nullptr;
+    s->spill_prefix = prefix ? prefix : "";
+    s->spill_header = prefix ? std::string((const char *)bam_header, (size_t)l_header) : std::string();
+    return SLX_OK;
+}
+
 extern "C" int slx_sort_finish(slx_sort *s, slx_bgzf *w)
 {
     if (!s || !w) { slx_set_error("slx_sort_finish: null argument"); return SLX_EINVAL; }
+    if (!s->runs.empty()) {          // the sort went beyond HBM: what is still held is the last run, and the runs are merged
+        int rc = slx_bgzf_write_device(w, nullptr, 0), wdev = -1;
+        if (rc == SLX_OK && (hipGetDevice(&wdev) != hipSuccess || wdev != s->device)) {
+            slx_set_error("slx_sort_finish: the writer is on device %d, the sorter on device %d: both must be on one", wdev, s->device);
+            rc = SLX_EINVAL;
+        }
+        if (rc == SLX_OK && s->held_records) rc = sort_spill_run(s);
+        if (rc == SLX_OK) return sort_merge_runs(s, w);
+        const std::string msg = slx_last_error();
+        (void)hipSetDevice(s->device);
+        (void)hipStreamSynchronize(s->st);
+        sort_clear(s);
+        sort_drop_runs(s);
+        slx_set_error("%s", msg.c_str());
+        return rc;
+    }
     // the writer takes the slabs by a device-to-device copy inside its own device: an empty write makes it select that device, which must be the sorter's
     int rc = slx_bgzf_write_device(w, nullptr, 0), wdev = -1;
     if (rc == SLX_OK && (hipGetDevice(&wdev) != hipSuccess || wdev != s->device)) {
@@ -287,6 +390,7 @@ extern "C" int slx_sort_finish(slx_sort *s, slx_bgzf *w)
 extern "C" int slx_sort_to_host(slx_sort *s, void *dst, uint64_t cap, uint64_t *rec_off_dst, uint32_t *perm_dst)
 {
     if (!s) { slx_set_error("slx_sort_to_host: null argument"); return SLX_EINVAL; }
+    if (!s->runs.empty()) { slx_set_error("slx_sort_to_host: %zu runs were spilled to disk: only slx_sort_finish brings them together", s->runs.size()); return SLX_EUNSUPPORTED; }
     const uint64_t B = s->held_bytes, N = s->held_records;
     if (B > cap || (B && !dst)) { slx_set_error("slx_sort_to_host: %llu bytes do not fit the %llu given", (ull)B, (ull)cap); return SLX_EINVAL; }
     if (N == 0) { if (rec_off_dst) rec_off_dst[0] = 0; return SLX_OK; }
@@ -318,18 +422,11 @@ extern "C" int64_t slx_sort_header(const char *text, int64_t l_text, char *dst, 
     return (int64_t)out.size();
 }
 
-static void sort_put32(std::string &o, uint32_t v) { const char b[4] = {(char)v, (char)(v >> 8), (char)(v >> 16), (char)(v >> 24)}; o.append(b, 4); }
-
-static int sort_file_impl(slx_sort *s, slx_bam *rd, const char *out_path, bool *created)
+// the header block of the sorted file: SO:coordinate by the rule, the reader's references
+static std::string sort_header_block(slx_bam *rd)
 {
-    for (;;) {
-        slx_bam_batch b;
-        SLX_CHK(slx_bam_next(rd, s->batch_bytes, &b));
-        if (b.n_records == 0) break;
-        SLX_CHK(slx_sort_add_device(s, b.d_stream, b.n_bytes, b.d_rec_off, b.n_records));
-    }
     const char *text = nullptr; int64_t l_text = 0; int n_ref = 0;
-    SLX_CHK(slx_bam_header(rd, &text, &l_text, &n_ref));
+    if (slx_bam_header(rd, &text, &l_text, &n_ref) != SLX_OK) return std::string();
     const std::string so = recsort_header_so(std::string(text, (size_t)l_text));
     std::string h("BAM\1", 4);
     sort_put32(h, (uint32_t)so.size());
@@ -341,6 +438,22 @@ static int sort_file_impl(slx_sort *s, slx_bam *rd, const char *out_path, bool *
         h += nm; h.push_back('\0');
         sort_put32(h, (uint32_t)slx_bam_ref_len(rd, i));
     }
+    return h;
+}
+
+static int sort_file_impl(slx_sort *s, slx_bam *rd, const char *out_path, bool *created, const char *spill_prefix)
+{
+    if (spill_prefix) {
+        const std::string h = sort_header_block(rd);
+        SLX_CHK(slx_sort_spill(s, spill_prefix, h.data(), (int64_t)h.size()));
+    }
+    for (;;) {
+        slx_bam_batch b;
+        SLX_CHK(slx_bam_next(rd, s->batch_bytes, &b));
+        if (b.n_records == 0) break;
+        SLX_CHK(slx_sort_add_device(s, b.d_stream, b.n_bytes, b.d_rec_off, b.n_records));
+    }
+    const std::string h = sort_header_block(rd);
     slx_bgzf *w = nullptr;
     SLX_CHK(slx_bgzf_open(out_path, s->device, &w));
     *created = true;
@@ -353,29 +466,39 @@ static int sort_file_impl(slx_sort *s, slx_bam *rd, const char *out_path, bool *
     return rc2;
 }
 
-extern "C" int slx_sort_file_ex(slx_sort *s, const char *in_path, const char *out_path)
+static int sort_file_with(slx_sort *s, const char *in_path, const char *out_path, const char *spill_prefix)
 {
     if (!s || !in_path || !out_path) { slx_set_error("slx_sort_file: null argument"); return SLX_EINVAL; }
     if (!strcmp(in_path, out_path) || !strcmp(in_path, "-") || !strcmp(out_path, "-")) {
         slx_set_error("slx_sort_file: '%s' -> '%s': the output must be another file than the input, and neither is a pipe", in_path, out_path);
         return SLX_EINVAL;
     }
-    if (s->held_records) { slx_set_error("slx_sort_file_ex: the sorter holds %llu records; it must be empty", (ull)s->held_records); return SLX_EINVAL; }
+    if (s->held_records || !s->runs.empty()) { slx_set_error("slx_sort_file_ex: the sorter holds %llu records and %zu runs; it must be empty", (ull)s->held_records, s->runs.size()); return SLX_EINVAL; }
     SLX_HIPCHK(hipSetDevice(s->device));
     slx_bam *rd = nullptr;
     SLX_CHK(slx_bam_open(in_path, s->device, &rd));
     bool created = false;
-    const int rc = sort_file_impl(s, rd, out_path, &created);
+    const int rc = sort_file_impl(s, rd, out_path, &created, spill_prefix);
     std::string msg = rc != SLX_OK ? slx_last_error() : "";
     slx_bam_close(rd);
     (void)hipSetDevice(s->device);
     (void)hipStreamSynchronize(s->st);
     sort_clear(s);
+    sort_drop_runs(s);          // (none are left after a finish; an error on the way leaves none either)
+    if (spill_prefix) { s->spill_on = false; s->spill_prefix.clear(); s->spill_header.clear(); }
     if (rc != SLX_OK) {
         if (created) (void)unlink(out_path);          // no output file is left behind
         slx_set_error("%s", msg.c_str());
     }
     return rc;
+}
+
+extern "C" int slx_sort_file_ex(slx_sort *s, const char *in_path, const char *out_path) { return sort_file_with(s, in_path, out_path, nullptr); }
+
+extern "C" int slx_sort_file_spill(slx_sort *s, const char *in_path, const char *out_path, const char *prefix)
+{
+    if (!s || !in_path || !out_path) { slx_set_error("slx_sort_file_spill: null argument"); return SLX_EINVAL; }
+    return sort_file_with(s, in_path, out_path, prefix ? prefix : out_path);
 }
 
 extern "C" int slx_sort_file(const char *in_path, const char *out_path, int device)
@@ -418,6 +541,9 @@ extern "C" int64_t slx_sort_counter(const slx_sort *s, const char *name)
     if (!strcmp(name, "us_gather")) return (int64_t)s->us_gather;
     if (!strcmp(name, "held_records")) return (int64_t)s->held_records;
     if (!strcmp(name, "held_bytes")) return (int64_t)s->held_bytes;
+    if (!strcmp(name, "runs")) return s->c_runs;
+    if (!strcmp(name, "run_bytes")) return s->c_run_bytes;
+    if (!strcmp(name, "us_merge")) return (int64_t)s->us_merge;
     return -1;
 }
 
@@ -426,6 +552,10 @@ extern "C" int64_t slx_sort_counter(const slx_sort *s, const char *name)
 extern "C" int slx_dup_mark_sorter(slx_dup *d, slx_sort *s)
 {
     if (!d || !s) { slx_set_error("slx_dup_mark_sorter: null argument"); return SLX_EINVAL; }
+    if (!s->runs.empty()) {
+        slx_set_error("slx_dup_mark_sorter: %zu runs were spilled to disk and the marker works among held records only; slx_dup_file is the route for files beyond HBM", s->runs.size());
+        return SLX_EUNSUPPORTED;
+    }
     if (slx_dup_counter(d, "device") != s->device) {
         slx_set_error("slx_dup_mark_sorter: the marker is on device %lld, the sorter on device %d: both must be on one", (long long)slx_dup_counter(d, "device"), s->device);
         return SLX_EINVAL;

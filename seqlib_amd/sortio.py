@@ -11,8 +11,8 @@ from . import _ffi, bamio
 
 # every symbol include/seqlib_amd_sort.h declares (checked by tests/test_sort_host.py against the header text)
 SORT_EXPORTS = ["slx_sort_create", "slx_sort_free", "slx_sort_add_device", "slx_sort_add_host", "slx_sort_finish", "slx_sort_to_host", "slx_sort_file", "slx_sort_file_ex",
-                "slx_sort_header", "slx_sort_set", "slx_sort_counter"]
-COUNTERS = ("records", "bytes", "segments", "slabs", "us_key", "us_sort", "us_gather", "held_records", "held_bytes")
+                "slx_sort_header", "slx_sort_set", "slx_sort_counter", "slx_sort_spill", "slx_sort_file_spill"]
+COUNTERS = ("records", "bytes", "segments", "slabs", "us_key", "us_sort", "us_gather", "held_records", "held_bytes", "runs", "run_bytes", "us_merge")
 
 _READY = False
 
@@ -30,6 +30,8 @@ def lib():
         L.slx_sort_to_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.slx_sort_file.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
         L.slx_sort_file_ex.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
+        L.slx_sort_spill.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int64]
+        L.slx_sort_file_spill.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p]
         L.slx_sort_header.argtypes = [C.c_char_p, C.c_int64, C.c_char_p, C.c_int64]
         L.slx_sort_header.restype = C.c_int64
         L.slx_sort_set.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
@@ -97,22 +99,30 @@ class Sorter:
         _ffi.check(lib().slx_sort_to_host(self.h, buf.ctypes.data, nb, off.ctypes.data, perm.ctypes.data))
         return buf[:nb].tobytes(), off.tolist(), perm[:n].tolist()
 
-    def sort_file(self, in_path, out_path):
-        """file to file with this sorter's device, knobs and counters"""
-        _ffi.check(lib().slx_sort_file_ex(self.h, str(in_path).encode(), str(out_path).encode()))
+    def spill(self, prefix, bam_header=b""):
+        """run files "<prefix>.run%04d.bam" for what passes max_bytes, each with the header block bam_header; None: off"""
+        _ffi.check(lib().slx_sort_spill(self.h, None if prefix is None else str(prefix).encode(), bam_header, len(bam_header)))
+
+    def sort_file(self, in_path, out_path, spill_prefix=None):
+        """file to file with this sorter's device, knobs and counters; spill_prefix: sorted runs go to disk where max_bytes is passed, and are merged"""
+        if spill_prefix is None:
+            _ffi.check(lib().slx_sort_file_ex(self.h, str(in_path).encode(), str(out_path).encode()))
+        else:
+            _ffi.check(lib().slx_sort_file_spill(self.h, str(in_path).encode(), str(out_path).encode(), str(spill_prefix).encode()))
 
 
-def sort_file(in_path, out_path, device=-1, **knobs):
-    """in_path coordinate-sorted into out_path on the GPU.  knobs: max_bytes, slab_bytes, batch_bytes (None or absent: the default).  -> the sorter's counters"""
+def sort_file(in_path, out_path, device=-1, spill_prefix=None, **knobs):
+    """in_path coordinate-sorted into out_path on the GPU.  knobs: max_bytes, slab_bytes, batch_bytes (None or absent: the default).  spill_prefix: where the
+    run files of an input beyond max_bytes go (None: such an input is refused).  -> the sorter's counters"""
     knobs = {k: v for k, v in knobs.items() if v is not None}
-    if not knobs:
+    if not knobs and spill_prefix is None:
         _ffi.check(lib().slx_sort_file(str(in_path).encode(), str(out_path).encode(), device))
         return {}
     s = Sorter(device)
     try:
         for k, v in knobs.items():
             s.set(k, v)
-        s.sort_file(in_path, out_path)
+        s.sort_file(in_path, out_path, spill_prefix)
         return {name: s.counter(name) for name in COUNTERS}
     finally:
         s.close()
