@@ -1,9 +1,10 @@
 // cov_host.h -- what the coverage unit (include/seqlib_amd_cov.h) computes per record and per position, compilable for host and device like dev_rfilter.h and
-// dev_samw.h (`lane` of `nlanes`; the host build runs lane 0 of 1): the array layout, the eligibility test, the intervals a record contributes in the three modes,
+// dev_samw.h (`lane` of `nlanes` lanes that call together, with dev_lanes.h's collectives; the host build runs lane 0 of 1): the array layout, the eligibility test, the intervals a record contributes in the three modes,
 // the decimal formatter and the piece of bedGraph text one position gives.  dev_cov.h's kernels, slx_cov_record_intervals and tests/cpp/cov_host_test.cpp (under
 // ASan + UBSan) all go over these bodies.  The fixed fields and the record's end are the read filter's (dev_rfilter.h: rf_fixed, rf_end).
 #pragma once
 #include <stdint.h>
+#include "dev_lanes.h"
 #include "dev_rfilter.h"
 
 #define COV_SPAN 0
@@ -50,17 +51,6 @@ RF_HD uint32_t cov_depth_put(uint8_t *o, int32_t d)
 }
 
 // ---- one record
-// what a lone lane has in place of the wave's sums
-#if defined(__HIPCC__)
-#define COV_MEMBER __host__ __device__ __forceinline__
-#else
-#define COV_MEMBER inline
-#endif
-struct cov_one {
-    COV_MEMBER uint64_t sum(uint64_t v) const { return v; }
-    COV_MEMBER uint64_t scan(uint64_t v, uint64_t *total) const { *total = v; return 0; }
-};
-
 // the fixed fields and the verdict; F is the filter's feature block (reflen not yet set)
 RF_HD int cov_head(const uint8_t *h, uint64_t span, const cov_par &P, int32_t n_ref, rf_feat *F)
 {
@@ -95,7 +85,7 @@ template <class Sink> RF_HD void cov_span_full(const rf_feat &F, const cov_par &
 }
 
 // The intervals of an eligible record (cov_head said COUNTED or LONG), by `nlanes` lanes that call together: lane `lane` takes ops lane, lane + nlanes, ...;
-// W.scan gives a block its start from the reference lengths of the ops before it, W.sum the reference length.  nlanes == 1 with cov_one is the plain walk.
+// W.scan gives a block its start from the reference lengths of the ops before it, W.sum the reference length.  nlanes == 1 with lanes_one (dev_lanes.h) is the plain walk.
 template <class Wave, class Sink> RF_HD void cov_record(const rf_feat &F0, const cov_par &P, const cov_geo &G, uint32_t lane, uint32_t nlanes, const Wave &W, Sink &S)
 {
     if (P.mode != COV_ALIGNED) {

@@ -8,6 +8,7 @@
 // Every read of a record's variable part is checked against its block_size; the index (dev_bamidx.h) has already placed the whole record inside the stream.
 #pragma once
 #include "dev_bamidx.h"
+#include "dev_lanes.h"
 
 #define BAI_COOP_OPS   64u
 #define BAI_COOP_WINS  64u
@@ -70,8 +71,7 @@ __device__ __forceinline__ uint64_t bai_reflen_wave(const uint8_t *cig, uint32_t
         m &= m - 1;
         const uint8_t *c = (const uint8_t *)__shfl((unsigned long long)cig, src, 64);
         const uint32_t nc = (uint32_t)__shfl((int)n_cig, src, 64);
-        uint64_t part = bai_reflen_part(c, (uint32_t)lane, nc, 64);
-        for (int o = 32; o; o >>= 1) part += __shfl_xor((unsigned long long)part, o, 64);
+        const uint64_t part = wave_sum(bai_reflen_part(c, (uint32_t)lane, nc, 64));
         if (lane == src) len = part;
     }
     return len;

@@ -5,23 +5,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "cov_host.h"
+#include "slx_hip.h"
 
 typedef unsigned long long cov_ull;
 
-// device counters of one add
-enum { COV_C_ERR = 0, COV_C_NLONG, COV_C_COUNTED, COV_C_LDS, COV_C_GLOBAL, COV_C_RUNS, COV_C_N };
-
-struct cov_wave {
-    __device__ __forceinline__ uint64_t sum(uint64_t v) const { for (int o = 32; o; o >>= 1) v += (uint64_t)__shfl_xor((cov_ull)v, o, 64); return v; }
-    __device__ __forceinline__ uint64_t scan(uint64_t v, uint64_t *total) const
-    {
-        const uint32_t lane = threadIdx.x & 63;
-        uint64_t x = v;
-        for (uint32_t o = 1; o < 64; o <<= 1) { const uint64_t y = (uint64_t)__shfl_up((cov_ull)x, o, 64); if (lane >= o) x += y; }
-        *total = (uint64_t)__shfl((cov_ull)x, 63, 64);
-        return x - v;
-    }
-};
+// device counters: an add's (slx_hip.h: SLX_ADD_*), then the bedGraph's runs
+enum { COV_C_RUNS = SLX_ADD_N, COV_C_N };
 
 // where the +-1 of an interval go: entries [A, A + W) of the array stand in LDS, the others in HBM
 struct cov_sink {
@@ -42,15 +31,9 @@ struct cov_sink {
     }
 };
 
-__device__ __forceinline__ void cov_count(cov_ull *cnt, int which, uint32_t v)
-{
-    const uint64_t s = cov_wave().sum(v);
-    if ((threadIdx.x & 63) == 0 && s) atomicAdd(&cnt[which], (cov_ull)s);
-}
-
 // Block b takes records [b * slice, (b + 1) * slice), one lane per record.  lds_window > 0: the block keeps the lds_window entries from the first eligible
 // record's start in LDS (dynamic shared memory, lds_window ints) and flushes the non-zero ones at its end.  Records with more than P.long_cigar ops go to
-// long_list; the lowest index of a record whose fields pass its block_size goes to cnt[COV_C_ERR].
+// long_list; the lowest index of a record whose fields pass its block_size goes to cnt[SLX_ADD_ERR].
 __global__ __launch_bounds__(256) void k_cov_events(const uint8_t *s, uint64_t n_bytes, const cov_ull *rec_off, uint64_t n, cov_par P, cov_geo G, int32_t *arr, uint32_t slice,
                                                     uint32_t lds_window, cov_ull *long_list, cov_ull *cnt)
 {
@@ -85,9 +68,9 @@ __global__ __launch_bounds__(256) void k_cov_events(const uint8_t *s, uint64_t n
         const uint64_t b = rec_off[k], e = rec_off[k + 1];
         rf_feat F;
         const int v = b <= e && e <= n_bytes ? cov_head(s + b, e - b, P, G.n_ref, &F) : COV_R_BAD;
-        if (v == COV_R_BAD) atomicMin(&cnt[COV_C_ERR], (cov_ull)k);
-        else if (v == COV_R_LONG) long_list[atomicAdd(&cnt[COV_C_NLONG], 1ull)] = k;
-        else if (v == COV_R_COUNTED) { cov_record(F, P, G, 0u, 1u, cov_one(), S); ++counted; }
+        if (v == COV_R_BAD) atomicMin(&cnt[SLX_ADD_ERR], (cov_ull)k);
+        else if (v == COV_R_LONG) long_list[atomicAdd(&cnt[SLX_ADD_NLONG], 1ull)] = k;
+        else if (v == COV_R_COUNTED) { cov_record(F, P, G, 0u, 1u, lanes_one(), S); ++counted; }
     }
     if (lds_window) {
         __syncthreads();
@@ -96,9 +79,9 @@ __global__ __launch_bounds__(256) void k_cov_events(const uint8_t *s, uint64_t n
             if (v && S.A + i < (uint64_t)G.total) atomicAdd(&arr[S.A + i], v);
         }
     }
-    cov_count(cnt, COV_C_COUNTED, counted);
-    cov_count(cnt, COV_C_LDS, S.n_lds);
-    cov_count(cnt, COV_C_GLOBAL, S.n_global);
+    wave_count(&cnt[SLX_ADD_COUNTED], counted);
+    wave_count(&cnt[SLX_ADD_LDS], S.n_lds);
+    wave_count(&cnt[SLX_ADD_GLOBAL], S.n_global);
 }
 
 // one wave per record of long_list[0, m): ops 64 at a time, a block's start from the wave's prefix sum; global atomics only
@@ -110,9 +93,9 @@ __global__ __launch_bounds__(256) void k_cov_events_long(const uint8_t *s, const
     rf_feat F;
     (void)cov_head(s + b, rec_off[k + 1] - b, P, G.n_ref, &F);          // (k_cov_events took it: the fields are inside the record)
     cov_sink S = {arr, nullptr, 0, 0, G.beg, G.off, 0, 0};
-    cov_record(F, P, G, threadIdx.x & 63u, 64u, cov_wave(), S);
-    cov_count(cnt, COV_C_COUNTED, (threadIdx.x & 63) == 0 ? 1u : 0u);
-    cov_count(cnt, COV_C_GLOBAL, S.n_global);
+    cov_record(F, P, G, threadIdx.x & 63u, 64u, lanes_group<>(), S);
+    wave_count(&cnt[SLX_ADD_COUNTED], (threadIdx.x & 63) == 0 ? 1u : 0u);
+    wave_count(&cnt[SLX_ADD_GLOBAL], S.n_global);
 }
 
 // ---- settle (inclusive scan in place, hipCUB, chunk by chunk) and its inverse
@@ -143,7 +126,7 @@ __global__ __launch_bounds__(256) void k_cov_max(const int32_t *arr, uint64_t g0
 {
     int32_t m = INT32_MIN;
     for (uint64_t g = g0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < g1; g += (uint64_t)gridDim.x * blockDim.x) { const int32_t v = arr[g]; m = v > m ? v : m; }
-    for (int o = 32; o; o >>= 1) { const int32_t u = __shfl_xor(m, o, 64); m = u > m ? u : m; }
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0 && m != INT32_MIN) atomicMax(out, m);
 }
 
@@ -166,7 +149,7 @@ __global__ __launch_bounds__(256) void k_cov_regions(const int32_t *arr, const c
             if (g >= it.g0 && g < it.g1) { s += e[i]; c += e[i] >= min_depth; }
         }
     }
-    s = (int64_t)cov_wave().sum((uint64_t)s); c = cov_wave().sum(c);
+    s = (int64_t)wave_sum((uint64_t)s); c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) { if (s) atomicAdd(&sum[it.r], (cov_ull)s); if (c) atomicAdd(&n_at_least[it.r], (cov_ull)c); }
 }
 
@@ -177,7 +160,7 @@ __global__ __launch_bounds__(256) void k_cov_bg_len(const int32_t *arr, cov_geo 
     uint32_t head = 0;
     if (i < m) len[i] = cov_bg_piece(arr, G, N, c0 + i, include_zero, (uint8_t *)nullptr, &head);
     else if (i == m) len[i] = 0;
-    cov_count(cnt, COV_C_RUNS, head);
+    wave_count(&cnt[COV_C_RUNS], head);
 }
 __global__ __launch_bounds__(256) void k_cov_bg_fill(const int32_t *arr, cov_geo G, cov_names N, uint64_t c0, uint64_t m, int include_zero, const cov_ull *at, uint8_t *text)
 {

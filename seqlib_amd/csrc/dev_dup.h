@@ -18,6 +18,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "dev_lanes.h"
 #include "dev_wave.h"
 #include "dup_host.h"
 
@@ -31,19 +32,6 @@ struct dp_cols {
     dp_ull *hi, *lo; uint32_t *score; uint8_t *cls;
     uint32_t *pord; dp_ull *phash, *pname; uint32_t *plen;
 };
-
-__device__ __forceinline__ uint32_t dp_wave_sum32(uint32_t v) { for (int o = 32; o; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64); return v; }
-__device__ __forceinline__ void dp_count(uint32_t *ctr, uint32_t v)
-{
-    const uint32_t s = dp_wave_sum32(v);
-    if ((threadIdx.x & 63) == 0 && s) atomicAdd(ctr, s);
-}
-__device__ __forceinline__ void dp_report(bool broken, uint64_t i, dp_state *st)
-{
-    dp_ull bad = broken ? i : ED_NONE;
-    for (int o = 32; o; o >>= 1) { const dp_ull b2 = __shfl_xor(bad, o, 64); bad = b2 < bad ? b2 : bad; }
-    if ((threadIdx.x & 63) == 0 && bad != ED_NONE) atomicMin(&st->bad, bad);
-}
 
 // ------------------------------------------------------------------ add
 __global__ __launch_bounds__(256) void k_dup_sig(dp_libtab T, dp_args A, uint32_t wave_len, dp_sig *S, uint32_t *longlist, dp_state *st)
@@ -64,7 +52,7 @@ __global__ __launch_bounds__(256) void k_dup_sig(dp_libtab T, dp_args A, uint32_
         S[i] = s;
     }
     if (is_long) longlist[wave_fetch_inc(&st->n_long)] = (uint32_t)i;
-    dp_report(broken, i, st);
+    wave_report_min(&st->bad, broken, i);
 }
 
 // (only records whose span and head k_dup_sig has passed are listed)
@@ -90,7 +78,7 @@ __global__ __launch_bounds__(256) void k_dup_sizes(const dp_sig *S, uint64_t n, 
         pcnt[i] = c == DP_PAIRED ? 1 : 0;
         nlen[i] = c == DP_PAIRED ? S[i].name_len : 0;
     }
-    dp_count(&st->n_ignored, c == DP_IGNORED);
+    wave_count(&st->n_ignored, c == DP_IGNORED);
 }
 
 __global__ __launch_bounds__(256) void k_dup_commit(dp_args A, const dp_sig *S, const dp_ull *poff, const dp_ull *noff, uint64_t base, uint64_t m_old, uint8_t *seg, dp_cols C)
@@ -179,9 +167,9 @@ __global__ __launch_bounds__(256) void k_dup_join(dp_cols C, const dp_ull *key, 
         mate[me] = res;
         orphan = res == DP_NO_MATE;
     }
-    dp_count(&st->too_long, too_long);
-    dp_count(&st->mixed, mixed);
-    dp_count(&st->n_orphans, orphan);
+    wave_count(&st->too_long, too_long);
+    wave_count(&st->mixed, mixed);
+    wave_count(&st->n_orphans, orphan);
 }
 
 // a pair is entered by its member of the lower ordinal (paired indices rise with the ordinal)
@@ -223,7 +211,7 @@ __global__ __launch_bounds__(256) void k_dup_pair_verdict(const uint32_t *perm, 
         ver[E.oa[e]] = 1; ver[E.ob[e]] = 1;
         dup = 1;
     }
-    dp_count(&st->dup_pairs, dup);
+    wave_count(&st->dup_pairs, dup);
 }
 
 // a fragment that is not its group's head is a duplicate: the head is a paired record where the group holds one, or else the best fragment
@@ -235,7 +223,7 @@ __global__ __launch_bounds__(256) void k_dup_frag_verdict(const uint32_t *perm, 
         const uint32_t r = perm[i];
         if ((cls[r] & DP_CLASS) == DP_FRAGMENT) { ver[r] = 1; dup = 1; }
     }
-    dp_count(&st->dup_frags, dup);
+    wave_count(&st->dup_frags, dup);
 }
 
 // ------------------------------------------------------------------ apply
@@ -260,7 +248,7 @@ __global__ __launch_bounds__(256) void k_dup_apply(uint8_t *s, uint64_t n_bytes,
         }
     }
     if (!commit) {
-        dp_report(broken, i, st);
-        dp_count(&st->bad_ord, bad_ord);
+        wave_report_min(&st->bad, broken, i);
+        wave_count(&st->bad_ord, bad_ord);
     }
 }

@@ -25,6 +25,7 @@
 #pragma once
 #include <stdint.h>
 #include <string.h>
+#include "dev_lanes.h"
 
 #if defined(__HIPCC__)
 #define ED_FN __host__ __device__ __forceinline__
@@ -237,10 +238,8 @@ template <class PU16> ED_FN uint32_t ed_find(PU16 p, uint32_t cnt, uint32_t i)
 ED_FN uint32_t ed_excl_scan(uint32_t v, int lane, uint32_t *total)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-    uint32_t s = v;
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t t = (uint32_t)__shfl_up((int)s, d, 64); if (lane >= d) s += t; }
-    *total = (uint32_t)__shfl((int)s, 63, 64);
-    return s - v;
+    (void)lane;
+    return wave_scan_excl(v, total);
 #else
     (void)lane;
     *total = v;

@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "dev_lanes.h"
 #include "grc_host.h"
 
 typedef unsigned long long grc_ull;
@@ -152,9 +153,7 @@ __global__ __launch_bounds__(256) void k_grc_records_long(const uint8_t *s, cons
     rf_part P;
     memset(&P, 0, sizeof P);
     rf_cigar_part(F.cig, threadIdx.x & 63u, F.n_cig, 64, &P);
-    grc_ull r = P.reflen;
-    for (int o = 32; o; o >>= 1) r += (grc_ull)__shfl_xor(r, o, 64);
-    F.reflen = r;
+    F.reflen = wave_sum((grc_ull)P.reflen);
     if ((threadIdx.x & 63u) == 0) { const grc_iv v = grc_record_iv(F); q[k] = v; ks[k] = grc_key2(v.chr, v.pos1); ke[k] = grc_key2(v.chr, v.pos2); }
 }
 

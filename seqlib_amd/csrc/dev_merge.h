@@ -24,6 +24,7 @@
 // the counts of disjoint sets of eligible records); LDS indices are below k + 1 <= MG_MAX_IN + 1.
 #pragma once
 #include <stdint.h>
+#include "dev_lanes.h"
 #include "dev_recsort.h"
 
 #define MG_MAX_IN 64            // inputs of one merger
@@ -56,23 +57,23 @@ RS_FN uint32_t mg_count(const bool *p, int nlanes)
 }
 RS_FN mg_ull mg_min(const mg_ull *v, int nlanes)
 {
-    mg_ull m = v[0];
 #if defined(__HIPCC__)
-    for (int o = 32; o; o >>= 1) { const mg_ull x = __shfl_xor(m, o, 64); m = x < m ? x : m; }
+    return wave_min(v[0]);
 #else
+    mg_ull m = v[0];
     for (int l = 1; l < nlanes; ++l) m = v[l] < m ? v[l] : m;
-#endif
     return m;
+#endif
 }
 RS_FN mg_ull mg_max(const mg_ull *v, int nlanes)
 {
-    mg_ull m = v[0];
 #if defined(__HIPCC__)
-    for (int o = 32; o; o >>= 1) { const mg_ull x = __shfl_xor(m, o, 64); m = x > m ? x : m; }
+    return wave_max(v[0]);
 #else
+    mg_ull m = v[0];
     for (int l = 1; l < nlanes; ++l) m = v[l] > m ? v[l] : m;
-#endif
     return m;
+#endif
 }
 
 // ---- key and order test

@@ -4,26 +4,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "pile_host.h"
+#include "slx_hip.h"
 #include "seqlib_amd_pile.h"
 
 typedef unsigned long long pile_ull;
 
-// device counters of one add
-enum { PILE_C_ERR = 0, PILE_C_NLONG, PILE_C_COUNTED, PILE_C_LDS, PILE_C_GLOBAL, PILE_C_N };
-
-// the prefix sum and the broadcast of the G lanes (16, 32 or 64, aligned in the wave) that walk one record
-template <int G> struct pile_group {
-    __device__ __forceinline__ uint64_t scan(uint64_t v, uint64_t *total) const
-    {
-        const uint32_t lane = threadIdx.x & (G - 1);
-        uint64_t x = v;
-#pragma unroll
-        for (uint32_t o = 1; o < G; o <<= 1) { const uint64_t y = (uint64_t)__shfl_up((pile_ull)x, o, G); if (lane >= o) x += y; }
-        *total = (uint64_t)__shfl((pile_ull)x, G - 1, G);
-        return x - v;
-    }
-    __device__ __forceinline__ uint64_t bcast(uint64_t v, uint32_t j) const { return (uint64_t)__shfl((pile_ull)v, (int)j, G); }
-};
+// (the device counters of one add are slx_hip.h's SLX_ADD_*; the G lanes -- 16, 32 or 64, aligned in the wave -- that walk one record are a lanes_group<G>)
 
 // where an event goes: positions [A, A + W) of every plane stand in LDS (plane-major, lstride entries a plane: a multiple of 32, so the bank of an entry is
 // its position's whatever its plane, and the consecutive positions of a group's lanes fall on consecutive banks), the others in HBM
@@ -40,16 +26,9 @@ struct pile_sink {
     }
 };
 
-__device__ __forceinline__ void pile_count(pile_ull *cnt, int which, uint32_t v)
-{
-    uint64_t s = v;
-    for (int o = 32; o; o >>= 1) s += (uint64_t)__shfl_xor((pile_ull)s, o, 64);
-    if ((threadIdx.x & 63) == 0 && s) atomicAdd(&cnt[which], (pile_ull)s);
-}
-
 // Block b (256 threads) takes records [b * slice, (b + 1) * slice), a group of G lanes per record.  lds_window > 0: the block keeps lds_window positions of all
 // 15 planes from the first eligible record's start in LDS (dynamic shared memory, 15 * lstride ints) and flushes the non-zero entries at its end.  Long
-// records go to long_list; the lowest index of a record whose fields pass its block_size goes to cnt[PILE_C_ERR].
+// records go to long_list; the lowest index of a record whose fields pass its block_size goes to cnt[SLX_ADD_ERR].
 template <int G> __global__ __launch_bounds__(256) void k_pile_events(const uint8_t *s, uint64_t n_bytes, const pile_ull *rec_off, uint64_t n, pile_par P, int32_t *arr, uint64_t stride,
                                                                       uint32_t slice, uint32_t lds_window, uint32_t lstride, pile_ull *long_list, pile_ull *cnt)
 {
@@ -85,9 +64,9 @@ template <int G> __global__ __launch_bounds__(256) void k_pile_events(const uint
         const uint64_t b = rec_off[k], e = rec_off[k + 1];
         rf_feat F;
         const int v = b <= e && e <= n_bytes ? pile_head(s + b, e - b, P, &F) : PILE_R_BAD;
-        if (v == PILE_R_BAD) { if (lane == 0) atomicMin(&cnt[PILE_C_ERR], (pile_ull)k); }
-        else if (v == PILE_R_LONG) { if (lane == 0) long_list[atomicAdd(&cnt[PILE_C_NLONG], 1ull)] = k; }
-        else if (v == PILE_R_COUNTED) { pile_record(F, P, lane, (uint32_t)G, pile_group<G>(), S); counted += lane == 0; }
+        if (v == PILE_R_BAD) { if (lane == 0) atomicMin(&cnt[SLX_ADD_ERR], (pile_ull)k); }
+        else if (v == PILE_R_LONG) { if (lane == 0) long_list[atomicAdd(&cnt[SLX_ADD_NLONG], 1ull)] = k; }
+        else if (v == PILE_R_COUNTED) { pile_record(F, P, lane, (uint32_t)G, lanes_group<G>(), S); counted += lane == 0; }
     }
     if (lds_window) {
         __syncthreads();
@@ -97,9 +76,9 @@ template <int G> __global__ __launch_bounds__(256) void k_pile_events(const uint
                 if (v && S.A + i < P.end) atomicAdd(&arr[p * stride + (uint64_t)(S.A + i - P.beg)], v);
             }
     }
-    pile_count(cnt, PILE_C_COUNTED, counted);
-    pile_count(cnt, PILE_C_LDS, S.n_lds);
-    pile_count(cnt, PILE_C_GLOBAL, S.n_global);
+    wave_count(&cnt[SLX_ADD_COUNTED], counted);
+    wave_count(&cnt[SLX_ADD_LDS], S.n_lds);
+    wave_count(&cnt[SLX_ADD_GLOBAL], S.n_global);
 }
 
 // one wave per record of long_list[0, m): ops 64 at a time, the bases of a block over the 64 lanes; global atomics only
@@ -111,9 +90,9 @@ __global__ __launch_bounds__(256) void k_pile_events_long(const uint8_t *s, cons
     rf_feat F;
     (void)pile_head(s + b, rec_off[k + 1] - b, P, &F);          // (k_pile_events took it: the fields are inside the record)
     pile_sink S = {arr, nullptr, stride, P.beg, 0, 0u, 0u, 0u, 0u};
-    pile_record(F, P, threadIdx.x & 63u, 64u, pile_group<64>(), S);
-    pile_count(cnt, PILE_C_COUNTED, (threadIdx.x & 63) == 0 ? 1u : 0u);
-    pile_count(cnt, PILE_C_GLOBAL, S.n_global);
+    pile_record(F, P, threadIdx.x & 63u, 64u, lanes_group<64>(), S);
+    wave_count(&cnt[SLX_ADD_COUNTED], (threadIdx.x & 63) == 0 ? 1u : 0u);
+    wave_count(&cnt[SLX_ADD_GLOBAL], S.n_global);
 }
 
 // ---- candidate sites.  A lane takes the four positions 4q .. 4q + 3 of the window: one 16-byte load per plane (the planes start on 16-byte boundaries and

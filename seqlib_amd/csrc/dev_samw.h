@@ -4,19 +4,18 @@
 //   samw_line   `lane` of `nl` lanes call it with the same arguments.  out == nullptr: every refusal rule, the line's length and the field table F (text offsets of
 //               CIGAR, SEQ, QUAL and the optional fields).  out != nullptr: the line, from F: the short fields by lane 0, QNAME, Z / H strings, CIGAR ops and B elements
 //               over the lanes (their places from the lanes' scan, nl at a time).  WV carries what the lanes share: the kernel plugs in the wave's cross-lane
-//               operations (all 64 lanes call together), the host and a single lane of the size kernel the identity (lane 0 of 1).
+//               operations (dev_lanes.h: lanes_group<64>, all 64 lanes call together), the host and a single lane of the size kernel lanes_one (lane 0 of 1).
 //   samw_bulk   SEQ (two bases per packed byte) and QUAL + 33 of a sized record, over any number of lanes: a long record takes several waves for it.
 // Verdicts: SAMW_FAST the line is decided here; SAMW_SLOW the record carries an f, d or B:f field and FL cannot print floating-point text (the GPU); SAMW_ERROR with
 // *err; SAMW_DEFER (sizing only) the record has more than `defer` CIGAR ops or B elements: the caller sizes it again with more lanes.
 // Nothing outside r[0, n) is read, and out is written only for a record that an out == nullptr call has taken.
 #pragma once
 #include <stdint.h>
+#include "dev_lanes.h"
 #if defined(__HIPCC__)
 #define SAMW_FN __host__ __device__ __forceinline__
-#define SAMW_MEMBER __host__ __device__ __forceinline__
 #else
 #define SAMW_FN static inline
-#define SAMW_MEMBER
 #endif
 
 enum { SAMW_FAST = 0, SAMW_SLOW = 1, SAMW_ERROR = 2, SAMW_DEFER = 3 };
@@ -37,17 +36,11 @@ struct samw_fld {
     uint32_t qn, l_seq;                            // QNAME's printed length; l_seq
 };
 
-// what a single lane plugs in: lane 0 of 1
-struct samw_one {
-    SAMW_MEMBER uint64_t sum(uint64_t v) const { return v; }
-    SAMW_MEMBER uint64_t min(uint64_t v) const { return v; }
-    SAMW_MEMBER uint32_t scan(uint32_t v, uint32_t *total) const { *total = v; return 0; }          // exclusive
-};
 // what the GPU plugs in: no floating-point text is printed there
 struct samw_no_float {
     static constexpr bool has = false;
-    SAMW_MEMBER int f32(const uint8_t *, char *) const { return 0; }
-    SAMW_MEMBER int f64(const uint8_t *, char *) const { return 0; }
+    LANES_MEMBER int f32(const uint8_t *, char *) const { return 0; }
+    LANES_MEMBER int f64(const uint8_t *, char *) const { return 0; }
 };
 
 SAMW_FN uint32_t samw_le16(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }

@@ -203,19 +203,13 @@ template <class Sink> RF_HD void st_adds(const st_lay *L, const st_rec *R, bool 
 // ---------------------------------------------------------------- the kernels
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#include "dev_lanes.h"
 // (no work is TAKEN from a device counter here -- blocks own windows, waves stride the long list -- so dev_wave.h is not needed: the appends to the long and the
 // miss list use the counter's old value in the lane that added, and nowhere else)
 
 typedef unsigned long long st_ull;
 // device counters of one add: the lowest record with broken fields or aux, the lowest with too long a key, list lengths, and what was done
 enum { ST_K_ERR_IO = 0, ST_K_ERR_KEY, ST_K_NLONG, ST_K_NMISS, ST_K_COUNTED, ST_K_LDS, ST_K_GLOBAL, ST_K_N };
-
-__device__ __forceinline__ st_ull st_wave_sum(st_ull v) { for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64); return v; }
-__device__ __forceinline__ void st_count(st_ull *cnt, int which, uint32_t v)
-{
-    const st_ull s = st_wave_sum(v);
-    if ((threadIdx.x & 63) == 0 && s) atomicAdd(&cnt[which], s);
-}
 
 // The adds of a wave's 64 records.  Where every lane that adds goes to the same entry of the same group (one read group, MAPQ 60, NM 0: the common case) one
 // lane adds the wave's total; otherwise every lane adds its own.  Groups below lds_groups have their row in LDS (uint32: a block's records are bounded by its
@@ -236,7 +230,7 @@ struct st_sink {
         const uint32_t lg = (uint32_t)__builtin_amdgcn_readlane((int)g, leader), le = (uint32_t)__builtin_amdgcn_readlane((int)entry, leader);
         if (__ballot(on && (g != lg || entry != le)) == 0) {
             const bool ones = __ballot(on && amount != 1u) == 0;          // (the same in every lane)
-            const uint32_t total = ones ? (uint32_t)__popcll(m) : (uint32_t)st_wave_sum(on ? amount : 0u);
+            const uint32_t total = ones ? (uint32_t)__popcll(m) : (uint32_t)wave_sum((st_ull)(on ? amount : 0u));
             if ((int)(threadIdx.x & 63) == leader) put(entry, total);
         } else if (on) put(entry, amount);
     }
@@ -330,9 +324,9 @@ __global__ __launch_bounds__(256) void k_st_add(const uint8_t *s, uint64_t n_byt
         const uint32_t v = hist[i];
         if (v) { const uint32_t g = i / L.row; atomicAdd(&mine[(uint64_t)g * ST_REPLICAS * L.row + (i - g * L.row)], (st_ull)v); }
     }
-    st_count(cnt, ST_K_COUNTED, counted);
-    st_count(cnt, ST_K_LDS, S.n_lds);
-    st_count(cnt, ST_K_GLOBAL, S.n_glob);
+    wave_count(&cnt[ST_K_COUNTED], counted);
+    wave_count(&cnt[ST_K_LDS], S.n_lds);
+    wave_count(&cnt[ST_K_GLOBAL], S.n_glob);
 }
 
 // one wave per record of long_list[0, m): the lanes share the CIGAR ops and the QUAL words out of HBM, lane 0 finishes and adds to HBM
@@ -349,7 +343,7 @@ __global__ __launch_bounds__(256) void k_st_add_long(const uint8_t *s, const st_
     if (!st_eligible(&P, &F)) return;
     st_part Q;
     st_part_of(&F, lane, 64, &Q);
-    Q.qsum = st_wave_sum(Q.qsum); Q.clip = (uint32_t)st_wave_sum(Q.clip);
+    Q.qsum = wave_sum((st_ull)Q.qsum); Q.clip = (uint32_t)wave_sum((st_ull)Q.clip);
     if (lane != 0) return;
     st_rec R;
     memset(&R, 0, sizeof R);

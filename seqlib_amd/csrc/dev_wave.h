@@ -1,4 +1,5 @@
-// dev_wave.h -- how a wave (or a block) takes work from a device-wide counter, in one place.
+// dev_wave.h -- how a wave (or a block) takes work from a device-wide counter, in one place (what a wave's lanes compute together -- sums, minima, prefix
+// sums -- is dev_lanes.h's).
 //
 // The idiom: ONE lane does the atomicAdd for the wave and the old value comes back to every lane through readfirstlane.
 // The hazard: written as `if (lane == 0) slot = atomicAdd(queue, 1u); slot = readfirstlane(slot);` at the head of a persistent loop,

@@ -11,6 +11,7 @@
 #include <stdint.h>
 #include <string.h>
 #include "dev_edit.h"
+#include "dev_lanes.h"
 
 enum { DP_IGNORED = 0, DP_FRAGMENT = 1, DP_PAIRED = 2, DP_CLASS = 3, DP_FIRST = 4, DP_SECOND = 8 };          // dp_sig.cls: the class, and 0x40 / 0x80 of a paired record
 #define DP_WAVE_LEN 512u          // the default of "wave_len"
@@ -45,7 +46,7 @@ struct dp_sig {
 template <bool WAVE> ED_FN uint64_t dp_wsum(uint64_t v)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-    if (WAVE) for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
+    if (WAVE) v = wave_sum(v);
 #endif
     return v;
 }

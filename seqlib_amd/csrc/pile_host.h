@@ -1,11 +1,12 @@
 // pile_host.h -- what the pileup unit (include/seqlib_amd_pile.h) computes per record and per position, compilable for host and device like cov_host.h
-// (`lane` of `nlanes` lanes call together): the eligibility test, the walk of one record that gives its (plane, position) events, and the candidate-site rule
+// (`lane` of `nlanes` lanes call together; W is dev_lanes.h's lanes_one or lanes_group): the eligibility test, the walk of one record that gives its (plane, position) events, and the candidate-site rule
 // of one position.  dev_pile.h's kernels (a group of lanes per record, a wave per long record), slx_pile_record_events and tests/cpp/pile_host_test.cpp (under
 // ASan + UBSan, with 1, 16 and 64 simulated lanes) all go over these bodies.  The fixed fields are the read filter's (dev_rfilter.h: rf_fixed).
 // Memory safety: rf_fixed has placed the name, the CIGAR, the packed sequence and the l_seq quality bytes inside the record before pile_record reads any of
 // them; the walk reads the sequence and the qualities at y < l_seq only.  The sink is called for positions inside [P.beg, P.end) only.
 #pragma once
 #include <stdint.h>
+#include "dev_lanes.h"
 #include "dev_rfilter.h"
 
 #define PILE_PLANES 15
@@ -26,17 +27,6 @@ struct pile_par { int64_t beg, end; int32_t tid, min_mapq, min_baseq; uint32_t e
 // planes of `stride` entries each, one behind the other
 RF_HD uint64_t pile_stride(int64_t L) { return ((uint64_t)L + 3u) & ~3ull; }
 
-#if defined(__HIPCC__)
-#define PILE_MEMBER __host__ __device__ __forceinline__
-#else
-#define PILE_MEMBER inline
-#endif
-// what a lone lane has in place of the group's prefix sum and broadcast
-struct pile_one {
-    PILE_MEMBER uint64_t scan(uint64_t v, uint64_t *total) const { *total = v; return 0; }
-    PILE_MEMBER uint64_t bcast(uint64_t v, uint32_t) const { return v; }
-};
-
 // the fixed fields and the verdict; F is the filter's feature block
 RF_HD int pile_head(const uint8_t *h, uint64_t span, const pile_par &P, rf_feat *F)
 {
@@ -52,7 +42,7 @@ RF_HD uint32_t pile_base(uint32_t code) { return code == 1u ? 0u : code == 2u ? 
 // a time: lane `lane` reads op base + lane, W.scan gives every op its start on the reference and in the read from the lengths of the ops before it, then the
 // ops of the chunk are walked one after the other, W.bcast handing an op and its starts to all lanes, and lane `lane` takes bases lane, lane + nlanes, ... of
 // an M or D block: neighbouring lanes read neighbouring bases and add to neighbouring positions.  The trip counts of every loop that holds a scan or a bcast
-// are the same for all lanes of the group.  nlanes == 1 with pile_one is the plain walk.  S(plane, x) is called for P.beg <= x < P.end only.
+// are the same for all lanes of the group.  nlanes == 1 with lanes_one is the plain walk.  S(plane, x) is called for P.beg <= x < P.end only.
 template <class Wave, class Sink> RF_HD void pile_record(const rf_feat &F, const pile_par &P, uint32_t lane, uint32_t nlanes, const Wave &W, Sink &S)
 {
     const uint64_t ls = (uint64_t)F.l_seq;

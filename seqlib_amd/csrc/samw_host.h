@@ -52,11 +52,11 @@ static inline int samwh_format(const uint8_t *rec, uint64_t n, const samw_refs &
     memset(&F, 0, sizeof F);
     uint64_t size = 0, size2 = 0;
     const samwh_float fl;
-    const int v = samw_line(rec, n, R, &F, (uint8_t *)nullptr, &size, err, 0u, 1u, samw_one(), fl, SAMW_NO_DEFER);
+    const int v = samw_line(rec, n, R, &F, (uint8_t *)nullptr, &size, err, 0u, 1u, lanes_one(), fl, SAMW_NO_DEFER);
     if (v != SAMW_FAST) return v;
     const size_t at = text.size();
     text.resize(at + size);
-    (void)samw_line(rec, n, R, &F, text.data() + at, &size2, err, 0u, 1u, samw_one(), fl, SAMW_NO_DEFER);
+    (void)samw_line(rec, n, R, &F, text.data() + at, &size2, err, 0u, 1u, lanes_one(), fl, SAMW_NO_DEFER);
     samw_bulk(rec, F, text.data() + at, 0, 1);
     return SAMW_FAST;
 }

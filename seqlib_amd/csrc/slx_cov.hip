@@ -34,8 +34,8 @@ typedef SlxPinBuf<SlxMargin<4, 256>> CHBuf;
 
 static const char COV_NO_DEVICE[] = "no HIP device: coverage is computed on MI355X only (no CPU fallback)";
 
-struct slx_cov : SlxGpu<> {
-    slx_cov() : SlxGpu(COV_NO_DEVICE) {}
+struct slx_cov : SlxTwoPass {
+    slx_cov() : SlxTwoPass(COV_NO_DEVICE) {}
     std::vector<int64_t> len, beg, end, off;
     std::vector<std::string> names;
     uint64_t total = 0;
@@ -44,11 +44,11 @@ struct slx_cov : SlxGpu<> {
     uint64_t scan_chunk = 1ull << 30;
     bool settled = false;          // the array holds depths, not differences
     SlxDevBuf<SlxExact> d_arr{*this};
-    CDBuf d_geo{*this}, d_names{*this}, d_noff{*this}, d_in{*this}, d_off{*this}, d_long{*this}, d_cnt{*this}, d_tmp{*this}, d_bound{*this}, d_items{*this}, d_sums{*this}, d_len{*this},
+    CDBuf d_geo{*this}, d_names{*this}, d_noff{*this}, d_in{*this}, d_off{*this}, d_tmp{*this}, d_bound{*this}, d_items{*this}, d_sums{*this}, d_len{*this},
           d_at{*this}, d_text{*this}, d_max{*this};
-    CHBuf h_cnt{*this}, h_items{*this}, h_sums{*this}, h_text[2] = {*this, *this};
-    int64_t c_seen = 0, c_counted = 0, c_long = 0, c_lds = 0, c_global = 0, c_runs = 0;
-    double us_add = 0, us_settle = 0;
+    CHBuf h_items{*this}, h_sums{*this}, h_text[2] = {*this, *this};
+    int64_t c_runs = 0;
+    double us_settle = 0;
     cov_geo geo() const { const int64_t *g = d_geo.as<int64_t>(); const size_t n = len.size(); return cov_geo{g, g + n, g + 2 * n, (int32_t)n, 0, (int64_t)total}; }
     int32_t *arr() const { return d_arr.as<int32_t>(); }
 };
@@ -163,35 +163,12 @@ static int cov_settle(slx_cov *c)
 static int cov_add(slx_cov *c, const uint8_t *d_s, uint64_t n_bytes, const ull *d_off, uint64_t n)
 {
     if (n == 0) return SLX_OK;
-    if (n >= 0x7fffffffull) { slx_set_error("coverage: 2^31 records or more in one batch"); return SLX_EUNSUPPORTED; }
-    SLX_CHK(cov_unsettle(c));
+    if (n < 0x7fffffffull) SLX_CHK(cov_unsettle(c));          // (a batch that is refused for its size leaves the array as it stands)
     hipStream_t st = c->st;
-    SLX_CHK(c->d_long.ensure(8 * n));
-    ull *hc = c->h_cnt.as<ull>(), *dc = c->d_cnt.as<ull>();
-    memset(hc, 0, 8 * COV_C_N);
-    hc[COV_C_ERR] = ~0ull;
-    SLX_HIPCHK(hipMemcpyAsync(dc, hc, 8 * COV_C_N, hipMemcpyHostToDevice, st));
-    SLX_HIPCHK(hipEventRecord(c->ev[0], st));
-    const uint64_t blocks = (n + c->slice - 1) / c->slice;
-    k_cov_events<<<(unsigned)blocks, 256, 4 * (size_t)c->lds_window, st>>>(d_s, n_bytes, d_off, n, c->par, c->geo(), c->arr(), c->slice, c->lds_window, c->d_long.as<ull>(), dc);
-    SLX_HIPCHK(hipGetLastError());
-    SLX_HIPCHK(hipMemcpyAsync(hc, dc, 8 * COV_C_N, hipMemcpyDeviceToHost, st));
-    SLX_HIPCHK(slx_wait_stream(st));
-    if (hc[COV_C_ERR] != ~0ull) {
-        slx_set_error("coverage: record %llu of the batch: its fields pass its block_size, or its extent is not block_size + 4 inside the stream", hc[COV_C_ERR]);
-        return SLX_EIO;
-    }
-    const uint64_t n_long = hc[COV_C_NLONG];
-    if (n_long) {
-        k_cov_events_long<<<(unsigned)((n_long + 3) / 4), 256, 0, st>>>(d_s, d_off, c->d_long.as<ull>(), n_long, c->par, c->geo(), c->arr(), dc);
-        SLX_HIPCHK(hipGetLastError());
-        SLX_HIPCHK(hipMemcpyAsync(hc, dc, 8 * COV_C_N, hipMemcpyDeviceToHost, st));
-    }
-    SLX_HIPCHK(hipEventRecord(c->ev[1], st));
-    SLX_HIPCHK(slx_wait_stream(st));
-    c->us_add += slx_ev_us(c->ev[0], c->ev[1]);
-    c->c_seen += (int64_t)n; c->c_counted += (int64_t)hc[COV_C_COUNTED]; c->c_long += (int64_t)n_long; c->c_lds += (int64_t)hc[COV_C_LDS]; c->c_global += (int64_t)hc[COV_C_GLOBAL];
-    return SLX_OK;
+    ull *dc = c->d_cnt.as<ull>();
+    return slx_two_pass_add(*c, "coverage", n, COV_C_N,
+        [&]() { k_cov_events<<<(unsigned)((n + c->slice - 1) / c->slice), 256, 4 * (size_t)c->lds_window, st>>>(d_s, n_bytes, d_off, n, c->par, c->geo(), c->arr(), c->slice, c->lds_window, c->d_long.as<ull>(), dc); },
+        [&](uint64_t n_long) { k_cov_events_long<<<(unsigned)((n_long + 3) / 4), 256, 0, st>>>(d_s, d_off, c->d_long.as<ull>(), n_long, c->par, c->geo(), c->arr(), dc); });
 }
 
 extern "C" int slx_cov_add_device(slx_cov *c, const void *d_stream, int64_t n_bytes, const void *d_rec_off, int64_t n_records)
@@ -230,7 +207,7 @@ extern "C" int slx_cov_record_intervals(const uint8_t *rec, int64_t n, int mode,
     const cov_geo G = {&beg, &end, &off, 1, 0, 0};
     F.tid = 0;
     CovHostSink S = {out_lo, out_hi, cap, 0};
-    cov_record(F, P, G, 0u, 1u, cov_one(), S);
+    cov_record(F, P, G, 0u, 1u, lanes_one(), S);
     *n_out = S.n;
     if (S.n > cap) { slx_set_error("slx_cov_record_intervals: %lld intervals, out holds %lld", (long long)S.n, (long long)cap); return SLX_EINVAL; }
     return SLX_OK;

@@ -14,6 +14,7 @@
 #include "slx_internal.h"
 #include "slx_hip.h"
 #include "seqlib_amd_edit.h"
+#include "dev_lanes.h"
 #include "dev_wave.h"
 #include "dev_edit.h"
 #include "edit_host.h"
@@ -31,16 +32,9 @@ struct ed_args { const uint8_t *s; uint64_t n_bytes; const uint64_t *off; uint64
 // ------------------------------------------------------------------ kernels
 __device__ __forceinline__ void ed_report(uint32_t rc, uint64_t i, ed_state *st)
 {
-    ull bad = rc == ED_E_RECORD ? i : ED_NONE, col = rc == ED_E_COLUMN ? i : ED_NONE, big = rc == ED_E_SIZE ? i : ED_NONE;
-    for (int o = 32; o; o >>= 1) {
-        const ull b2 = __shfl_xor(bad, o, 64), c2 = __shfl_xor(col, o, 64), g2 = __shfl_xor(big, o, 64);
-        bad = b2 < bad ? b2 : bad; col = c2 < col ? c2 : col; big = g2 < big ? g2 : big;
-    }
-    if ((threadIdx.x & 63) == 0) {
-        if (bad != ED_NONE) atomicMin(&st->bad, bad);
-        if (col != ED_NONE) atomicMin(&st->col, col);
-        if (big != ED_NONE) atomicMin(&st->big, big);
-    }
+    wave_report_min(&st->bad, rc == ED_E_RECORD, i);
+    wave_report_min(&st->col, rc == ED_E_COLUMN, i);
+    wave_report_min(&st->big, rc == ED_E_SIZE, i);
 }
 
 __global__ __launch_bounds__(256) void k_edit_size(ed_plan P, ed_args A, ull *sz, ed_desc *desc, uint32_t *longlist, ed_state *st)

@@ -30,6 +30,7 @@
 #include "seqlib_amd_bam.h"
 #include "seqlib_amd_fastq.h"
 #include "dev_inflate.h"
+#include "dev_lanes.h"
 #include "dev_fastq.h"
 #include "fq_host.h"
 #include "fq_text.h"
@@ -64,7 +65,7 @@ __global__ __launch_bounds__(256) void k_fq_count(const uint8_t *text, uint64_t 
     const uint64_t t0 = t * tile, t1 = t0 + tile < n ? t0 + tile : n;
     uint32_t c = 0;
     for (uint64_t p = t0 + ((uint64_t)lane << 4); p < t1; p += 1024) c += (uint32_t)__popc(fq_nl_mask(text, p, t1));
-    for (int o = 32; o; o >>= 1) c += __shfl_xor(c, o, 64);
+    c = wave_sum(c);
     if (lane == 0) count[t] = c;
 }
 
@@ -85,11 +86,10 @@ __global__ __launch_bounds__(256) void k_fq_lines(const uint8_t *text, uint64_t 
         const uint64_t p = s + ((uint64_t)lane << 4);
         uint32_t m = p < t1 ? fq_nl_mask(text, p, t1) : 0u;
         const uint32_t c = (uint32_t)__popc(m);
-        uint32_t incl = c;
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_up(incl, o, 64); if ((int)lane >= o) incl += u; }
-        uint64_t w = at + (incl - c);
+        uint32_t total;
+        uint64_t w = at + wave_scan_excl(c, &total);
         while (m) { const uint32_t j = (uint32_t)__ffs(m) - 1u; m &= m - 1u; line_off[w++] = p + j + 1; }
-        at += __shfl(incl, 63, 64);
+        at += total;
     }
 }
 
@@ -116,8 +116,7 @@ __global__ __launch_bounds__(256) void k_fq_check(const uint8_t *text, uint64_t 
             A.flags[k] = (uint8_t)o.flag;
         } else key = (fq_u64)k << 2 | (fq_u64)s;
     }
-    for (int o = 32; o; o >>= 1) { const fq_u64 u = __shfl_xor(key, o, 64); key = u < key ? u : key; }
-    if ((threadIdx.x & 63) == 0 && key != ~0ull) atomicMin(first, key);          // at most one per wave, and only from a wave that holds a failing record
+    wave_report_min(first, key);          // at most one atomic per wave, and only from a wave that holds a failing record
 }
 
 // out[0, off[n]) = the fields src[k][0, off[k + 1] - off[k]) one behind the other.  One wave per `tile` output bytes (a multiple of 16, at most FQ_GATHER_MAX):

@@ -15,6 +15,7 @@
 #include <vector>
 #include "slx_internal.h"
 #include "seqlib_amd_filter.h"
+#include "dev_lanes.h"
 #include "rfilter_host.h"
 #include "slx_hip.h"
 
@@ -31,8 +32,7 @@ __global__ __launch_bounds__(256) void k_flt_eval(const uint8_t *s, const uint64
         T.dfa = d;
     }
     uint32_t kept = rf_window(s, n_bytes, rec_off, n_rec, blockIdx.x, W, V, flt_lds, &T, keep, long_list, st, st + 1, threadIdx.x, blockDim.x);
-    for (int o = 32; o; o >>= 1) kept += __shfl_xor(kept, o, 64);
-    if ((threadIdx.x & 63) == 0 && kept) atomicAdd(st + 2, kept);
+    wave_count(st + 2, kept);
 }
 
 __global__ __launch_bounds__(256) void k_flt_eval_long(const uint8_t *s, const uint64_t *rec_off, uint64_t n_rec, rf_tab T, uint32_t chunk_bases, uint8_t *keep, const uint32_t *long_list,

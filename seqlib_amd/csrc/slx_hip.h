@@ -1,6 +1,6 @@
 // slx_hip.h -- the host-side HIP plumbing the translation units of libseqlib_amd.so share: the error macros, the grow-only device and pinned buffers and
 // their tally, the event timer, one runner for hipCUB calls with their temporary storage, the device context of a handle (device, stream, events, owned buffers:
-// SlxGpu) and the intake of a batch of records.  Host code only; included from .hip files and their internal
+// SlxGpu), the intake of a batch of records and the two-pass add of the units that list their long records.  Host code only; included from .hip files and their internal
 // headers.  Nothing here is part of the C-ABI.  DESIGN.md section 9.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -8,6 +8,7 @@
 #include <atomic>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include "slx_internal.h"
 
 // A HIP call that failed ends the function: out of memory is SLX_ENOMEM, anything else SLX_ENODEVICE; the message carries the expression.
@@ -224,5 +225,51 @@ template <class Buf> static inline int slx_batch_stage(Buf &d_in, Buf &d_off, si
     SLX_CHK(d_in.ensure((size_t)n_bytes + pad)); SLX_CHK(d_off.ensure(8 * ((size_t)n + 1)));
     if (n_bytes) SLX_HIPCHK(hipMemcpyAsync(d_in.p, s, (size_t)n_bytes, hipMemcpyHostToDevice, st));
     SLX_HIPCHK(hipMemcpyAsync(d_off.p, off, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, st));
+    return SLX_OK;
+}
+
+// ------------------------------------------------------------------ a two-pass add
+// What the units that add a batch in two passes share (coverage, pileup): a lane kernel over all the records, which lists the long ones, then a wave kernel over
+// that list.  The device counters of one add stand in this order (a unit's own come behind SLX_ADD_N), and the members below are the part of the handle the
+// add works on.
+enum { SLX_ADD_ERR = 0, SLX_ADD_NLONG, SLX_ADD_COUNTED, SLX_ADD_LDS, SLX_ADD_GLOBAL, SLX_ADD_N };
+struct SlxTwoPass : SlxGpu<> {
+    explicit SlxTwoPass(const char *no_device_sentence) : SlxGpu(no_device_sentence) {}
+    SlxDevBuf<SlxMargin<4, 256>> d_long{*this}, d_cnt{*this};          // the long list; the counters (the unit's create makes d_cnt and h_cnt)
+    SlxPinBuf<SlxMargin<4, 256>> h_cnt{*this};
+    int64_t c_seen = 0, c_counted = 0, c_long = 0, c_lds = 0, c_global = 0;
+    double us_add = 0;
+};
+// The n > 0 records of a batch: the n_cnt counters are reset, lane_pass() launches the lane kernel (a record it refuses ends the call), long_pass(n_long) the wave
+// kernel when anything was listed; the span is timed and tallied.  unit: what the sentences begin with.  The stream has drained on return.
+template <class LanePass, class LongPass> static inline int slx_two_pass_add(SlxTwoPass &h, const char *unit, uint64_t n, int n_cnt, LanePass lane_pass, LongPass long_pass)
+{
+    typedef unsigned long long ull;
+    if (n >= 0x7fffffffull) { slx_set_error("%s: 2^31 records or more in one batch", unit); return SLX_EUNSUPPORTED; }
+    hipStream_t st = h.st;
+    SLX_CHK(h.d_long.ensure(8 * n));
+    ull *hc = h.h_cnt.template as<ull>(), *dc = h.d_cnt.template as<ull>();
+    memset(hc, 0, 8 * (size_t)n_cnt);
+    hc[SLX_ADD_ERR] = ~0ull;
+    SLX_HIPCHK(hipMemcpyAsync(dc, hc, 8 * (size_t)n_cnt, hipMemcpyHostToDevice, st));
+    SLX_HIPCHK(hipEventRecord(h.ev[0], st));
+    lane_pass();
+    SLX_HIPCHK(hipGetLastError());
+    SLX_HIPCHK(hipMemcpyAsync(hc, dc, 8 * (size_t)n_cnt, hipMemcpyDeviceToHost, st));
+    SLX_HIPCHK(slx_wait_stream(st));
+    if (hc[SLX_ADD_ERR] != ~0ull) {
+        slx_set_error("%s: record %llu of the batch: its fields pass its block_size, or its extent is not block_size + 4 inside the stream", unit, hc[SLX_ADD_ERR]);
+        return SLX_EIO;
+    }
+    const uint64_t n_long = hc[SLX_ADD_NLONG];
+    if (n_long) {
+        long_pass(n_long);
+        SLX_HIPCHK(hipGetLastError());
+        SLX_HIPCHK(hipMemcpyAsync(hc, dc, 8 * (size_t)n_cnt, hipMemcpyDeviceToHost, st));
+    }
+    SLX_HIPCHK(hipEventRecord(h.ev[1], st));
+    SLX_HIPCHK(slx_wait_stream(st));
+    h.us_add += slx_ev_us(h.ev[0], h.ev[1]);
+    h.c_seen += (int64_t)n; h.c_counted += (int64_t)hc[SLX_ADD_COUNTED]; h.c_long += (int64_t)n_long; h.c_lds += (int64_t)hc[SLX_ADD_LDS]; h.c_global += (int64_t)hc[SLX_ADD_GLOBAL];
     return SLX_OK;
 }

@@ -22,6 +22,7 @@
 #include <unistd.h>
 #include "slx_internal.h"
 #include "seqlib_amd_merge.h"
+#include "dev_lanes.h"
 #include "dev_wave.h"
 #include "dev_merge.h"
 #include "merge_host.h"
@@ -46,10 +47,7 @@ __global__ __launch_bounds__(256) void k_merge_key(const uint8_t *stream, uint64
             if (i + 1 == n) st->last_key = kk;
         } else { bad = i; key[i] = 0; len[i] = 0; src[i] = 0; }
     }
-    for (int o = 32; o; o >>= 1) {
-        const ull b2 = __shfl_xor(bad, o, 64), u2 = __shfl_xor(uns, o, 64);
-        bad = b2 < bad ? b2 : bad; uns = u2 < uns ? u2 : uns;
-    }
+    bad = wave_min(bad); uns = wave_min(uns);          // (both before either atomic: the two chains of shuffles run side by side)
     if ((threadIdx.x & 63) == 0) {
         if (bad != RS_NO_BAD) atomicMin(&st->bad, bad);
         if (uns != RS_NO_BAD) atomicMin(&st->unsorted, uns);

@@ -27,8 +27,8 @@ typedef SlxPinBuf<SlxMargin<4, 256>> PHBuf;
 
 static const char PILE_NO_DEVICE[] = "no HIP device: the pileup is computed on MI355X only (no CPU fallback)";
 
-struct slx_pile : SlxGpu<> {
-    slx_pile() : SlxGpu(PILE_NO_DEVICE) {}
+struct slx_pile : SlxTwoPass {
+    slx_pile() : SlxTwoPass(PILE_NO_DEVICE) {}
     std::vector<int64_t> len;
     std::vector<std::string> names;
     pile_par par = {0, 0, 0, 0, 0, 0x704u, 64u, 1024u};
@@ -36,10 +36,9 @@ struct slx_pile : SlxGpu<> {
     uint64_t stride = 0;
     uint32_t lds_window = PILE_LDS_DEFAULT, slice = 1024, group = 16;
     SlxDevBuf<SlxExact> d_arr{*this};
-    PDBuf d_in{*this}, d_off{*this}, d_long{*this}, d_cnt{*this}, d_tmp{*this}, d_n4{*this}, d_at{*this}, d_sites{*this};
-    PHBuf h_cnt{*this};
-    int64_t c_seen = 0, c_counted = 0, c_long = 0, c_lds = 0, c_global = 0, n_sites = -1;          // n_sites -1: no slx_pile_sites yet
-    double us_add = 0, us_sites = 0;
+    PDBuf d_in{*this}, d_off{*this}, d_tmp{*this}, d_n4{*this}, d_at{*this}, d_sites{*this};
+    int64_t n_sites = -1;          // n_sites -1: no slx_pile_sites yet
+    double us_sites = 0;
     int32_t *arr() const { return d_arr.as<int32_t>(); }
     size_t arr_bytes() const { return 4 * (size_t)PILE_PLANES * stride + 16; }
 };
@@ -69,7 +68,7 @@ static int pile_create_impl(slx_pile *p, int device, int n_ref, const int64_t *r
     if (p->device < 0) return SLX_OK;          // host only
     SLX_CHK(p->d_arr.ensure(p->arr_bytes()));
     SLX_HIPCHK(hipMemsetAsync(p->d_arr.p, 0, p->arr_bytes(), p->st));
-    SLX_CHK(p->d_cnt.ensure(8 * PILE_C_N)); SLX_CHK(p->h_cnt.ensure(8 * (PILE_C_N + 1)));
+    SLX_CHK(p->d_cnt.ensure(8 * SLX_ADD_N)); SLX_CHK(p->h_cnt.ensure(8 * (SLX_ADD_N + 1)));
     SLX_HIPCHK(slx_wait_stream(p->st));
     return SLX_OK;
 }
@@ -109,40 +108,20 @@ extern "C" int slx_pile_set(slx_pile *p, const char *key, int64_t v)
 static int pile_add(slx_pile *p, const uint8_t *d_s, uint64_t n_bytes, const ull *d_off, uint64_t n)
 {
     if (n == 0) return SLX_OK;
-    if (n >= 0x7fffffffull) { slx_set_error("pileup: 2^31 records or more in one batch"); return SLX_EUNSUPPORTED; }
     hipStream_t st = p->st;
-    SLX_CHK(p->d_long.ensure(8 * n));
-    ull *hc = p->h_cnt.as<ull>(), *dc = p->d_cnt.as<ull>();
-    memset(hc, 0, 8 * PILE_C_N);
-    hc[PILE_C_ERR] = ~0ull;
-    SLX_HIPCHK(hipMemcpyAsync(dc, hc, 8 * PILE_C_N, hipMemcpyHostToDevice, st));
-    SLX_HIPCHK(hipEventRecord(p->ev[0], st));
+    ull *dc = p->d_cnt.as<ull>();
     const unsigned blocks = (unsigned)((n + p->slice - 1) / p->slice);
     const uint32_t lstride = (p->lds_window + 31u) & ~31u;
     const size_t lds_bytes = 4 * (size_t)PILE_PLANES * lstride;
-    switch (p->group) {
-    case 16: k_pile_events<16><<<blocks, 256, lds_bytes, st>>>(d_s, n_bytes, d_off, n, p->par, p->arr(), p->stride, p->slice, p->lds_window, lstride, p->d_long.as<ull>(), dc); break;
-    case 32: k_pile_events<32><<<blocks, 256, lds_bytes, st>>>(d_s, n_bytes, d_off, n, p->par, p->arr(), p->stride, p->slice, p->lds_window, lstride, p->d_long.as<ull>(), dc); break;
-    default: k_pile_events<64><<<blocks, 256, lds_bytes, st>>>(d_s, n_bytes, d_off, n, p->par, p->arr(), p->stride, p->slice, p->lds_window, lstride, p->d_long.as<ull>(), dc); break;
-    }
-    SLX_HIPCHK(hipGetLastError());
-    SLX_HIPCHK(hipMemcpyAsync(hc, dc, 8 * PILE_C_N, hipMemcpyDeviceToHost, st));
-    SLX_HIPCHK(slx_wait_stream(st));
-    if (hc[PILE_C_ERR] != ~0ull) {
-        slx_set_error("pileup: record %llu of the batch: its fields pass its block_size, or its extent is not block_size + 4 inside the stream", hc[PILE_C_ERR]);
-        return SLX_EIO;
-    }
-    const uint64_t n_long = hc[PILE_C_NLONG];
-    if (n_long) {
-        k_pile_events_long<<<(unsigned)((n_long + 3) / 4), 256, 0, st>>>(d_s, d_off, p->d_long.as<ull>(), n_long, p->par, p->arr(), p->stride, dc);
-        SLX_HIPCHK(hipGetLastError());
-        SLX_HIPCHK(hipMemcpyAsync(hc, dc, 8 * PILE_C_N, hipMemcpyDeviceToHost, st));
-    }
-    SLX_HIPCHK(hipEventRecord(p->ev[1], st));
-    SLX_HIPCHK(slx_wait_stream(st));
-    p->us_add += slx_ev_us(p->ev[0], p->ev[1]);
-    p->c_seen += (int64_t)n; p->c_counted += (int64_t)hc[PILE_C_COUNTED]; p->c_long += (int64_t)n_long; p->c_lds += (int64_t)hc[PILE_C_LDS]; p->c_global += (int64_t)hc[PILE_C_GLOBAL];
-    return SLX_OK;
+    return slx_two_pass_add(*p, "pileup", n, SLX_ADD_N,
+        [&]() {
+            switch (p->group) {
+            case 16: k_pile_events<16><<<blocks, 256, lds_bytes, st>>>(d_s, n_bytes, d_off, n, p->par, p->arr(), p->stride, p->slice, p->lds_window, lstride, p->d_long.as<ull>(), dc); break;
+            case 32: k_pile_events<32><<<blocks, 256, lds_bytes, st>>>(d_s, n_bytes, d_off, n, p->par, p->arr(), p->stride, p->slice, p->lds_window, lstride, p->d_long.as<ull>(), dc); break;
+            default: k_pile_events<64><<<blocks, 256, lds_bytes, st>>>(d_s, n_bytes, d_off, n, p->par, p->arr(), p->stride, p->slice, p->lds_window, lstride, p->d_long.as<ull>(), dc); break;
+            }
+        },
+        [&](uint64_t n_long) { k_pile_events_long<<<(unsigned)((n_long + 3) / 4), 256, 0, st>>>(d_s, d_off, p->d_long.as<ull>(), n_long, p->par, p->arr(), p->stride, dc); });
 }
 
 extern "C" int slx_pile_add_device(slx_pile *p, const void *d_stream, int64_t n_bytes, const void *d_rec_off, int64_t n_records)
@@ -176,7 +155,7 @@ extern "C" int slx_pile_record_events(const uint8_t *rec, int64_t n, int min_bas
     P.tid = F.tid;          // (whatever contig the record names stands for the window's)
     if (pile_head(rec, (uint64_t)n, P, &F) == PILE_R_SKIP) return SLX_OK;
     PileHostSink S = {plane, pos, cap, 0};
-    pile_record(F, P, 0u, 1u, pile_one(), S);
+    pile_record(F, P, 0u, 1u, lanes_one(), S);
     *n_out = S.n;
     if (S.n > cap) { slx_set_error("slx_pile_record_events: %lld events, out holds %lld", (long long)S.n, (long long)cap); return SLX_EINVAL; }
     return SLX_OK;

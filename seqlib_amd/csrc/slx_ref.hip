@@ -26,6 +26,7 @@
 #include "slx_hip.h"
 #include "seqlib_amd_ref.h"
 #include "fq_text.h"
+#include "dev_lanes.h"
 #include "dev_wave.h"
 #include "ref_host.h"
 
@@ -79,8 +80,7 @@ __global__ __launch_bounds__(256) void k_ref_check(const rg_line *li, const ull 
         const uint32_t er = rg_check_line(li[j].nb, li[j].width, li[j].bad, lb, lw, is_last, prev_blank);
         if (er) key = (ull)j << 3 | er;
     }
-    for (int o = 32; o; o >>= 1) { const ull u = __shfl_xor(key, o, 64); key = u < key ? u : key; }
-    if ((threadIdx.x & 63) == 0 && key != ~0ull) atomicMin(first, key);
+    wave_report_min(first, key);
 }
 
 // out[o0, o1) from the segments: byte p belongs to the last segment k with dst[k] <= p; it is that segment's byte p - dst[k] when that is below cnt[k], and 0
@@ -181,8 +181,7 @@ __global__ __launch_bounds__(256) void k_md_size(md_args A, int32_t *nm, ull *sz
         }
         nm[i] = v; sz[i] = size;
     }
-    for (int o = 32; o; o >>= 1) { const ull u = __shfl_xor(bad, o, 64); bad = u < bad ? u : bad; }
-    if ((threadIdx.x & 63) == 0 && bad != ~0ull) atomicMin(cnt, bad);
+    wave_report_min(cnt, bad);
 }
 
 __global__ __launch_bounds__(256) void k_md_text(md_args A, const int32_t *nm, const ull *mdoff, uint8_t *md)

@@ -37,20 +37,6 @@ typedef unsigned long long ull;
 #define SAMW_STAGE (16ull << 20)  // bytes of text one pinned staging buffer holds (knob "stage_bytes")
 
 // ------------------------------------------------------------------ kernels
-// what the 64 lanes of a wave share (all of them call together)
-struct samw_wave {
-    __device__ __forceinline__ uint64_t sum(uint64_t v) const { for (int o = 32; o; o >>= 1) v += (uint64_t)__shfl_xor((ull)v, o, 64); return v; }
-    __device__ __forceinline__ uint64_t min(uint64_t v) const { for (int o = 32; o; o >>= 1) { const uint64_t u = (uint64_t)__shfl_xor((ull)v, o, 64); v = u < v ? u : v; } return v; }
-    __device__ __forceinline__ uint32_t scan(uint32_t v, uint32_t *total) const
-    {
-        const uint32_t lane = threadIdx.x & 63;
-        uint32_t x = v;
-        for (uint32_t o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(x, o, 64); if (lane >= o) x += y; }
-        *total = __shfl(x, 63, 64);
-        return x - v;
-    }
-};
-
 // size[k] = bytes of record k's line when it is FAST, else 0; size[n] = 0; verdict[k] = verdict | error << 2; fld[k]; extra[k] = waves beyond the first that fill it;
 // *cnt += records that are not FAST | records sized by the wave << 32
 __global__ __launch_bounds__(256) void k_samw_size(const uint8_t *s, uint64_t n_bytes, const ull *rec_off, uint64_t n, samw_refs R, int fast_fail, ull *size, uint8_t *verdict, samw_fld *fld,
@@ -64,7 +50,7 @@ __global__ __launch_bounds__(256) void k_samw_size(const uint8_t *s, uint64_t n_
     if (k < n) {
         b = rec_off[k]; e = rec_off[k + 1];
         if (b > e || e > n_bytes) { v = SAMW_ERROR; err = SAMW_E_SPAN; }
-        else v = samw_line(s + b, e - b, R, &F, (uint8_t *)nullptr, &sz, &err, 0u, 1u, samw_one(), samw_no_float(), SAMW_WIDE);
+        else v = samw_line(s + b, e - b, R, &F, (uint8_t *)nullptr, &sz, &err, 0u, 1u, lanes_one(), samw_no_float(), SAMW_WIDE);
     }
     const ull wide = __ballot(v == SAMW_DEFER);
     for (ull m = wide; m; m &= m - 1ull) {          // (wave-uniform: all 64 lanes size the record of lane j together)
@@ -73,7 +59,7 @@ __global__ __launch_bounds__(256) void k_samw_size(const uint8_t *s, uint64_t n_
         samw_fld Fj = {};
         uint64_t szj = 0;
         int errj = SAMW_E_NONE;
-        const int vj = samw_line(s + bj, ej - bj, R, &Fj, (uint8_t *)nullptr, &szj, &errj, lane, 64u, samw_wave(), samw_no_float(), SAMW_NO_DEFER);
+        const int vj = samw_line(s + bj, ej - bj, R, &Fj, (uint8_t *)nullptr, &szj, &errj, lane, 64u, lanes_group<>(), samw_no_float(), SAMW_NO_DEFER);
         if ((int)lane == j) { v = vj; F = Fj; sz = szj; err = errj; }
     }
     if (k < n) {
@@ -124,7 +110,7 @@ __global__ __launch_bounds__(256) void k_samw_fill(const uint8_t *s, const ull *
     const uint8_t *r = s + rec_off[k];
     uint64_t sz = 0;
     int err;
-    (void)samw_line(r, rec_off[k + 1] - rec_off[k], R, &F, o, &sz, &err, lane, 64u, samw_wave(), samw_no_float(), SAMW_NO_DEFER);
+    (void)samw_line(r, rec_off[k + 1] - rec_off[k], R, &F, o, &sz, &err, lane, 64u, lanes_group<>(), samw_no_float(), SAMW_NO_DEFER);
     samw_bulk(r, F, o, lane, 64u * (extra[k] + 1));
 }
 

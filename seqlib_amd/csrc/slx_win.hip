@@ -21,6 +21,7 @@
 #include "slx_internal.h"
 #include "slx_hip.h"
 #include "seqlib_amd_win.h"
+#include "dev_lanes.h"
 #include "dev_wave.h"
 #include "dev_win.h"
 
@@ -37,13 +38,6 @@ struct wn_state { ull bad; uint32_t n_long, max_len; uint32_t drop[WN_N_STATUS];
 struct wn_args { const uint8_t *s; uint64_t n_bytes; const uint64_t *off; uint64_t n; };
 
 // ------------------------------------------------------------------ kernels
-__device__ __forceinline__ void wn_report(bool broken, uint64_t i, wn_state *st)
-{
-    ull bad = broken ? i : ED_NONE;
-    for (int o = 32; o; o >>= 1) { const ull b2 = __shfl_xor(bad, o, 64); bad = b2 < bad ? b2 : bad; }
-    if ((threadIdx.x & 63) == 0 && bad != ED_NONE) atomicMin(&st->bad, bad);
-}
-
 __global__ __launch_bounds__(256) void k_win_measure(wn_rules R, wn_args A, wn_rec *M, ull *sz, uint32_t *longlist, wn_state *st)
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -67,7 +61,7 @@ __global__ __launch_bounds__(256) void k_win_measure(wn_rules R, wn_args A, wn_r
         M[i] = m;
         sz[i] = m.status == WN_KEEP ? wn_padded(m.klen) : 0;
     }
-    wn_report(broken, i, st);
+    wave_report_min(&st->bad, broken, i);
 }
 
 // (only records that k_win_measure has selected are listed: their fields lie inside their spans)
@@ -127,7 +121,7 @@ __global__ __launch_bounds__(256) void k_win_lens(const wn_entry *ent, const uin
     uint32_t l = 0;
     if (i == n) len[i] = 0;
     if (i < n) { const wn_entry E = ent[idx[i]]; l = E.len; len[i] = l; rec_of_read[i] = E.ord; }
-    for (int o = 32; o; o >>= 1) { const uint32_t l2 = (uint32_t)__shfl_xor((int)l, o, 64); l = l2 > l ? l2 : l; }
+    l = wave_max(l);
     if ((threadIdx.x & 63) == 0 && l) atomicMax(&st->max_len, l);
 }
 

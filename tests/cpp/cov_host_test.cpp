@@ -4,7 +4,8 @@
 //   cov_host_test dec VALUE...      prints every value through cov_dec_put / cov_depth_put, one per line
 //   cov_host_test cases FILE        lines of FILE:
 //     R n_ref (name len)...                              the contigs
-//     C name hex eligible mode buff count_del beg end n (lo hi)...   cov_head's verdict with the default parameters, and cov_record's intervals for the clip [beg, end);
+//     C name hex eligible mode buff count_del beg end n (lo hi)...   cov_head's verdict with the default parameters, and cov_record's intervals for the clip [beg, end),
+//                                                        by one lane and by the 64 lanes of tests/cpp/lanes_sim.h (the same intervals as a multiset);
 //                                                        the record lies in a heap block of exactly its size, so a byte read past it is a sanitizer report
 //     B mode buff count_del include_zero hex             all C records so far through cov_head + cov_record into the difference array of the layout, a prefix sum,
 //                                                        and cov_bg_piece over every entry: the text
@@ -17,7 +18,9 @@
 #include <sstream>
 #include <string>
 #include <vector>
+#include <algorithm>
 #include "cov_host.h"
+#include "lanes_sim.h"
 
 static int g_fail = 0;
 #define CHECK(c, ...) do { if (!(c)) { std::fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__); std::fprintf(stderr, __VA_ARGS__); std::fprintf(stderr, "\n"); ++g_fail; } } while (0)
@@ -71,13 +74,23 @@ static int run_cases(const char *path)
             CHECK(v != COV_R_LONG || F.n_cig > 64, "%s: LONG with %u ops", name.c_str(), F.n_cig);
             const cov_par P = {mode, buff, cd, 0, 0u, 1u << 20};
             ListSink S;
-            if (cov_head(h, r.size(), P, 0x7fffffff, &F) > COV_R_SKIP) {
-                const int64_t o = 0;
-                const cov_geo G = {&cb, &ce, &o, 1, 0, 0};
+            const int64_t o = 0;
+            const cov_geo G = {&cb, &ce, &o, 1, 0, 0};
+            const bool elig_walk = cov_head(h, r.size(), P, 0x7fffffff, &F) > COV_R_SKIP;
+            if (elig_walk) {
                 F.tid = 0;
-                cov_record(F, P, G, 0u, 1u, cov_one(), S);
+                cov_record(F, P, G, 0u, 1u, lanes_one(), S);
             }
             CHECK(S.v == want, "%s mode %d buff %d count_del %d: %zu intervals, expected %zu", name.c_str(), mode, buff, cd, S.v.size(), want.size());
+            // the same record by 64 lanes that call together (the long-record kernel's path): the same intervals in some other order
+            if (elig_walk) {
+                std::vector<ListSink> sinks(64);
+                lanes_run(64u, [&](uint32_t l, const GroupLane &W) { cov_record(F, P, G, l, 64u, W, sinks[l]); });
+                std::vector<std::pair<int64_t, int64_t>> got, one = S.v;
+                for (const ListSink &s : sinks) got.insert(got.end(), s.v.begin(), s.v.end());
+                std::sort(got.begin(), got.end()); std::sort(one.begin(), one.end());
+                CHECK(got == one, "%s mode %d buff %d count_del %d with 64 lanes: %zu intervals, one lane gives %zu", name.c_str(), mode, buff, cd, got.size(), one.size());
+            }
             // cut short, the record is refused, never read past
             for (size_t cut : {(size_t)0, (size_t)35, r.size() - 1}) {
                 uint8_t *q = (uint8_t *)malloc(cut ? cut : 1);
@@ -99,7 +112,7 @@ static int run_cases(const char *path)
             ArraySink S = {&a, &G};
             for (const std::string &r : recs) {
                 rf_feat F;
-                if (cov_head((const uint8_t *)r.data(), r.size(), P, G.n_ref, &F) > COV_R_SKIP) cov_record(F, P, G, 0u, 1u, cov_one(), S);
+                if (cov_head((const uint8_t *)r.data(), r.size(), P, G.n_ref, &F) > COV_R_SKIP) cov_record(F, P, G, 0u, 1u, lanes_one(), S);
             }
             for (uint64_t g = 1; g < total; ++g) a[g] += a[g - 1];
             std::string nm; std::vector<uint32_t> noff(1, 0);

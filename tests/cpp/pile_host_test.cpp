@@ -4,11 +4,10 @@
 //   pile_host_test cases FILE        lines of FILE:
 //     C name hex eligible min_baseq many beg end n (plane pos)...   pile_head's verdict for the window [beg, end) of contig 2 with the default parameters, and
 //                                    pile_record's events for that window.  The record lies in a heap block of exactly its size, so a byte read past it is a
-//                                    sanitizer report.  The body runs with 1 lane and, when many is 1, with 16 and 64 lanes: a lane is a thread, the group's prefix sum and broadcast go
-//                                    through a barrier, as the lanes of a GPU group run in step.  One lane gives the events in the walk's order; 16 and 64
+//                                    sanitizer report.  The body runs with 1 lane and, when many is 1, with 16 and 64 lanes: a lane is a thread of lanes_sim.h's
+//                                    simulated group.  One lane gives the events in the walk's order; 16 and 64
 //                                    lanes give the same events in some other order.
 //     S min_depth min_alt num den ref_byte c0..c14 is_site ref depth alt ins     pile_site on one position
-#include <pthread.h>
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -17,9 +16,9 @@
 #include <fstream>
 #include <sstream>
 #include <string>
-#include <thread>
 #include <utility>
 #include <vector>
+#include "lanes_sim.h"
 #include "pile_host.h"
 
 static int g_fail = 0;
@@ -40,45 +39,11 @@ struct ListSink {
     void operator()(uint32_t plane, int64_t x) { v.push_back({(int32_t)plane, x}); }
 };
 
-// what the lanes of a simulated group share: two sets of slots taken in turn, so that one barrier a collective is enough (a lane that writes set k again has
-// passed the barrier of the collective on the other set, behind which every lane has read set k)
-struct Group {
-    pthread_barrier_t bar;
-    uint64_t slot[2][64];
-    uint32_t nlanes;
-};
-struct GroupLane {
-    Group *g; uint32_t lane; mutable uint32_t turn;
-    const uint64_t *exchange(uint64_t v) const
-    {
-        uint64_t *s = g->slot[turn & 1u];
-        ++turn;
-        s[lane] = v;
-        pthread_barrier_wait(&g->bar);
-        return s;
-    }
-    uint64_t scan(uint64_t v, uint64_t *total) const
-    {
-        const uint64_t *s = exchange(v);
-        uint64_t before = 0, all = 0;
-        for (uint32_t i = 0; i < g->nlanes; ++i) { if (i < lane) before += s[i]; all += s[i]; }
-        *total = all;
-        return before;
-    }
-    uint64_t bcast(uint64_t v, uint32_t j) const { return exchange(v)[j]; }
-};
-
 static Events run_lanes(const rf_feat &F, const pile_par &P, uint32_t nlanes)
 {
-    if (nlanes == 1) { ListSink S; pile_record(F, P, 0u, 1u, pile_one(), S); return S.v; }
-    Group g;
-    g.nlanes = nlanes;
-    pthread_barrier_init(&g.bar, nullptr, nlanes);
+    if (nlanes == 1) { ListSink S; pile_record(F, P, 0u, 1u, lanes_one(), S); return S.v; }
     std::vector<ListSink> sinks(nlanes);
-    std::vector<std::thread> th;
-    for (uint32_t l = 0; l < nlanes; ++l) th.emplace_back([&, l]() { GroupLane W = {&g, l, 0u}; pile_record(F, P, l, nlanes, W, sinks[l]); });
-    for (auto &t : th) t.join();
-    pthread_barrier_destroy(&g.bar);
+    lanes_run(nlanes, [&](uint32_t l, const GroupLane &W) { pile_record(F, P, l, nlanes, W, sinks[l]); });
     Events all;
     for (const ListSink &s : sinks) all.insert(all.end(), s.v.begin(), s.v.end());
     return all;

@@ -45,12 +45,12 @@ static int dev_line(const uint8_t *r, uint64_t n, const samw_refs &R, std::strin
     samw_fld F;
     memset(&F, 0, sizeof F);
     uint64_t size = 0, size2 = 0;
-    int v = samw_line(r, n, R, &F, (uint8_t *)nullptr, &size, err, 0u, 1u, samw_one(), samw_no_float(), defer);
+    int v = samw_line(r, n, R, &F, (uint8_t *)nullptr, &size, err, 0u, 1u, lanes_one(), samw_no_float(), defer);
     line.clear();
     if (v != SAMW_FAST) return v;
     uint8_t *out = (uint8_t *)malloc(size);          // exactly the size: a byte written past it is a sanitizer report
     memset(out, 0xa5, size);
-    v = samw_line(r, n, R, &F, out, &size2, err, 0u, 1u, samw_one(), samw_no_float(), SAMW_NO_DEFER);
+    v = samw_line(r, n, R, &F, out, &size2, err, 0u, 1u, lanes_one(), samw_no_float(), SAMW_NO_DEFER);
     if (v == SAMW_FAST && size2 == size) samw_bulk(r, F, out, 0, 1); else v = -1;
     line.assign((const char *)out, size);
     free(out);

@@ -21,7 +21,7 @@ CLIPS = [(0, 1 << 40), (0, 5000), (100, 300), (4990, 5000), (0, 1)]
 def exe(tmp_path_factory):
     """tests/cpp/cov_host_test.cpp under ASan and UBSan: a program of its own, nothing is loaded into Python"""
     out = str(tmp_path_factory.mktemp("cov") / "cov_host_test")
-    subprocess.check_call(["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g", "-O1", "-Wall", "-Werror",
+    subprocess.check_call(["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g", "-O1", "-Wall", "-Werror", "-pthread",
                            "-I" + os.path.join(ROOT, "seqlib_amd", "csrc"), "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "cov_host_test.cpp"), "-o", out])
     return out
 
