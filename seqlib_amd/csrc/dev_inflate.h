@@ -2,7 +2,7 @@
 // k_bgzf_crc (slx_bam.hip), kept apart and host-compilable so that tests/cpp/inflate_host_test.cpp can hold them against zlib under ASan + UBSan
 // before they ever run on a GPU.  Restated from the RFCs; no library decompressor.
 //
-// Work split inside a wave (`lane` of `nlanes`; the host build runs it as lane 0 of 1):
+// Work split inside a wave (`lane` of `nlanes`; the host build runs it as lane 0 of 1, and tests/cpp/inflate_lanes_test.cpp as 7 and 64 threads under ThreadSanitizer):
 //   * the bit stream is decoded redundantly by every lane: one address per load (a broadcast), wave-uniform control flow, no cross-lane traffic per symbol;
 //   * the decode tables live in LDS, built per deflate block: lane 0 counts and sorts the code lengths (the canonical order), then all lanes fill the
 //     first-level lookup tables (10 bits literal/length, 8 bits distance), each entry by a canonical decode of its own index;
@@ -19,7 +19,9 @@
 #else
 #define INF_FN static inline
 #define INF_TAB static const
+#ifndef INF_SYNC        // tests/cpp/inflate_lanes_test.cpp runs the lanes as threads and makes this a barrier
 #define INF_SYNC() do { } while (0)
+#endif
 #endif
 
 enum {

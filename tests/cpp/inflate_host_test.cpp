@@ -4,8 +4,10 @@
 //      (1, 7 and 64 slices) equals zlib's crc32;
 //   2. seeded single-byte and single-bit damage of every member (argv[2] variants each): the decoder returns an error, or INF_OK with exactly ISIZE bytes --
 //      and the sanitizers see no access outside the member's compressed bytes and its ISIZE bytes of output;
-//   3. hand-made malformed streams end with the error code that names them.
-// Prints "<members> members <damaged> damaged <bad> bad".
+//   3. hand-made malformed streams end with the error code that names them;
+//   4. with argv[3] (tests/test_inflate_foreign.py: repeated {u32 size, u32 ISIZE, u32 expected code or 0, deflate bytes}), streams that zlib refuses or does not
+//      end: inf_member returns non-zero exactly when zlib does not end the stream with ISIZE bytes, and the expected code where one is given.
+// Prints "<members> members <damaged> damaged <bad> bad", and before it "<refused> refused <bad> bad" when there is an argv[3].
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -101,6 +103,33 @@ int main(int argc, char **argv)
     { BitW w; w.put(1, 1); w.put(2, 2); w.put(30, 5); w.put(0, 5); w.put(0, 4); w.put(0, 32); expect("HLIT above 286", w.b, 10, INF_E_CODE); }
     { BitW w; w.put(1, 1); w.put(1, 2); w.put(0x63, 8); w.put(0, 16); expect("length symbol 286", w.b, 10, INF_E_SYM); }          // fixed 11000110 -> symbol 286, sent MSB first
     { std::vector<uint8_t> e; expect("empty input", e, 0, INF_E_EOF); }
+    // the refused set (argv[3]: repeated {u32 size, u32 ISIZE, u32 expected code or 0 for any non-zero, bytes}): zlib does not end the stream with ISIZE bytes exactly
+    // when inf_member returns non-zero, and with the code named where one is
+    if (argc > 3) {
+        FILE *g = fopen(argv[3], "rb");
+        if (!g) return 2;
+        long refused = 0, rbad = 0;
+        uint32_t h3[3];
+        while (fread(h3, 4, 3, g) == 3) {
+            comp.resize(h3[0]);
+            if (h3[0] && fread(comp.data(), 1, h3[0], g) != h3[0]) return 2;
+            ++refused;
+            std::vector<uint8_t> want(h3[1] + 1);
+            z_stream zs; memset(&zs, 0, sizeof zs);
+            inflateInit2(&zs, -15);
+            zs.next_in = comp.data(); zs.avail_in = h3[0]; zs.next_out = want.data(); zs.avail_out = h3[1];
+            const int zr = inflate(&zs, Z_FINISH);
+            const bool zok = zr == Z_STREAM_END && zs.total_out == h3[1];
+            inflateEnd(&zs);
+            const int e = run(comp.data(), h3[0], h3[1], got);
+            if (zok) { printf("refused %ld: zlib accepts it\n", refused); ++rbad; }
+            if (zok != (e == INF_OK)) { printf("refused %ld: zlib %s, inf_member %d\n", refused, zok ? "accepts" : "refuses", e); ++rbad; }
+            if (h3[2] && e != (int)h3[2]) { printf("refused %ld: code %d, expected %u\n", refused, e, h3[2]); ++rbad; }
+        }
+        fclose(g);
+        printf("%ld refused %ld bad\n", refused, rbad);
+        bad += rbad;
+    }
     printf("%ld members %ld damaged %ld bad\n", members, damaged, bad);
     return bad ? 1 : 0;
 }

@@ -1,6 +1,7 @@
 """CPU tests of the BamReader path (include/seqlib_amd_bam.h, seqlib_amd/csrc/slx_bam.hip): the exports, the host-side member scan against the Python
 statement of BGZF (tests/bam_util.py), the refusal without a GPU, the host-compiled DEFLATE / CRC32 bodies against zlib under ASan + UBSan, and the
-record index's algorithm restated in scalar C against the plain chain walk.  No test here needs a GPU."""
+record index's algorithm restated in scalar C against the plain chain walk.  No test here needs a GPU.
+DEFLATE that zlib never writes, streams it refuses and the 64-lane host run are in tests/test_inflate_foreign.py."""
 import json
 import os
 import random

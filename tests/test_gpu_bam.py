@@ -1,7 +1,8 @@
 """GPU tests of the BamReader path at the C-ABI (include/seqlib_amd_bam.h through seqlib_amd/bamio.py): k_bgzf_inflate + k_bgzf_crc against zlib on every
 compression setting and payload of the corpus, the error paths (a flipped CRC byte, one damaged deflate byte -- the input the host-compiled build has
 passed under the sanitizers in tests/test_bam_reader.py), records and header against the Python parser over a sweep of batch sizes, and the index's
-repair path (the decoy, idx_fail).  The C++ class is driven in tests/test_cpp_bam.py."""
+repair path (the decoy, idx_fail).  The C++ class is driven in tests/test_cpp_bam.py.
+Members no zlib writes (other encoders' valid DEFLATE, crafted bit by bit) go through the same kernels in tests/test_gpu_inflate_foreign.py."""
 import pytest
 
 from tests import bam_util as bu
